@@ -9,12 +9,16 @@ stream (seed 20260102), cut at ARBITRARY byte offsets (not record aligned), scan
 exchange their 32-word partials with one RCCL all-gather issued by the C library itself (scfq_comm_*: its own rendezvous,
 librccl; the combine is ordered / non-commutative, so a sum-allreduce of counters would be wrong)
 -> "scaling": "weak".  torch.distributed only provides the contract's barrier and the max over ranks (control plane: gloo by
-default, so that the library's RCCL communicator is the only one a rank creates).  At N=1 the line also carries a non-headline
-`ingest` object: a gzip member and a BGZF file of the same stream, written here, counted by a fresh `sc fq-count` process (cold)
-and by the second call in this process (warm) — BASELINE configs[3] end to end, compressed bytes over PCIe, inflate on the device —
-and a non-headline `dedup` object: the fq-dedup pipeline over a resident 10 GB input with one record in six repeated.
+default, so that the library's RCCL communicator is the only one a rank creates).
 
-Launch:  python bench.py --gpus 1 --steps K --warmup W
+A plain run sets up, warms up, times the steps and prints the line.  With --full, the line also carries what takes runs of its
+own: the scan's read-stream ceiling and the offline PMC traffic in `roofline`, and at N=1 the `cpu_baseline` / `cpu_all_cores`
+objects, a non-headline `ingest` object (a gzip member and a BGZF file of the same stream, written here, counted by a fresh
+`sc fq-count` process (cold) and by the second call in this process (warm) — BASELINE configs[3] end to end, compressed bytes over
+PCIe, inflate on the device) and a non-headline `dedup` object (the fq-dedup pipeline, SURVEY.md §8f-3, over a resident 10 GB input
+with one record in six repeated).  --dump-outputs DIR writes the counters of the last timed step as DIR/<field>.npy (float64).
+
+Launch:  python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 Rank 0 prints ONE JSON line.
 """
@@ -353,7 +357,14 @@ def main():
                     help="rehearsal only: every rank uses cuda:0 (1-GPU box, gloo backend); the number is not a scaling result")
     ap.add_argument("--exchange-at-1", action="store_true",
                     help="rehearsal only: run the N>1 exchange path (helper thread + collective) with a single rank")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: stream ceiling and PMC traffic of the roofline, and at N=1 the "
+                         "CPU baselines and the non-headline ingest and dedup objects")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the counters of the last timed step as DIR/<field>.npy (float64; rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -611,6 +622,14 @@ def main():
     exact = (counts.gc_bases, counts.n_bases, counts.bases, counts.reads) == tuple(tallies.tolist())
     assert exact or args.no_verify, ("scan disagrees with generator tallies", counts.gc_bases, counts.n_bases, counts.bases,
                    counts.reads, tallies.tolist())
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives (scfq_partial_finalize's scfq_counts, all ranks folded): every field is a count
+        # below 2^53, so float64 holds it exactly
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name in ("reads", "gc_bases", "n_bases", "bases", "lines", "newlines", "input_bytes", "bad_at", "bad_plus"):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.array([getattr(counts, name)], dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, "qual_hist.npy"), np.array(list(counts.qual_hist), dtype=np.float64))
 
     total_bases = counts.bases   # bases of the WHOLE job (all ranks' shards folded)
     value = total_bases * args.steps / elapsed / 1e9
@@ -665,7 +684,7 @@ def main():
     mirror_fallback = bool(exchange and args.exchange == "lib" and any(r["exchange_path"] != "library" for r in per_rank))
     # the same device's read-stream ceiling: the scan kernel's load structure with no compute (diagnostic kernel)
     al = (-shard_ptr) % 4096
-    if shard_n > al + (1 << 20):
+    if args.full and shard_n > al + (1 << 20):
         sm = scfq.debug_stream_ms(shard_ptr + al, shard_n - al, 5)
         if sm > 0:
             sbytes = (shard_n - al) // 4096 * 4096
@@ -674,7 +693,7 @@ def main():
             out["roofline"]["frac_of_stream_ceiling"] = round(achieved / (sbytes / (sm * 1e-3) / 1e9), 4)
     # PMC traffic measured offline with rocprofv3 (separate --pmc pass), if committed for this workload
     pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-    if os.path.exists(pmc) and args.flags == 0 and kind == 0:
+    if args.full and os.path.exists(pmc) and args.flags == 0 and kind == 0:
         try:
             with open(pmc) as f:
                 j = json.load(f)
@@ -690,7 +709,7 @@ def main():
             pass
 
     # ---- CPU baseline: reference-shaped restatement on ONE host core, bounded sample of the same bytes ---
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import numpy as np
         L, OC = load_oracle()
         sample = int(min(args.cpu_sample_bytes, shard_n))
@@ -725,7 +744,7 @@ def main():
                                 "note": "optimised CPU restatement: byte-range shards + the same ordered fold, byte-serial scan per shard"}
         del host
     side_leg_failed = False
-    if rank == 0 and world == 1 and args.ingest_bytes > 0 and kind == 0 and args.flags == 0:
+    if args.full and rank == 0 and world == 1 and args.ingest_bytes > 0 and kind == 0 and args.flags == 0:
         del buf          # (the 10 GB workload: the ingest legs measure processes of their own, beside a parent that holds little)
         torch.cuda.empty_cache()
         # (non-headline: a failure here — no room for the files, a host short of memory — is reported in the object, never allowed to take

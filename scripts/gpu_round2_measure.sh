@@ -2,11 +2,12 @@
 # Round-2 measurement pass on the GPU box (run through gpurun in pieces: see the calls in the round's log).
 # usage: scripts/gpu_round2_measure.sh <part>     part = tests | bench | aux | prof | inflate
 TAG=r02; mkdir -p gpurun_out/$TAG
+OUT=${BENCH_OUT:-bench_out}/$TAG; mkdir -p "$OUT"      # the --full bench line
 case "$1" in
 tests)
   python -m pytest tests -q -m gpu 2>&1 | tail -6 | tee gpurun_out/$TAG/pytest_gpu.txt ;;
 bench)
-  python bench.py --steps 30 --warmup 3 2>gpurun_out/$TAG/bench.err | tail -1 | tee gpurun_out/$TAG/bench_n1.json | cut -c1-300
+  python bench.py --steps 30 --warmup 3 --full 2>"$OUT/bench.err" | tail -1 | tee "$OUT/bench_n1.json" | cut -c1-300
   python bench.py --steps 10 --warmup 2 --no-cpu-baseline --flags 2 2>/dev/null | tail -1 > gpurun_out/$TAG/bench_struct.json
   python bench.py --steps 10 --warmup 2 --no-cpu-baseline --flags 1 2>/dev/null | tail -1 > gpurun_out/$TAG/bench_hist.json
   python bench.py --steps 10 --warmup 2 --no-cpu-baseline --flags 3 2>/dev/null | tail -1 > gpurun_out/$TAG/bench_hist_struct.json

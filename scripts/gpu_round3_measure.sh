@@ -2,10 +2,11 @@
 # Round-3 measurement pass on the GPU box (run through gpurun in pieces).
 # usage: scripts/gpu_round3_measure.sh <part>     part = bench | gz | cold | prof | aux
 TAG=r03; mkdir -p gpurun_out/$TAG
+OUT=${BENCH_OUT:-bench_out}/$TAG; mkdir -p "$OUT"      # the --full bench line
 case "$1" in
 bench)
-  python bench.py --steps 30 --warmup 3 2>gpurun_out/$TAG/bench.err | tail -1 | tee gpurun_out/$TAG/bench_n1.json | cut -c1-400
-  python -c "import json;d=json.load(open('gpurun_out/$TAG/bench_n1.json'));print(json.dumps(d.get('ingest'),indent=1))" ;;
+  python bench.py --steps 30 --warmup 3 --full 2>"$OUT/bench.err" | tail -1 | tee "$OUT/bench_n1.json" | cut -c1-400
+  python -c "import json;d=json.load(open('$OUT/bench_n1.json'));print(json.dumps(d.get('ingest'),indent=1))" ;;
 gz)
   python scripts/measure_gz_device.py 1e9 /tmp > gpurun_out/$TAG/gz_device.jsonl 2>gpurun_out/$TAG/gzd.err
   python scripts/measure_gz_device.py 2e9 /tmp >> gpurun_out/$TAG/gz_device.jsonl 2>>gpurun_out/$TAG/gzd.err

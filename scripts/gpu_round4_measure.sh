@@ -2,9 +2,10 @@
 # Round-4 measurement pass on the GPU box (run through gpurun in pieces).
 # usage: scripts/gpu_round4_measure.sh <part>     part = bench | gz | cold | prof | aux | hist | dedup
 TAG=r04; mkdir -p gpurun_out/$TAG
+OUT=${BENCH_OUT:-bench_out}/$TAG; mkdir -p "$OUT"      # the --full bench line
 case "$1" in
 bench)
-  python3 bench.py --gpus 1 --steps 20 --warmup 5 2>gpurun_out/$TAG/bench.err | tail -1 | tee gpurun_out/$TAG/bench_n1.json | cut -c1-400 ;;
+  python3 bench.py --gpus 1 --steps 20 --warmup 5 --full 2>"$OUT/bench.err" | tail -1 | tee "$OUT/bench_n1.json" | cut -c1-400 ;;
 anchor)
   python3 bench.py --gpus 1 --steps 20 --warmup 5 --bytes-per-gpu 25e9 --no-cpu-baseline --ingest-bytes 0 2>gpurun_out/$TAG/bench_anchor.err | tail -1 | tee gpurun_out/$TAG/bench_n1_anchor_25GB.json | cut -c1-600 ;;
 gz)

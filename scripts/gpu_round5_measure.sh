@@ -3,9 +3,10 @@
 # usage: scripts/gpu_round5_measure.sh <part>
 #   part = bench | hist | prof | profhist | gz | gzkernels | sharded | cold | dedup | tests
 TAG=r05; mkdir -p gpurun_out/$TAG
+OUT=${BENCH_OUT:-bench_out}/$TAG; mkdir -p "$OUT"      # the --full bench line
 case "$1" in
 bench)
-  python3 bench.py --gpus 1 --steps 20 --warmup 5 2>gpurun_out/$TAG/bench.err | tail -1 | tee gpurun_out/$TAG/bench_n1.json | cut -c1-400 ;;
+  python3 bench.py --gpus 1 --steps 20 --warmup 5 --full 2>"$OUT/bench.err" | tail -1 | tee "$OUT/bench_n1.json" | cut -c1-400 ;;
 hist)
   for w in "" "--workload nanopore"; do for f in 1 3 2; do
     n=hist_f${f}$(echo $w | sed 's/--workload /_/')

@@ -2,8 +2,9 @@
 # Full measurement pass on the GPU box: all -m gpu tests, bench (with cpu baseline), variants, ingest paths, rocprofv3.
 TAG=${1:-r01}
 mkdir -p gpurun_out/$TAG
+OUT=${BENCH_OUT:-bench_out}/$TAG; mkdir -p "$OUT"      # the --full bench line
 python -m pytest tests -q -m gpu 2>&1 | tail -5 | tee gpurun_out/$TAG/pytest_gpu.txt
-python bench.py --steps 30 --warmup 3 2>gpurun_out/$TAG/bench.err | tail -1 | tee gpurun_out/$TAG/bench_n1.json | cut -c1-400
+python bench.py --steps 30 --warmup 3 --full 2>"$OUT/bench.err" | tail -1 | tee "$OUT/bench_n1.json" | cut -c1-400
 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --flags 2 2>/dev/null | tail -1 > gpurun_out/$TAG/bench_struct.json
 python bench.py --steps 5 --warmup 1 --no-cpu-baseline --flags 1 2>/dev/null | tail -1 > gpurun_out/$TAG/bench_hist.json
 SCFQ_HIST_MODE=exact python bench.py --steps 5 --warmup 1 --no-cpu-baseline --flags 1 2>/dev/null | tail -1 > gpurun_out/$TAG/bench_hist_exact.json

@@ -214,9 +214,9 @@ def test_bench_configs2_shape_at_full_shard_size(gpu):
 
 
 def test_bench_ingest_object(gpu):
-    """the non-headline `ingest` object of the default N=1 line: a gzip member and a BGZF file written in setup, a cold process and
+    """the non-headline `ingest` object of the N=1 `--full` line: a gzip member and a BGZF file written in setup, a cold process and
     the warm call, counters == generator tallies (here at a fifth of the default size)"""
-    j = _bench(["--gpus", "1", "--bytes-per-gpu", "3e8", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--ingest-bytes", "4e8"])
+    j = _bench(["--gpus", "1", "--bytes-per-gpu", "3e8", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--ingest-bytes", "4e8"])
     ing = j["ingest"]
     for k in ("gzip_member", "bgzf"):
         assert ing[k]["counters_match_generator"] is True and ing[k]["compressed_bytes"] < ing[k]["inflated_bytes"] // 2
@@ -231,6 +231,22 @@ def test_bench_ingest_object(gpu):
     ho = ing["gzip_member_host_inflate_overlap"]          # the same member inflated on the host, overlapped with copy + scan
     assert ho["counters_match_generator"] is True and ho["scan_kernel_ms"] < 0.5 * ho["host_fill_ms"]
     assert ing["device_bytes_high_water"] > 0
+
+
+def test_bench_plain_line_and_dump_outputs(gpu, tmp_path):
+    """a plain N=1 line carries no side legs; --dump-outputs writes the last timed step's counters as float64 .npy files, the same
+    from run to run"""
+    runs = []
+    for d in ("a", "b"):
+        j = _bench(["--gpus", "1", "--bytes-per-gpu", "3e8", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / d)])
+        assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["counters"]["matches_generator_tally"] is True
+        assert not {"cpu_baseline", "cpu_all_cores", "ingest", "dedup"} & set(j) and "stream_ceiling" not in j["roofline"]
+        runs.append({f: np.load(tmp_path / d / f) for f in os.listdir(tmp_path / d)})
+        assert all(a.dtype == np.float64 for a in runs[-1].values())
+        assert sum(a.nbytes for a in runs[-1].values()) <= 64 << 20
+        for k in ("reads", "gc_bases", "n_bases", "bases"):
+            assert runs[-1][k + ".npy"].tolist() == [j["counters"][k]]
+    assert runs[0].keys() == runs[1].keys() and all(np.array_equal(runs[0][k], runs[1][k]) for k in runs[0])
 
 
 def _gz_members(data, cuts, level=6):
