@@ -1980,8 +1980,11 @@ int scfq_count_file_sharded(const char* path, const scfq_opts* opts, scfq_comm* 
         return scfq_partial_finalize(&all, want_hist ? hist_all.data() : nullptr, out);
       }
       // a cut that was no member start after all (or a damaged file): every rank knows, rank 0 reads the whole file the ordinary way —
-      // its readers are gzread byte for byte, error text included — and the others contribute the identity to the exchange below
+      // its readers are gzread byte for byte, error text included — and the others contribute the identity to the exchange below.  What
+      // the block stage said of itself ("did not join up") is no part of that text: a damaged file must end with gzread's message alone
+      // (tests/test_gpu_inflate_crafted.py::test_sharded_stretch_reference_before_the_member_start)
       local = SCFQ_OK;
+      g_err[0] = '\0';
       scfq_partial_identity(&mine, want_hist ? hist.data() : nullptr);
       if (rank == 0) {
         scfq_opts o1 = o;

@@ -88,8 +88,9 @@ def _raw_crc(data, tabs):                # zero initial value, no final inversio
 
 
 def test_lane_slices_stitched_in_a_tree_give_zlib_crc32():
-    """bgzf_inflate: 64 equally long slices of "pad zeros + member", raw CRC per lane, six tree steps with one shift per step,
-    then crc32(M) = R(M) ^ 0xFFFFFFFF x^(8|M|) ^ 0xFFFFFFFF"""
+    """r4's bgzf_inflate tail (since r5 the member CRC is a kernel of its own, bgzf_crc32_members: 256 threads x 256 bytes, modelled in
+    test_deflate_writer_host.py): 64 equally long slices of "pad zeros + member", raw CRC per lane, six tree steps with one shift per
+    step, then crc32(M) = R(M) ^ 0xFFFFFFFF x^(8|M|) ^ 0xFFFFFFFF"""
     import random
     import zlib
     tabs, rng = _tables(), random.Random(3)
