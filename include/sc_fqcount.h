@@ -261,6 +261,60 @@ int scfq_dedup_buffer(const void* ptr, uint64_t n, int is_device, void* out, uin
 int scfq_dedup_file(const char* path, const scfq_opts* opts, int out_fd, scfq_dedup_stats* stats);
 const char* scfq_dedup_error_detail(void);
 
+/* ---- `sc fq-readstats` (addition; not in the reference): per-read length, G+C, N and quality ------------------
+ * Lines are those of K5 above; record i is lines 4i .. 4i+3, reads = ceil(lines / 4) as scfq_counts.reads, a line a
+ * truncated last record does not have is empty. All values are integers and exact. Device pipeline over the
+ * HBM-resident input: line index (K5), R1 — a reduction segmented by record whose work is partitioned by BYTES (a
+ * block per 32 KiB tile, so a 150-byte record and a 100 kB record cost the same per byte; a record inside one tile is
+ * stored, a record that crosses a tile border is added to by every tile it touches) — and R2, the summary. */
+typedef struct scfq_read_rec {
+  uint64_t seq_len;       /* text length of line 4i+1 (EOL stripped as K5 does) */
+  uint64_t gc_bases;      /* bytes 'G' or 'C' in it (case-sensitive, as scfq_counts.gc_bases) */
+  uint64_t n_bases;       /* bytes 'N' in it */
+  uint64_t qual_len;      /* text length of line 4i+3 */
+  uint64_t qual_sum;      /* sum of its byte values (raw bytes, no Phred offset subtracted) */
+} scfq_read_rec;
+
+#define SCFQ_LEN_HIST_BINS   65
+#define SCFQ_GC_HIST_BINS    102
+#define SCFQ_MEANQ_HIST_BINS 256
+typedef struct scfq_read_summary {
+  uint64_t struct_size;   /* caller sets to sizeof(scfq_read_summary) before the call */
+  uint64_t abi_version;   /* library writes SCFQ_ABI_VERSION */
+  uint64_t reads;         /* ceil(lines / 4) */
+  uint64_t lines;
+  uint64_t input_bytes;   /* bytes scanned (inflated bytes for .gz) */
+  uint64_t bases;         /* sum of seq_len */
+  uint64_t gc_bases;
+  uint64_t n_bases;
+  uint64_t qual_bytes;    /* sum of qual_len */
+  uint64_t qual_sum;
+  uint64_t min_len;       /* over seq_len; 0 when reads == 0 */
+  uint64_t max_len;
+  /* seq_len in descending order, accumulated: Nx = the length of the read at which acc * 100 >= bases * x first holds,
+   * Lx = how many reads were taken, that one included; all four 0 when bases == 0 */
+  uint64_t n50, l50, n90, l90;
+  uint64_t len_hist[SCFQ_LEN_HIST_BINS];     /* bin k: reads whose seq_len has bit length k (0 | 1 | 2-3 | 4-7 | ...) */
+  uint64_t gc_hist[SCFQ_GC_HIST_BINS];       /* bin floor(100 * gc_bases / (seq_len - n_bases)); bin 101: denominator 0 */
+  uint64_t meanq_hist[SCFQ_MEANQ_HIST_BINS]; /* bin floor(qual_sum / qual_len) of the reads with qual_len > 0 */
+  uint64_t no_qual;       /* reads with qual_len == 0 (in no bin of meanq_hist) */
+} scfq_read_summary;
+
+/* Input in host (is_device = 0) or device memory. records_device: device memory for `cap` records that receives the
+ * per-read table, or NULL for the summary only. A table with cap < reads returns SCFQ_EARG with out->reads (and lines,
+ * input_bytes) set: size with NULL, call again. Device pointers follow the scfq_set_wait_stream contract of
+ * scfq_index_lines. One device, the whole input resident, fewer than 2^31 records (SCFQ_EARG beyond, the text in
+ * scfq_read_stats_error_detail()). */
+int scfq_read_stats_buffer(const void* ptr, uint64_t n, int is_device, scfq_read_rec* records_device, uint64_t cap,
+                           scfq_read_summary* out);
+/* Stages the whole (inflated) input with scfq_stage_file, ".gz" and BGZF by suffix as everywhere else. */
+int scfq_read_stats_file(const char* path, const scfq_opts* opts, scfq_read_summary* out);
+/* "<reads>\t<bases>\t<min_len>\t<max_len>\t<mean_len>\t<n50>\t<l50>\t<n90>\t<l90>\t<mean_qual>" without trailing newline;
+ * mean_len = bases / reads and mean_qual = qual_sum / qual_bytes as IEEE doubles printed by the rule of scfq_format_tsv
+ * ("nan" for 0/0). Returns the number of bytes needed (excluding NUL); writes at most cap bytes incl. NUL. */
+int scfq_format_read_stats_tsv(const scfq_read_summary* s, char* buf, uint64_t cap);
+const char* scfq_read_stats_error_detail(void);   /* static, thread-local */
+
 /* Whole (inflated) input of `path` into a device buffer the caller frees with scfq_device_free(). */
 int scfq_stage_file(const char* path, const scfq_opts* opts, void** device_ptr_out, uint64_t* n_out);
 int scfq_device_free(void* device_ptr);

@@ -54,6 +54,11 @@ void scfq_debug_stage_mark(const char* what);
 /* The scan kernel instance and range geometry of the calling thread's last scan launch, e.g.
  * "fq_scan_tiles<false, 0, 2, true, false> tiles_per_range=100" (same contract as scfq_debug_stages: returns the length, writes when it fits). */
 int64_t scfq_debug_last_scan_kernel(char* buf, uint64_t cap);
+/* Stage times of the calling thread's last scfq_read_stats_buffer / scfq_read_stats_file, in milliseconds:
+ * ms[0] line index (host clock around the synchronous index call), ms[1] R1 with its border pass, ms[2] R2 first pass
+ * (sums and histograms), ms[3] R2 N50 / N90 (sort, scan, search; 0 when every read has the same length) — [1..3] are HIP-event
+ * times, taken only while SCFQ_READSTATS_TIMING=1 is in the environment (zeros otherwise). Writes min(cap, 4) values, returns 4. */
+int scfq_debug_read_stats_stages(double* ms, uint32_t cap);
 
 #ifdef __cplusplus
 }

@@ -130,7 +130,8 @@ static void help_top(FILE* f) {
   std::fprintf(f,
                "sc (%s) — MI355X-native host for the fq-count path of seq-collection\n\n"
                "Usage:\n  sc COMMAND\n\nCommands:\n\nFASTQ\n  fq-count         Counts lines in a FASTQ\n"
-               "  fq-dedup         Removes exact duplicates from FASTQ Files\n  fq-meta          Output metadata for FASTQ\n\n"
+               "  fq-dedup         Removes exact duplicates from FASTQ Files\n  fq-meta          Output metadata for FASTQ\n"
+               "  fq-readstats     Per-read length, N50, GC and quality of a FASTQ\n\n"
                "Options:\n  -h, --help                 Show this help\n  -v, --version              Show version\n"
                "      --debug                Debug mode\n",
                kVersion);
@@ -315,6 +316,78 @@ static int cmd_fq_meta(const std::vector<std::string>& params) {
   return 0;
 }
 
+// command "fq-readstats" (addition, not in the reference): -t/--header, -b/--basename, -a/--absolute as fq-count, [fastq ...]
+static const char* kReadStatsHeader = "reads\tbases\tmin_len\tmax_len\tmean_len\tn50\tl50\tn90\tl90\tmean_qual";
+static int cmd_fq_readstats(const std::vector<std::string>& params) {
+  auto help = [](FILE* f) {
+    std::fputs("Per-read length, N50, GC and quality of a FASTQ\n\nUsage:\n  fq-readstats [options] [fastq ...]\n\nArguments:\n"
+               "  [fastq ...]      Input FASTQ\n\nOptions:\n  -t, --header               Output the header\n"
+               "  -b, --basename             Add basename column\n  -a, --absolute             Add column for absolute path\n"
+               "      --hist=len|gc|qual     Print bin<TAB>count of the non-empty bins of a histogram instead of the row:\n"
+               "                             len: bit length of the read length; gc: percent G+C of the non-N bases (101: none);\n"
+               "                             qual: mean quality byte\n"
+               "  -h, --help                 Show this help\n", f);
+  };
+  if (params.size() == 1) { help(stdout); return 0; }
+  bool header = false, basename = false, absolute = false, only_positional = false;
+  std::string hist;
+  std::vector<std::string> files;
+  for (size_t i = 1; i < params.size(); ++i) {
+    const std::string& a = params[i];
+    if (only_positional || a.empty() || a[0] != '-' || a == "-") { files.push_back(a); continue; }
+    if (a == "--") { only_positional = true; continue; }
+    if (a == "-h" || a == "--help") { help(stdout); return 0; }
+    if (a == "--header") header = true;
+    else if (a == "--basename") basename = true;
+    else if (a == "--absolute") absolute = true;
+    else if (a == "--hist=len" || a == "--hist=gc" || a == "--hist=qual") hist = a.substr(7);
+    else if (a.size() >= 2 && a[1] != '-') {
+      for (size_t k = 1; k < a.size(); ++k) {
+        if (a[k] == 't') header = true;
+        else if (a[k] == 'b') basename = true;
+        else if (a[k] == 'a') absolute = true;
+        else if (a[k] == 'h') { help(stdout); return 0; }
+        else { help(stdout); quit_error(std::string("Error: Unknown option: -") + a[k], 1); }
+      }
+    } else {
+      help(stdout);
+      quit_error("Error: Unknown option: " + a, 1);
+    }
+  }
+  if (header) std::printf("%s\n", output_header(hist.empty() ? kReadStatsHeader : "bin\tcount", basename, absolute).c_str());
+  else if (files.empty()) quit_error("No FASTQ specified", 3);
+  for (const auto& fastq : files) {
+    if (fastq.size() < 3) quit_error("index out of bounds", 1);
+    scfq_read_summary s;
+    std::memset(&s, 0, sizeof s);
+    s.struct_size = sizeof s;
+    const int rc = scfq_read_stats_file(fastq.c_str(), nullptr, &s);
+    if (rc == SCFQ_EOPEN) quit_error("Unable to open file: " + fastq, fastq.compare(fastq.size() - 3, 3, ".gz") == 0 ? 1 : 2);   // as fq-count
+    if (rc != SCFQ_OK) {
+      std::string msg = scfq_strerror(rc);
+      const char* d = *scfq_read_stats_error_detail() ? scfq_read_stats_error_detail() : scfq_last_error_detail();
+      if (d && *d) { msg += ": "; msg += d; }
+      quit_error(msg, 1);
+    }
+    if (hist.empty()) {
+      char row[512];
+      scfq_format_read_stats_tsv(&s, row, sizeof row);
+      std::printf("%s\n", output_w_fnames(row, fastq, basename, absolute).c_str());
+    } else {
+      const uint64_t* h = hist == "len" ? s.len_hist : (hist == "gc" ? s.gc_hist : s.meanq_hist);
+      const int bins = hist == "len" ? SCFQ_LEN_HIST_BINS : (hist == "gc" ? SCFQ_GC_HIST_BINS : SCFQ_MEANQ_HIST_BINS);
+      for (int k = 0; k < bins; ++k) {
+        if (!h[k]) continue;
+        char line[64];
+        std::snprintf(line, sizeof line, "%d\t%llu", k, (unsigned long long)h[k]);
+        std::printf("%s\n", output_w_fnames(line, fastq, basename, absolute).c_str());
+      }
+    }
+  }
+  std::fflush(stdout);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   scfq_debug_stage_mark("sc: main entered");
   signal(SIGPIPE, SIG_IGN);   // sc.nim:45-46
@@ -326,6 +399,7 @@ int main(int argc, char** argv) {
   if (params[0] == "-v" || params[0] == "--version") { std::printf("%s\n", kVersion); return 0; }
   if (params[0] == "fq-dedup") return cmd_fq_dedup(params);
   if (params[0] == "fq-meta") return cmd_fq_meta(params);
+  if (params[0] == "fq-readstats") return cmd_fq_readstats(params);
   if (params[0] != "fq-count") {
     help_top(stdout);
     quit_error("Unknown command: " + params[0] + " (this build provides the FASTQ commands only)", 1);

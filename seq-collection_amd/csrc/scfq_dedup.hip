@@ -28,6 +28,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "scfq_index_aux.hpp"      // scfq_index_lines_ex2: the index, and the header hashes on its way
+#include "scfq_scratch.hpp"        // what scfq_readstats.hip shares: the pool, the idle streams
 constexpr uint64_t kHashSeed = 0x5CF0DED0B1A5ull;
 
 #include <unistd.h>
@@ -743,6 +744,32 @@ int write_all(int fd, const uint8_t* p, uint64_t n) {
 }
 
 }  // namespace
+
+// the pool, the idle streams and the caller-stream rule for the other record pipeline (scfq_readstats.hip): scfq_scratch.hpp
+namespace scfq_scratch {
+int pool_alloc(void** p, size_t bytes, hipStream_t stream) {
+  DevBuf b;
+  const int rc = b.alloc(bytes, stream);
+  *p = b.release();
+  return rc;
+}
+int lease_stream(hipStream_t* s, int* dev) {
+  StreamLease l;
+  const int rc = l.acquire();
+  if (rc) return rc;
+  *s = l.s;
+  *dev = l.dev;
+  l.s = nullptr;
+  return SCFQ_OK;
+}
+void return_stream(hipStream_t s, int dev, bool clean) {
+  StreamLease l;
+  l.s = s;
+  l.dev = dev;
+  l.clean = clean;
+}
+int order_after_caller(hipStream_t stream) { return wait_for_caller(stream); }
+}  // namespace scfq_scratch
 
 // called by scfq_shutdown(): the pools go back to the driver
 extern "C" void scfq_dedup_release_pools(void) {

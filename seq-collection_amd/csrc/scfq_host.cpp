@@ -109,6 +109,25 @@ int scfq_format_tsv(const scfq_counts* c, char* buf, uint64_t cap) {
   return m;
 }
 
+// the fq-readstats row: mean_len and mean_qual by the same `$float` rule
+int scfq_format_read_stats_tsv(const scfq_read_summary* s, char* buf, uint64_t cap) {
+  if (!s) return SCFQ_EARG;
+  char ml[96], mq[96];
+  nim_float_to_str((double)s->bases / (double)s->reads, ml, sizeof ml);
+  nim_float_to_str((double)s->qual_sum / (double)s->qual_bytes, mq, sizeof mq);
+  char tmp[512];
+  const int m = std::snprintf(tmp, sizeof tmp, "%llu\t%llu\t%llu\t%llu\t%s\t%llu\t%llu\t%llu\t%llu\t%s", (unsigned long long)s->reads,
+                              (unsigned long long)s->bases, (unsigned long long)s->min_len, (unsigned long long)s->max_len, ml,
+                              (unsigned long long)s->n50, (unsigned long long)s->l50, (unsigned long long)s->n90,
+                              (unsigned long long)s->l90, mq);
+  if (buf && cap) {
+    const uint64_t ncopy = ((uint64_t)m < cap - 1) ? (uint64_t)m : cap - 1;
+    std::memcpy(buf, tmp, ncopy);
+    buf[ncopy] = 0;
+  }
+  return m;
+}
+
 const char* scfq_strerror(int rc) {
   switch (rc) {
     case SCFQ_OK: return "ok";

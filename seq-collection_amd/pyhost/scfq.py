@@ -45,6 +45,8 @@ EXPORTS = [
     "scfq_comm_rank", "scfq_comm_is_broken", "scfq_prepare", "scfq_comm_transport", "scfq_comm_exchange", "scfq_comm_exchange_start", "scfq_comm_exchange_finish",
     "scfq_comm_allgather_u64", "scfq_comm_destroy", "scfq_comm_error_detail", "scfq_debug_stages", "scfq_debug_stage_mark",
     "scfq_debug_gz_member_boundary", "scfq_debug_gz_shard_fix", "scfq_debug_last_scan_kernel",
+    "scfq_read_stats_buffer", "scfq_read_stats_file", "scfq_format_read_stats_tsv", "scfq_read_stats_error_detail",
+    "scfq_debug_read_stats_stages",
 ]
 
 
@@ -86,6 +88,22 @@ class Timing(ctypes.Structure):
 class DedupStats(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in ("struct_size", "total_reads", "duplicates", "false_positive", "records_out",
                                                "bytes_out", "hash_collisions")]
+
+
+class ReadRec(ctypes.Structure):
+    """scfq_read_rec: one row of the per-read table (five uint64)"""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("seq_len", "gc_bases", "n_bases", "qual_len", "qual_sum")]
+
+
+LEN_HIST_BINS, GC_HIST_BINS, MEANQ_HIST_BINS = 65, 102, 256
+
+
+class ReadSummary(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in (
+        "struct_size", "abi_version", "reads", "lines", "input_bytes", "bases", "gc_bases", "n_bases", "qual_bytes", "qual_sum",
+        "min_len", "max_len", "n50", "l50", "n90", "l90")] + [
+        ("len_hist", ctypes.c_uint64 * LEN_HIST_BINS), ("gc_hist", ctypes.c_uint64 * GC_HIST_BINS),
+        ("meanq_hist", ctypes.c_uint64 * MEANQ_HIST_BINS), ("no_qual", ctypes.c_uint64)]
 
 
 class SynthInfo(ctypes.Structure):
@@ -177,6 +195,12 @@ def lib():
         L.scfq_comm_destroy.argtypes = [vp]
         L.scfq_comm_error_detail.restype = ctypes.c_char_p
         L.scfq_count_file_sharded.argtypes = [ctypes.c_char_p, ctypes.POINTER(Opts), vp, ctypes.POINTER(Counts)]
+        L.scfq_read_stats_buffer.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
+                                             ctypes.POINTER(ReadSummary)]
+        L.scfq_read_stats_file.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.POINTER(ReadSummary)]
+        L.scfq_format_read_stats_tsv.argtypes = [ctypes.POINTER(ReadSummary), ctypes.c_char_p, ctypes.c_uint64]
+        L.scfq_read_stats_error_detail.restype = ctypes.c_char_p
+        L.scfq_debug_read_stats_stages.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]
         _lib = L
     return _lib
 
@@ -394,6 +418,54 @@ def dedup_file(path, out_fd=-1):
     st = _new_dedup_stats()
     _check(lib().scfq_dedup_file(os.fsencode(path), None, out_fd, ctypes.byref(st)), "scfq_dedup_file")
     return st
+
+
+def _new_read_summary():
+    s = ReadSummary()
+    s.struct_size = ctypes.sizeof(ReadSummary)
+    return s
+
+
+def _check_read_stats(rc, what):
+    if rc != 0:
+        raise ScfqError(rc, what, lib().scfq_read_stats_error_detail().decode() or lib().scfq_last_error_detail().decode())
+
+
+def read_stats_device(dev_ptr, n, records_ptr=None, cap=0):
+    """fq-readstats of a device-resident FASTQ; records_ptr: device memory for `cap` ReadRec rows (None: summary only; size
+    it with the `reads` of a summary-only call).  Returns the ReadSummary."""
+    s = _new_read_summary()
+    _check_read_stats(lib().scfq_read_stats_buffer(ctypes.c_void_p(dev_ptr), n, 1, ctypes.c_void_p(records_ptr) if records_ptr else None,
+                                                   cap, ctypes.byref(s)), "scfq_read_stats_buffer")
+    return s
+
+
+def read_stats_host(data):
+    """fq-readstats of a host buffer (bytes / numpy uint8); returns the ReadSummary"""
+    addr, n, keep = _host_ptr(data)
+    s = _new_read_summary()
+    _check_read_stats(lib().scfq_read_stats_buffer(addr, n, 0, None, 0, ctypes.byref(s)), "scfq_read_stats_buffer")
+    return s
+
+
+def read_stats_file(path):
+    s = _new_read_summary()
+    _check_read_stats(lib().scfq_read_stats_file(os.fsencode(path), None, ctypes.byref(s)), "scfq_read_stats_file")
+    return s
+
+
+def format_read_stats_tsv(s):
+    buf = ctypes.create_string_buffer(512)
+    lib().scfq_format_read_stats_tsv(ctypes.byref(s), buf, 512)
+    return buf.value.decode()
+
+
+def read_stats_stages():
+    """(index, R1, R2 sums + histograms, R2 N50 / N90) milliseconds of this thread's last read_stats call; the last three are HIP-event
+    times and zeros unless SCFQ_READSTATS_TIMING=1 is in the environment"""
+    ms = (ctypes.c_double * 4)()
+    lib().scfq_debug_read_stats_stages(ms, 4)
+    return list(ms)
 
 
 SCFQ_META_WHOLE_FILE = 0x1
