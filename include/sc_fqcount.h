@@ -315,6 +315,49 @@ int scfq_read_stats_file(const char* path, const scfq_opts* opts, scfq_read_summ
 int scfq_format_read_stats_tsv(const scfq_read_summary* s, char* buf, uint64_t cap);
 const char* scfq_read_stats_error_detail(void);   /* static, thread-local */
 
+/* ---- `sc fq-cycles` (addition; not in the reference): base composition and quality position by position ---------
+ * Lines and records are those of fq-readstats above. Every text byte b at 0-based position p of a sequence line (4i+1)
+ * adds 1 to bases[p] and to exactly one of a, c, g, t, n at p when b is that upper-case letter (case-sensitive, as
+ * scfq_counts.gc_bases); other = bases - a - c - g - t - n is not stored. Every text byte q at position p of a quality
+ * line (4i+3) adds 1 to quals[p] and its raw value to qual_sum[p] (no Phred offset, as scfq_read_rec.qual_sum). All
+ * values are integers and exact. Device pipeline over the HBM-resident input: line index (K5), a pass over its offsets
+ * (line lengths), C1 — the counting kernel, partitioned by line group and position window, 32-bit counters in LDS per
+ * block, flushed to 64-bit global counters — and a pass that turns the counters into rows, tail and total. */
+typedef struct scfq_cycle_row {       /* 64 bytes */
+  uint64_t bases, a, c, g, t, n;      /* sequence lines that have a byte at this position, and which byte */
+  uint64_t quals, qual_sum;           /* quality lines that have a byte here, and the sum of those bytes */
+} scfq_cycle_row;
+
+typedef struct scfq_cycle_summary {
+  uint64_t struct_size;   /* caller sets to sizeof(scfq_cycle_summary) before the call */
+  uint64_t abi_version;   /* library writes SCFQ_ABI_VERSION */
+  uint64_t reads;         /* ceil(lines / 4) */
+  uint64_t lines;
+  uint64_t input_bytes;   /* bytes scanned (inflated bytes for .gz) */
+  uint64_t max_seq_len, max_qual_len; /* longest text of a line 4i+1 / 4i+3; 0 without one */
+  uint64_t cycles;                    /* rows written: min(cap, max(max_seq_len, max_qual_len)) */
+  scfq_cycle_row tail;                /* everything at positions >= cap, added up */
+  scfq_cycle_row total;               /* every position added up: does not depend on cap */
+} scfq_cycle_summary;
+
+#define SCFQ_CYCLES_MAX_CAP (1ull << 24)
+/* Input in host (is_device = 0) or device memory. rows_host: HOST memory for `cap` rows (may be NULL when cap is 0);
+ * rows [0, cycles) are written, every field, rows [cycles, cap) are not touched. cap = 0 is the sizing call: everything
+ * lands in tail, read max_seq_len / max_qual_len and call again. total, reads, lines, input_bytes and the two maxima do
+ * not depend on cap, and rows[p] is the same for every cap > p. cap above SCFQ_CYCLES_MAX_CAP returns SCFQ_EARG (text in
+ * scfq_cycles_error_detail()). Device pointers follow the scfq_set_wait_stream contract of scfq_index_lines. One
+ * device, the whole input resident, fewer than 2^31 records, as scfq_read_stats_buffer. */
+int scfq_cycles_buffer(const void* ptr, uint64_t n, int is_device, scfq_cycle_row* rows_host, uint64_t cap,
+                       scfq_cycle_summary* out);
+/* Stages the whole (inflated) input with scfq_stage_file, ".gz" and BGZF by suffix as everywhere else. */
+int scfq_cycles_file(const char* path, const scfq_opts* opts, scfq_cycle_row* rows_host, uint64_t cap,
+                     scfq_cycle_summary* out);
+/* "<bases>\t<A>\t<C>\t<G>\t<T>\t<N>\t<other>\t<quals>\t<mean_qual>" without trailing newline; mean_qual = qual_sum /
+ * quals as an IEEE double printed by the rule of scfq_format_tsv ("nan" for 0/0). Returns the number of bytes needed
+ * (excluding NUL); writes at most cap bytes incl. NUL. */
+int scfq_format_cycle_row_tsv(const scfq_cycle_row* r, char* buf, uint64_t cap);
+const char* scfq_cycles_error_detail(void);   /* static, thread-local */
+
 /* Whole (inflated) input of `path` into a device buffer the caller frees with scfq_device_free(). */
 int scfq_stage_file(const char* path, const scfq_opts* opts, void** device_ptr_out, uint64_t* n_out);
 int scfq_device_free(void* device_ptr);

@@ -59,6 +59,11 @@ int64_t scfq_debug_last_scan_kernel(char* buf, uint64_t cap);
  * (sums and histograms), ms[3] R2 N50 / N90 (sort, scan, search; 0 when every read has the same length) — [1..3] are HIP-event
  * times, taken only while SCFQ_READSTATS_TIMING=1 is in the environment (zeros otherwise). Writes min(cap, 4) values, returns 4. */
 int scfq_debug_read_stats_stages(double* ms, uint32_t cap);
+/* Stage times of the calling thread's last scfq_cycles_buffer / scfq_cycles_file, in milliseconds: ms[0] line index (host
+ * clock around the synchronous index call), ms[1] line pass (lengths, maxima, block plan), ms[2] C1, the counting kernel,
+ * ms[3] finish (rows, tail, total; without the copy to the host) — [1..3] are HIP-event times, taken only while
+ * SCFQ_CYCLES_TIMING=1 is in the environment (zeros otherwise). Writes min(cap, 4) values, returns 4. */
+int scfq_debug_cycles_stages(double* ms, uint32_t cap);
 
 #ifdef __cplusplus
 }

@@ -131,7 +131,8 @@ static void help_top(FILE* f) {
                "sc (%s) — MI355X-native host for the fq-count path of seq-collection\n\n"
                "Usage:\n  sc COMMAND\n\nCommands:\n\nFASTQ\n  fq-count         Counts lines in a FASTQ\n"
                "  fq-dedup         Removes exact duplicates from FASTQ Files\n  fq-meta          Output metadata for FASTQ\n"
-               "  fq-readstats     Per-read length, N50, GC and quality of a FASTQ\n\n"
+               "  fq-readstats     Per-read length, N50, GC and quality of a FASTQ\n"
+               "  fq-cycles        Per-position base composition and quality of a FASTQ\n\n"
                "Options:\n  -h, --help                 Show this help\n  -v, --version              Show version\n"
                "      --debug                Debug mode\n",
                kVersion);
@@ -388,6 +389,85 @@ static int cmd_fq_readstats(const std::vector<std::string>& params) {
   return 0;
 }
 
+// command "fq-cycles" (addition, not in the reference): -t/--header, -b/--basename, -a/--absolute as fq-count, --max-cycles=N, [fastq ...]
+static const char* kCyclesHeader = "cycle\tbases\tA\tC\tG\tT\tN\tother\tquals\tmean_qual";
+static int cmd_fq_cycles(const std::vector<std::string>& params) {
+  auto help = [](FILE* f) {
+    std::fputs("Per-position base composition and quality of a FASTQ\n\nUsage:\n  fq-cycles [options] [fastq ...]\n\nArguments:\n"
+               "  [fastq ...]      Input FASTQ\n\nOptions:\n  -t, --header               Output the header\n"
+               "  -b, --basename             Add basename column\n  -a, --absolute             Add column for absolute path\n"
+               "      --max-cycles=N         One row per position up to N (default: 1000, at most 16777216); what lies beyond\n"
+               "                             comes added up as one last row \">N\"\n"
+               "  -h, --help                 Show this help\n", f);
+  };
+  if (params.size() == 1) { help(stdout); return 0; }
+  bool header = false, basename = false, absolute = false, only_positional = false;
+  uint64_t max_cycles = 1000;
+  std::vector<std::string> files;
+  for (size_t i = 1; i < params.size(); ++i) {
+    const std::string& a = params[i];
+    if (only_positional || a.empty() || a[0] != '-' || a == "-") { files.push_back(a); continue; }
+    if (a == "--") { only_positional = true; continue; }
+    if (a == "-h" || a == "--help") { help(stdout); return 0; }
+    if (a == "--header") header = true;
+    else if (a == "--basename") basename = true;
+    else if (a == "--absolute") absolute = true;
+    else if (a.compare(0, 13, "--max-cycles=") == 0) {
+      const std::string v = a.substr(13);
+      const bool digits = !v.empty() && v.size() <= 8 && v.find_first_not_of("0123456789") == std::string::npos;
+      if (!digits || std::stoull(v) > SCFQ_CYCLES_MAX_CAP) { help(stdout); quit_error("Error: Bad value for --max-cycles: " + v, 1); }
+      max_cycles = std::stoull(v);
+    } else if (a.size() >= 2 && a[1] != '-') {
+      for (size_t k = 1; k < a.size(); ++k) {
+        if (a[k] == 't') header = true;
+        else if (a[k] == 'b') basename = true;
+        else if (a[k] == 'a') absolute = true;
+        else if (a[k] == 'h') { help(stdout); return 0; }
+        else { help(stdout); quit_error(std::string("Error: Unknown option: -") + a[k], 1); }
+      }
+    } else {
+      help(stdout);
+      quit_error("Error: Unknown option: " + a, 1);
+    }
+  }
+  if (header) std::printf("%s\n", output_header(kCyclesHeader, basename, absolute).c_str());
+  else if (files.empty()) quit_error("No FASTQ specified", 3);
+  std::vector<scfq_cycle_row> rows;
+  for (const auto& fastq : files) {
+    if (fastq.size() < 3) quit_error("index out of bounds", 1);
+    scfq_cycle_summary s;
+    int rc = SCFQ_OK;
+    // the sizing call first: the table is as long as the file's longest line, not as --max-cycles
+    for (int pass = 0; pass < 2 && rc == SCFQ_OK; ++pass) {
+      std::memset(&s, 0, sizeof s);
+      s.struct_size = sizeof s;
+      rc = scfq_cycles_file(fastq.c_str(), nullptr, rows.empty() ? nullptr : rows.data(), rows.size(), &s);
+      if (pass == 1 || rc != SCFQ_OK) break;
+      rows.assign((size_t)std::min<uint64_t>(max_cycles, std::max(s.max_seq_len, s.max_qual_len)), scfq_cycle_row());
+      if (rows.empty()) break;
+    }
+    if (rc == SCFQ_EOPEN) quit_error("Unable to open file: " + fastq, fastq.compare(fastq.size() - 3, 3, ".gz") == 0 ? 1 : 2);   // as fq-count
+    if (rc != SCFQ_OK) {
+      std::string msg = scfq_strerror(rc);
+      const char* d = *scfq_cycles_error_detail() ? scfq_cycles_error_detail() : scfq_last_error_detail();
+      if (d && *d) { msg += ": "; msg += d; }
+      quit_error(msg, 1);
+    }
+    char row[512];
+    for (uint64_t p = 0; p < s.cycles; ++p) {
+      scfq_format_cycle_row_tsv(&rows[p], row, sizeof row);
+      std::printf("%s\n", output_w_fnames(std::to_string(p + 1) + "\t" + row, fastq, basename, absolute).c_str());
+    }
+    if (s.tail.bases || s.tail.quals) {
+      scfq_format_cycle_row_tsv(&s.tail, row, sizeof row);
+      std::printf("%s\n", output_w_fnames(">" + std::to_string(max_cycles) + "\t" + row, fastq, basename, absolute).c_str());
+    }
+    rows.clear();
+  }
+  std::fflush(stdout);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   scfq_debug_stage_mark("sc: main entered");
   signal(SIGPIPE, SIG_IGN);   // sc.nim:45-46
@@ -400,6 +480,7 @@ int main(int argc, char** argv) {
   if (params[0] == "fq-dedup") return cmd_fq_dedup(params);
   if (params[0] == "fq-meta") return cmd_fq_meta(params);
   if (params[0] == "fq-readstats") return cmd_fq_readstats(params);
+  if (params[0] == "fq-cycles") return cmd_fq_cycles(params);
   if (params[0] != "fq-count") {
     help_top(stdout);
     quit_error("Unknown command: " + params[0] + " (this build provides the FASTQ commands only)", 1);

@@ -128,6 +128,24 @@ int scfq_format_read_stats_tsv(const scfq_read_summary* s, char* buf, uint64_t c
   return m;
 }
 
+// the fq-cycles row: other = bases - a - c - g - t - n, mean_qual by the same `$float` rule
+int scfq_format_cycle_row_tsv(const scfq_cycle_row* r, char* buf, uint64_t cap) {
+  if (!r) return SCFQ_EARG;
+  char mq[96];
+  nim_float_to_str((double)r->qual_sum / (double)r->quals, mq, sizeof mq);
+  char tmp[512];
+  const int m = std::snprintf(tmp, sizeof tmp, "%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%s", (unsigned long long)r->bases,
+                              (unsigned long long)r->a, (unsigned long long)r->c, (unsigned long long)r->g, (unsigned long long)r->t,
+                              (unsigned long long)r->n, (unsigned long long)(r->bases - r->a - r->c - r->g - r->t - r->n),
+                              (unsigned long long)r->quals, mq);
+  if (buf && cap) {
+    const uint64_t ncopy = ((uint64_t)m < cap - 1) ? (uint64_t)m : cap - 1;
+    std::memcpy(buf, tmp, ncopy);
+    buf[ncopy] = 0;
+  }
+  return m;
+}
+
 const char* scfq_strerror(int rc) {
   switch (rc) {
     case SCFQ_OK: return "ok";

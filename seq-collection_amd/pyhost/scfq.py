@@ -47,6 +47,7 @@ EXPORTS = [
     "scfq_debug_gz_member_boundary", "scfq_debug_gz_shard_fix", "scfq_debug_last_scan_kernel",
     "scfq_read_stats_buffer", "scfq_read_stats_file", "scfq_format_read_stats_tsv", "scfq_read_stats_error_detail",
     "scfq_debug_read_stats_stages",
+    "scfq_cycles_buffer", "scfq_cycles_file", "scfq_format_cycle_row_tsv", "scfq_cycles_error_detail", "scfq_debug_cycles_stages",
 ]
 
 
@@ -104,6 +105,20 @@ class ReadSummary(ctypes.Structure):
         "min_len", "max_len", "n50", "l50", "n90", "l90")] + [
         ("len_hist", ctypes.c_uint64 * LEN_HIST_BINS), ("gc_hist", ctypes.c_uint64 * GC_HIST_BINS),
         ("meanq_hist", ctypes.c_uint64 * MEANQ_HIST_BINS), ("no_qual", ctypes.c_uint64)]
+
+
+CYCLE_FIELDS = ("bases", "a", "c", "g", "t", "n", "quals", "qual_sum")
+CYCLES_MAX_CAP = 1 << 24
+
+
+class CycleRow(ctypes.Structure):
+    """scfq_cycle_row: one position of the fq-cycles table (eight uint64)"""
+    _fields_ = [(n, ctypes.c_uint64) for n in CYCLE_FIELDS]
+
+
+class CycleSummary(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in ("struct_size", "abi_version", "reads", "lines", "input_bytes", "max_seq_len", "max_qual_len",
+                                               "cycles")] + [("tail", CycleRow), ("total", CycleRow)]
 
 
 class SynthInfo(ctypes.Structure):
@@ -201,6 +216,12 @@ def lib():
         L.scfq_format_read_stats_tsv.argtypes = [ctypes.POINTER(ReadSummary), ctypes.c_char_p, ctypes.c_uint64]
         L.scfq_read_stats_error_detail.restype = ctypes.c_char_p
         L.scfq_debug_read_stats_stages.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]
+        L.scfq_cycles_buffer.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
+                                         ctypes.POINTER(CycleSummary)]
+        L.scfq_cycles_file.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(CycleSummary)]
+        L.scfq_format_cycle_row_tsv.argtypes = [ctypes.POINTER(CycleRow), ctypes.c_char_p, ctypes.c_uint64]
+        L.scfq_cycles_error_detail.restype = ctypes.c_char_p
+        L.scfq_debug_cycles_stages.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]
         _lib = L
     return _lib
 
@@ -468,6 +489,60 @@ def read_stats_stages():
     return list(ms)
 
 
+def _new_cycle_summary():
+    s = CycleSummary()
+    s.struct_size = ctypes.sizeof(CycleSummary)
+    return s
+
+
+def _cycles_call(fn, what, cap, *head):
+    """rows: a caller's int64 array of shape (cap, 8) is filled in place ([cycles, cap) untouched) when `cap` is one"""
+    import numpy as np
+    if isinstance(cap, np.ndarray):
+        buf = cap
+        assert buf.dtype == np.int64 and buf.ndim == 2 and buf.shape[1] == 8 and buf.flags.c_contiguous
+    else:
+        buf = np.zeros((cap, 8), dtype=np.int64)
+    s = _new_cycle_summary()
+    rc = fn(*head, ctypes.c_void_p(buf.ctypes.data) if buf.shape[0] else None, buf.shape[0], ctypes.byref(s))
+    if rc != 0:
+        raise ScfqError(rc, what, lib().scfq_cycles_error_detail().decode() or lib().scfq_last_error_detail().decode())
+    return s, buf[:s.cycles]
+
+
+def cycles_device(dev_ptr, n, cap=0):
+    """fq-cycles of a device-resident FASTQ, at most `cap` positions (0: the sizing call; read max_seq_len / max_qual_len).
+    Returns (CycleSummary, rows as an int64 array of shape (cycles, 8), columns CYCLE_FIELDS)."""
+    return _cycles_call(lib().scfq_cycles_buffer, "scfq_cycles_buffer", cap, ctypes.c_void_p(dev_ptr), n, 1)
+
+
+def cycles_host(data, cap=0):
+    """fq-cycles of a host buffer (bytes / numpy uint8)"""
+    addr, n, keep = _host_ptr(data)
+    return _cycles_call(lib().scfq_cycles_buffer, "scfq_cycles_buffer", cap, addr, n, 0)
+
+
+def cycles_file(path, cap=0):
+    return _cycles_call(lib().scfq_cycles_file, "scfq_cycles_file", cap, os.fsencode(path), None)
+
+
+def format_cycle_row_tsv(row):
+    """row: a CycleRow or eight integers in the order of CYCLE_FIELDS"""
+    if not isinstance(row, CycleRow):
+        row = CycleRow(*[int(v) for v in row])
+    buf = ctypes.create_string_buffer(512)
+    lib().scfq_format_cycle_row_tsv(ctypes.byref(row), buf, 512)
+    return buf.value.decode()
+
+
+def cycles_stages():
+    """(index, line pass, counting kernel, finish) milliseconds of this thread's last cycles call; the last three are HIP-event
+    times and zeros unless SCFQ_CYCLES_TIMING=1 is in the environment"""
+    ms = (ctypes.c_double * 4)()
+    lib().scfq_debug_cycles_stages(ms, 4)
+    return list(ms)
+
+
 SCFQ_META_WHOLE_FILE = 0x1
 
 
@@ -571,6 +646,9 @@ def last_timing():
     t.struct_size = ctypes.sizeof(Timing)
     _check(lib().scfq_last_timing(ctypes.byref(t)), "scfq_last_timing")
     return t
+
+
+SCFQ_SYNTH_ILLUMINA, SCFQ_SYNTH_NANOPORE = 0, 1
 
 
 def synth_plan(kind, seed, min_bytes, first_record=0):
