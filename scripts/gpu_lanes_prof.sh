@@ -5,7 +5,7 @@ set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 S=$R/seq-collection_amd/csrc
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -DSCFQ_LPROF -o /tmp/libscfq_lprof.so \
-  $S/scfq_api.hip $S/scfq_host.cpp $S/scfq_synth.hip $S/scfq_dedup.hip $S/scfq_meta.cpp $S/scfq_comm.cpp -lz -lpthread -ldl 2>/dev/null
+  $S/scfq_api.hip $S/scfq_host.cpp $S/scfq_synth.hip $S/scfq_scratch.hip $S/scfq_dedup.hip $S/scfq_meta.cpp $S/scfq_comm.cpp -lz -lpthread -ldl 2>/dev/null
 for LOOP in ${SCFQ_PROF_LOOPS:-lanes dense}; do
 echo "== SCFQ_INFLATE_LOOP=$LOOP"
 SCFQ_INFLATE_LOOP=$LOOP SCFQ_LIB_OVERRIDE=/tmp/libscfq_lprof.so python - <<PY

@@ -221,7 +221,7 @@ struct SessionLock {
 
 int env_int(const char* name, int dflt);
 }  // namespace
-extern "C" void scfq_dedup_release_pools(void);      // scfq_dedup.hip
+namespace scfq_scratch { void release_all(); }      // scfq_scratch.hip
 namespace {
 
 std::mutex g_mu;
@@ -2144,7 +2144,7 @@ int scfq_shutdown(void) {
     if (c->compute) (void)hipStreamDestroy(c->compute);
     if (c->copy && !c->copy_is_alias) (void)hipStreamDestroy(c->copy);
   }
-  scfq_dedup_release_pools();     // fq-dedup keeps its scratch in library-owned stream-ordered pools: give them back
+  scfq_scratch::release_all();    // the record pipelines keep their scratch in library-owned stream-ordered pools: give them back
   release_comms();                // communicators of the single-process multi-device path
   g_ctx.clear();
   trace("shutdown done");

@@ -2,7 +2,7 @@
 // Not in the reference; definitions in include/sc_fqcount.h.
 //
 // The whole (inflated) input sits in HBM, as for fq-readstats:
-//   K5  line index            (scfq_index_lines_ex2: line_off[0 .. lines], and whether the input holds "\r\n" at all)
+//   K5  line index            (scfq_scratch::build_line_index: line_off[0 .. lines], and whether the input holds "\r\n" at all)
 //   C0  cy_lines              a pass over line_off.  Only the odd lines count (4i+1 sequence, 4i+3 quality): odd line k is line 2k+1,
 //                             a sequence line when k is even.  A block per GROUP of 2048 odd lines: the longest text of either kind
 //                             (global maxima) and the group's longest line, which says how many position WINDOWS of 1024 the group needs.
@@ -25,7 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
-#include "scfq_index_aux.hpp"
+#include "scfq_record_device.hpp"
 #include "scfq_scratch.hpp"
 
 #include <algorithm>
@@ -35,34 +35,10 @@
 
 namespace {
 
-thread_local char g_cerr[512] = "";
+thread_local char g_cerr[scfq_scratch::kErrBytes] = "";
 thread_local double g_stage_ms[4] = {0, 0, 0, 0};
 
-#define CCHK(call)                                                                                          \
-  do {                                                                                                      \
-    hipError_t e_ = (call);                                                                                 \
-    if (e_ != hipSuccess) {                                                                                 \
-      std::snprintf(g_cerr, sizeof g_cerr, "%s -> %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-      if (std::getenv("SCFQ_VERBOSE")) std::fprintf(stderr, "scfq: %s\n", g_cerr);                          \
-      return SCFQ_EHIP;                                                                                     \
-    }                                                                                                       \
-  } while (0)
-
-struct Lease {
-  hipStream_t s = nullptr;
-  int dev = -1;
-  bool clean = false;
-  ~Lease() { if (s) scfq_scratch::return_stream(s, dev, clean); }
-};
-
-struct Buf {   // pool memory, returned stream-ordered on scope exit
-  void* p = nullptr;
-  hipStream_t s = nullptr;
-  ~Buf() { if (p) (void)hipFreeAsync(p, s); }
-  template <typename T> T* as() { return static_cast<T*>(p); }
-  int alloc(size_t bytes, hipStream_t stream) { s = stream; return scfq_scratch::pool_alloc(&p, bytes, stream); }
-  void drop() { if (p) (void)hipFreeAsync(p, s); p = nullptr; }
-};
+using scfq_scratch::DevBuf;
 
 constexpr uint32_t kCyThreads = 256;
 constexpr uint32_t kCyGroup = 2048;                  // odd lines of a group (even: the parity of k inside a group is that of k)
@@ -73,17 +49,6 @@ constexpr uint32_t kCyArr = 8;                       // counter arrays: A C T G 
 constexpr uint32_t kQualShift = 20;
 static_assert(kCyGroup % 2 == 0 && (uint64_t)kCyGroup * 255 < (1u << kQualShift) && kCyGroup / 2 < (1u << (32 - kQualShift)), "the packed quality counter");
 
-__device__ __forceinline__ uint64_t wave_max(uint64_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { const uint64_t x = __shfl_xor((unsigned long long)v, o, 64); v = x > v ? x : v; }
-  return v;
-}
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor((unsigned long long)v, o, 64);
-  return v;
-}
-
 // C0: a block per group.  nwin[g]: windows the group's longest line needs (its chunk grid starts up to 15 bytes before the line)
 __global__ __launch_bounds__(kCyThreads) void cy_lines(const uint8_t* base, uint64_t n, const uint64_t* line_off, uint64_t odd, bool has_cr,
                                                       uint64_t groups, uint64_t* gmax, uint64_t* nwin, unsigned long long* mx) {
@@ -93,9 +58,8 @@ __global__ __launch_bounds__(kCyThreads) void cy_lines(const uint8_t* base, uint
   for (uint32_t i = threadIdx.x; i < kCyGroup; i += kCyThreads) {
     const uint64_t k = g * kCyGroup + i;
     if (k >= odd) break;
-    const uint64_t s = line_off[2 * k + 1], nl = line_off[2 * k + 2] - 1;      // (2k + 2 <= lines)
-    uint64_t e = nl;
-    if (has_cr && nl < n && e > s && base[e - 1] == '\r') --e;
+    uint64_t s, e;
+    line_span(base, n, line_off, 2 * k + 1, s, e, has_cr);      // (2k + 2 <= lines)
     const uint64_t len = e - s;
     if (i & 1) mq = len > mq ? len : mq; else ms = len > ms ? len : ms;
   }
@@ -282,31 +246,6 @@ __global__ __launch_bounds__(256) void cy_finish(unsigned long long* table, uint
   }
 }
 
-struct StageClock {      // HIP-event brackets, only with SCFQ_CYCLES_TIMING=1
-  bool on;
-  hipStream_t s;
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  bool set[5] = {false, false, false, false, false};
-  StageClock(hipStream_t stream) : s(stream) {
-    static const bool env = [] { const char* e = std::getenv("SCFQ_CYCLES_TIMING"); return e && std::atoi(e) != 0; }();
-    on = env;
-    if (on) for (auto& e : ev) if (hipEventCreate(&e) != hipSuccess) { on = false; break; }
-  }
-  ~StageClock() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
-  void mark(int k) { if (on && hipEventRecord(ev[k], s) == hipSuccess) set[k] = true; }
-  double between(int a, int b) {
-    float ms = 0;
-    return (on && set[a] && set[b] && hipEventElapsedTime(&ms, ev[a], ev[b]) == hipSuccess) ? (double)ms : 0.0;
-  }
-};
-
-void clear_summary(scfq_cycle_summary* out) {
-  const uint64_t keep = out->struct_size;
-  std::memset(out, 0, sizeof *out);
-  out->struct_size = keep;
-  out->abi_version = SCFQ_ABI_VERSION;
-}
-
 bool args_ok(const scfq_cycle_row* rows_host, uint64_t cap, const scfq_cycle_summary* out) {
   if (!out || out->struct_size != sizeof(scfq_cycle_summary) || (!rows_host && cap)) return false;
   if (cap > SCFQ_CYCLES_MAX_CAP) {
@@ -321,25 +260,14 @@ int cycles_device(const uint8_t* d_in, uint64_t n, scfq_cycle_row* rows_host, ui
   for (double& m : g_stage_ms) m = 0;
   out->input_bytes = n;
   uint64_t lines = 0;
-  uint32_t index_flags = 1;
-  Buf line_off, gmax, nwin, gbase, mx, table, tot, tmp;
+  DevBuf line_off, gmax, nwin, gbase, mx, table, tot, tmp;
   int rc = SCFQ_OK;
+  bool has_cr = true;
   {
-    // the index's size is guessed first, as fq-readstats does: only a wrong guess costs a second pass with the exact size
-    uint64_t lcap = n / 24 + 1024;
     const auto t_a = std::chrono::steady_clock::now();
-    for (int round = 0; round < 2; ++round) {
-      if ((rc = line_off.alloc(lcap * 8, stream))) return rc;
-      CCHK(hipStreamSynchronize(stream));       // scfq_index_lines works on the library's own stream
-      rc = scfq_index_lines_ex2(d_in, n, line_off.as<uint64_t>(), lcap, &lines, &index_flags, nullptr);
-      if (rc) return rc;
-      if (lines + 1 <= lcap) break;
-      line_off.drop();
-      lcap = lines + 1;
-    }
+    if ((rc = scfq_scratch::build_line_index(d_in, n, stream, g_cerr, line_off, &lines, &has_cr))) return rc;
     g_stage_ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_a).count();
   }
-  const bool has_cr = (index_flags & 1u) != 0;
   const uint64_t reads = (lines + 3) / 4;
   out->lines = lines;
   out->reads = reads;
@@ -347,49 +275,50 @@ int cycles_device(const uint8_t* d_in, uint64_t n, scfq_cycle_row* rows_host, ui
   const uint64_t odd = lines / 2;               // lines 1, 3, 5, ...: the sequence and quality lines
   if (odd == 0) return SCFQ_OK;
   const uint64_t groups = (odd + kCyGroup - 1) / kCyGroup;
-  if ((rc = gmax.alloc(groups * 8, stream)) || (rc = nwin.alloc((groups + 1) * 8, stream)) || (rc = gbase.alloc((groups + 1) * 8, stream)) ||
-      (rc = mx.alloc(16, stream)) || (rc = tot.alloc(64, stream)))
+  if ((rc = gmax.alloc(groups * 8, stream, g_cerr)) || (rc = nwin.alloc((groups + 1) * 8, stream, g_cerr)) || (rc = gbase.alloc((groups + 1) * 8, stream, g_cerr)) ||
+      (rc = mx.alloc(16, stream, g_cerr)) || (rc = tot.alloc(64, stream, g_cerr)))
     return rc;
-  StageClock clk(stream);
+  static const bool timing = scfq_scratch::env_switch("SCFQ_CYCLES_TIMING");
+  scfq_scratch::StageClock clk(stream, timing);
   clk.mark(0);
-  CCHK(hipMemsetAsync(mx.p, 0, 16, stream));
-  CCHK(hipMemsetAsync(tot.p, 0, 64, stream));
+  SCFQ_SCRATCH_CHK(g_cerr, hipMemsetAsync(mx.p, 0, 16, stream));
+  SCFQ_SCRATCH_CHK(g_cerr, hipMemsetAsync(tot.p, 0, 64, stream));
   hipLaunchKernelGGL(cy_lines, dim3((unsigned)groups), dim3(kCyThreads), 0, stream, d_in, n, line_off.as<uint64_t>(), odd, has_cr, groups,
                      gmax.as<uint64_t>(), nwin.as<uint64_t>(), mx.as<unsigned long long>());
-  CCHK(hipGetLastError());
+  SCFQ_SCRATCH_CHK(g_cerr, hipGetLastError());
   size_t scan_bytes = 0;
-  CCHK(rocprim::exclusive_scan(nullptr, scan_bytes, nwin.as<uint64_t>(), gbase.as<uint64_t>(), (uint64_t)0, (size_t)(groups + 1), rocprim::plus<uint64_t>(), stream));
-  if ((rc = tmp.alloc(std::max<size_t>(scan_bytes, 16), stream))) return rc;
-  CCHK(rocprim::exclusive_scan(tmp.p, scan_bytes, nwin.as<uint64_t>(), gbase.as<uint64_t>(), (uint64_t)0, (size_t)(groups + 1), rocprim::plus<uint64_t>(), stream));
+  SCFQ_SCRATCH_CHK(g_cerr, rocprim::exclusive_scan(nullptr, scan_bytes, nwin.as<uint64_t>(), gbase.as<uint64_t>(), (uint64_t)0, (size_t)(groups + 1), rocprim::plus<uint64_t>(), stream));
+  if ((rc = tmp.alloc(std::max<size_t>(scan_bytes, 16), stream, g_cerr))) return rc;
+  SCFQ_SCRATCH_CHK(g_cerr, rocprim::exclusive_scan(tmp.p, scan_bytes, nwin.as<uint64_t>(), gbase.as<uint64_t>(), (uint64_t)0, (size_t)(groups + 1), rocprim::plus<uint64_t>(), stream));
   clk.mark(1);
   uint64_t h_mx[2] = {0, 0}, blocks = 0;
-  CCHK(hipMemcpyAsync(h_mx, mx.p, 16, hipMemcpyDeviceToHost, stream));
-  CCHK(hipMemcpyAsync(&blocks, gbase.as<uint64_t>() + groups, 8, hipMemcpyDeviceToHost, stream));
-  CCHK(hipStreamSynchronize(stream));
+  SCFQ_SCRATCH_CHK(g_cerr, hipMemcpyAsync(h_mx, mx.p, 16, hipMemcpyDeviceToHost, stream));
+  SCFQ_SCRATCH_CHK(g_cerr, hipMemcpyAsync(&blocks, gbase.as<uint64_t>() + groups, 8, hipMemcpyDeviceToHost, stream));
+  SCFQ_SCRATCH_CHK(g_cerr, hipStreamSynchronize(stream));
   out->max_seq_len = h_mx[0];
   out->max_qual_len = h_mx[1];
   const uint64_t cycles = std::min(cap, std::max(h_mx[0], h_mx[1]));
   out->cycles = cycles;
   if (blocks >= (1ull << 31)) { std::snprintf(g_cerr, sizeof g_cerr, "input too large for one launch"); return SCFQ_EARG; }
   const uint64_t rows = cycles + 1;             // the last one is the tail
-  if ((rc = table.alloc(rows * sizeof(scfq_cycle_row), stream))) return rc;
-  CCHK(hipMemsetAsync(table.p, 0, rows * sizeof(scfq_cycle_row), stream));
+  if ((rc = table.alloc(rows * sizeof(scfq_cycle_row), stream, g_cerr))) return rc;
+  SCFQ_SCRATCH_CHK(g_cerr, hipMemsetAsync(table.p, 0, rows * sizeof(scfq_cycle_row), stream));
   clk.mark(2);
   if (blocks) {
     const uint32_t shift = (uint32_t)((uintptr_t)d_in & 15u);
     hipLaunchKernelGGL(cy_count, dim3((unsigned)blocks), dim3(kCyThreads), 0, stream, d_in, n, line_off.as<uint64_t>(), odd, shift, has_cr,
                        gbase.as<uint64_t>(), groups, gmax.as<uint64_t>(), cycles, table.as<unsigned long long>());
-    CCHK(hipGetLastError());
+    SCFQ_SCRATCH_CHK(g_cerr, hipGetLastError());
   }
   clk.mark(3);
   hipLaunchKernelGGL(cy_finish, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, table.as<unsigned long long>(), rows,
                      tot.as<unsigned long long>());
-  CCHK(hipGetLastError());
+  SCFQ_SCRATCH_CHK(g_cerr, hipGetLastError());
   clk.mark(4);
-  if (cycles) CCHK(hipMemcpyAsync(rows_host, table.p, cycles * sizeof(scfq_cycle_row), hipMemcpyDeviceToHost, stream));
-  CCHK(hipMemcpyAsync(&out->tail, table.as<scfq_cycle_row>() + cycles, sizeof(scfq_cycle_row), hipMemcpyDeviceToHost, stream));
-  CCHK(hipMemcpyAsync(&out->total, tot.p, sizeof(scfq_cycle_row), hipMemcpyDeviceToHost, stream));
-  CCHK(hipStreamSynchronize(stream));
+  if (cycles) SCFQ_SCRATCH_CHK(g_cerr, hipMemcpyAsync(rows_host, table.p, cycles * sizeof(scfq_cycle_row), hipMemcpyDeviceToHost, stream));
+  SCFQ_SCRATCH_CHK(g_cerr, hipMemcpyAsync(&out->tail, table.as<scfq_cycle_row>() + cycles, sizeof(scfq_cycle_row), hipMemcpyDeviceToHost, stream));
+  SCFQ_SCRATCH_CHK(g_cerr, hipMemcpyAsync(&out->total, tot.p, sizeof(scfq_cycle_row), hipMemcpyDeviceToHost, stream));
+  SCFQ_SCRATCH_CHK(g_cerr, hipStreamSynchronize(stream));
   g_stage_ms[1] = clk.between(0, 1);
   g_stage_ms[2] = clk.between(2, 3);
   g_stage_ms[3] = clk.between(3, 4);
@@ -402,45 +331,30 @@ extern "C" {
 
 const char* scfq_cycles_error_detail(void) { return g_cerr; }
 
-int scfq_debug_cycles_stages(double* ms, uint32_t cap) {
-  for (uint32_t k = 0; ms && k < cap && k < 4; ++k) ms[k] = g_stage_ms[k];
-  return 4;
-}
+int scfq_debug_cycles_stages(double* ms, uint32_t cap) { return scfq_scratch::copy_stage_ms(g_stage_ms, ms, cap); }
 
 int scfq_cycles_buffer(const void* ptr, uint64_t n, int is_device, scfq_cycle_row* rows_host, uint64_t cap, scfq_cycle_summary* out) {
   g_cerr[0] = '\0';
   if (!args_ok(rows_host, cap, out) || (!ptr && n)) return SCFQ_EARG;
-  clear_summary(out);
-  Lease lease;
-  { const int rc = scfq_scratch::lease_stream(&lease.s, &lease.dev); if (rc) return rc; }
-  const hipStream_t stream = lease.s;
-  Buf staged;
-  const uint8_t* d_in = static_cast<const uint8_t*>(ptr);
-  if (is_device) { const int rc = scfq_scratch::order_after_caller(stream); if (rc) return rc; }
-  if (!is_device && n) {
-    const int rc = staged.alloc(n, stream);
-    if (rc) return rc;
-    CCHK(hipMemcpyAsync(staged.p, ptr, n, hipMemcpyHostToDevice, stream));
-    CCHK(hipStreamSynchronize(stream));
-    d_in = staged.as<uint8_t>();
-  }
-  const int rc = cycles_device(d_in, n, rows_host, cap, out, stream);
-  if (rc == SCFQ_OK) lease.clean = true;      // (its last act was to wait for the stream)
+  scfq_scratch::clear_keep_size(out);
+  scfq_scratch::ResidentInput in;
+  int rc = in.from_buffer(ptr, n, is_device != 0, is_device != 0, g_cerr);
+  if (rc) return rc;
+  rc = cycles_device(in.d_in, n, rows_host, cap, out, in.stream);
+  if (rc == SCFQ_OK) in.mark_clean();      // (its last act was to wait for the stream)
   return rc;
 }
 
 int scfq_cycles_file(const char* path, const scfq_opts* opts, scfq_cycle_row* rows_host, uint64_t cap, scfq_cycle_summary* out) {
   g_cerr[0] = '\0';
   if (!path || !args_ok(rows_host, cap, out)) return SCFQ_EARG;
-  clear_summary(out);
-  void* d_in = nullptr;
-  uint64_t n = 0;
-  int rc = scfq_stage_file(path, opts, &d_in, &n);      // whole (inflated) input into HBM
+  scfq_scratch::clear_keep_size(out);
+  scfq_scratch::ResidentInput in;
+  int rc = in.from_file(path, opts, g_cerr);
   if (rc) return rc;
-  struct InGuard { void* p; ~InGuard() { if (p) (void)hipFree(p); } } ig{d_in};
-  Lease lease;
-  if ((rc = scfq_scratch::lease_stream(&lease.s, &lease.dev))) return rc;
-  return cycles_device(static_cast<const uint8_t*>(d_in), n, rows_host, cap, out, lease.s);
+  rc = cycles_device(in.d_in, in.n, rows_host, cap, out, in.stream);
+  if (rc == SCFQ_OK) in.mark_clean();      // (its last act was to wait for the stream)
+  return rc;
 }
 
 }  // extern "C"

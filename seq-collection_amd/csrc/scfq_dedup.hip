@@ -27,8 +27,9 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
-#include "scfq_index_aux.hpp"      // scfq_index_lines_ex2: the index, and the header hashes on its way
-#include "scfq_scratch.hpp"        // what scfq_readstats.hip shares: the pool, the idle streams
+#include "scfq_index_aux.hpp"      // what the index pass fills on its way: the header hashes
+#include "scfq_record_device.hpp"  // line_span
+#include "scfq_scratch.hpp"        // the pool, the leased stream, the resident input, the line index
 constexpr uint64_t kHashSeed = 0x5CF0DED0B1A5ull;
 
 #include <unistd.h>
@@ -39,121 +40,12 @@ constexpr uint64_t kHashSeed = 0x5CF0DED0B1A5ull;
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
-#include <mutex>
-#include <vector>
 
 namespace {
 
-thread_local char g_derr[512] = "";
+thread_local char g_derr[scfq_scratch::kErrBytes] = "";
 
-#define DCHK(call)                                                                                          \
-  do {                                                                                                      \
-    hipError_t e_ = (call);                                                                                 \
-    if (e_ != hipSuccess) {                                                                                 \
-      std::snprintf(g_derr, sizeof g_derr, "%s -> %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-      if (std::getenv("SCFQ_VERBOSE")) std::fprintf(stderr, "scfq: %s\n", g_derr);                          \
-      return SCFQ_EHIP;                                                                                     \
-    }                                                                                                       \
-  } while (0)
-
-// Scratch comes from a stream-ordered memory pool OWNED BY THIS LIBRARY (one per device, release threshold = keep
-// everything, destroyed by scfq_shutdown): after the first call a de-duplication allocates nothing from the driver
-// (hipMalloc / hipFree of multi-GB buffers cost more than all kernels of the pipeline together), and the device's default
-// pool — which belongs to the host application — is left as it was.
-std::mutex g_pool_mu;
-std::map<int, hipMemPool_t> g_pools;
-
-int scratch_pool(hipMemPool_t* out) {
-  int dev = 0;
-  DCHK(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(g_pool_mu);
-  auto it = g_pools.find(dev);
-  if (it == g_pools.end()) {
-    hipMemPoolProps props{};
-    props.allocType = hipMemAllocationTypePinned;
-    props.handleTypes = hipMemHandleTypeNone;
-    props.location.type = hipMemLocationTypeDevice;
-    props.location.id = dev;
-    hipMemPool_t pool = nullptr;
-    DCHK(hipMemPoolCreate(&pool, &props));
-    uint64_t keep = UINT64_MAX;
-    DCHK(hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &keep));
-    it = g_pools.emplace(dev, pool).first;
-  }
-  *out = it->second;
-  return SCFQ_OK;
-}
-
-// The call's private stream comes from a per-device list of idle ones and goes back to it (r4: creating and destroying a stream per
-// call cost more host time than all the launches of the pipeline; scfq_shutdown destroys them).  A stream is only returned by a call
-// that has waited for everything it put on it.
-std::map<int, std::vector<hipStream_t>> g_idle_streams;      // under g_pool_mu
-
-struct StreamLease {
-  hipStream_t s = nullptr;
-  int dev = -1;
-  bool clean = false;            // set by the owner once nothing is pending on s: a stream with work in flight is destroyed instead
-  int acquire() {
-    DCHK(hipGetDevice(&dev));
-    {
-      std::lock_guard<std::mutex> lk(g_pool_mu);
-      auto& v = g_idle_streams[dev];
-      if (!v.empty()) { s = v.back(); v.pop_back(); return SCFQ_OK; }
-    }
-    DCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    return SCFQ_OK;
-  }
-  ~StreamLease() {
-    if (!s) return;
-    if (clean || hipStreamSynchronize(s) == hipSuccess) {
-      std::lock_guard<std::mutex> lk(g_pool_mu);
-      auto& v = g_idle_streams[dev];
-      if (v.size() < 8) { v.push_back(s); return; }
-    }
-    (void)hipStreamDestroy(s);
-  }
-};
-
-struct DevBuf {   // returns its memory to the pool on scope exit (stream-ordered)
-  void* p = nullptr;
-  hipStream_t s = nullptr;
-  ~DevBuf() { if (p) (void)hipFreeAsync(p, s); }
-  template <typename T> T* as() { return static_cast<T*>(p); }
-  int alloc(size_t bytes, hipStream_t stream) {
-    s = stream;
-    hipMemPool_t pool;
-    int rc = scratch_pool(&pool);
-    if (rc) return rc;
-    DCHK(hipMallocFromPoolAsync(&p, std::max<size_t>(bytes, 16), pool, stream));
-    return SCFQ_OK;
-  }
-  void* release() { void* q = p; p = nullptr; return q; }
-};
-
-// the caller's stream (scfq_set_wait_stream) is ordered before this call's private stream
-int wait_for_caller(hipStream_t stream) {
-  int on = 0;
-  void* ws = scfq_get_wait_stream(&on);
-  if (!on) return SCFQ_OK;
-  hipEvent_t ev;
-  DCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  hipError_t e = hipEventRecord(ev, static_cast<hipStream_t>(ws));
-  if (e == hipSuccess) e = hipStreamWaitEvent(stream, ev, 0);
-  (void)hipEventDestroy(ev);
-  DCHK(e);
-  return SCFQ_OK;
-}
-
-// text of line j: [line_off[j], end) where end excludes the '\n' and a '\r' directly before a REAL '\n'
-// (Nim 1.0.6 readLine; a final line without '\n' keeps a trailing '\r')
-__device__ __forceinline__ void line_span(const uint8_t* base, uint64_t n, const uint64_t* line_off, uint64_t j,
-                                          uint64_t& s, uint64_t& e, bool has_cr = true) {
-  s = line_off[j];
-  const uint64_t nlpos = line_off[j + 1] - 1;     // position of the (real or implied) '\n'
-  e = nlpos;
-  if (has_cr && nlpos < n && e > s && base[e - 1] == '\r') --e;      // (has_cr: kernel-uniform, from the index pass)
-}
+using scfq_scratch::DevBuf;
 
 // Word k (bytes [8k, 8k + 8)) of the header that starts at s and is len bytes long, bytes past the header zeroed; addresses are
 // clamped to stay inside the input.
@@ -580,10 +472,8 @@ int dedup_device(const uint8_t* d_in, uint64_t n, uint8_t* user_out, uint64_t us
     t_last = now;
   };
   auto mark2 = [&](const char* what) { if (trace == 2) mark(what); };      // (enqueue-only marks)
-  // the line index in ONE pass (count and offsets together): its size is guessed first — a FASTQ line is rarely shorter
-  // than 24 bytes on average — and only a wrong guess costs a second pass with the exact size
   int rc = SCFQ_OK;
-  uint32_t index_flags = 1;
+  bool has_cr = true;
   DevBuf line_off, keys, keys2, idx, idx2, dup, out_len, group_len, group_off, counters, tmp, hdr, cand, unk;
   // 32 bits of hash in 32-bit keys: the radix sort makes 4 passes over 8-byte (key, record) pairs — 0.93 ms for 28 M records against
   // 1.29 ms for 40 bits in 64-bit keys — and the exact compare behind the sort makes collisions (n^2 / 2^33 pairs: 88 K among 28 M
@@ -597,52 +487,43 @@ int dedup_device(const uint8_t* d_in, uint64_t n, uint8_t* user_out, uint64_t us
   const bool fused = fused_env && hash_bits <= 56;
   const uint32_t key_bytes = hash_bits <= 32 ? 4u : 8u;
   scfq_index_aux aux{};
-  {
-    uint64_t cap = n / 24 + 1024;
-    for (int round = 0; round < 2; ++round) {
-      if ((rc = line_off.alloc(cap * 8, stream))) return rc;
-      if (fused) {
-        const uint64_t cap_records = cap / 4 + 2;
-        if ((rc = keys.alloc(cap_records * 8, stream)) || (rc = idx.alloc(cap_records * 4, stream)) || (rc = hdr.alloc(cap_records * 8, stream))) return rc;
-        aux.keys = keys.p; aux.idx = idx.as<uint32_t>(); aux.hdr = hdr.as<uint64_t>();
-        aux.cap_records = cap_records; aux.key_bytes = key_bytes; aux.hash_bits = hash_bits; aux.seed = kHashSeed;
-        if (!unk.p) {
-          aux.unk_tiles = n / 4096 + 2;      // (the index pass's tiles are 4 KiB, the first one may be a partial one)
-          if ((rc = unk.alloc(aux.unk_tiles * 4 * sizeof(uint32_t), stream))) return rc;
-          aux.unk = unk.as<uint32_t>();
-        }
+  // the index's buffers are sized by its guess of the line count (scfq_scratch::build_line_index), before the count is known
+  auto hashes_of_round = [&](uint64_t cap, scfq_index_aux** index_aux) -> int {
+    if (fused) {
+      const uint64_t cap_records = cap / 4 + 2;
+      keys.drop(); idx.drop(); hdr.drop();      // (a second round: all of the first one's go back before any is taken again)
+      if ((rc = keys.alloc(cap_records * 8, stream, g_derr)) || (rc = idx.alloc(cap_records * 4, stream, g_derr)) || (rc = hdr.alloc(cap_records * 8, stream, g_derr))) return rc;
+      aux.keys = keys.p; aux.idx = idx.as<uint32_t>(); aux.hdr = hdr.as<uint64_t>();
+      aux.cap_records = cap_records; aux.key_bytes = key_bytes; aux.hash_bits = hash_bits; aux.seed = kHashSeed;
+      if (!unk.p) {
+        aux.unk_tiles = n / 4096 + 2;      // (the index pass's tiles are 4 KiB, the first one may be a partial one)
+        if ((rc = unk.alloc(aux.unk_tiles * 4 * sizeof(uint32_t), stream, g_derr))) return rc;
+        aux.unk = unk.as<uint32_t>();
       }
-      mark("alloc line offsets");
-      DCHK(hipStreamSynchronize(stream));       // scfq_index_lines works on the library's own stream
-      mark("wait for the caller's stream");
-      rc = scfq_index_lines_ex2(d_in, n, line_off.as<uint64_t>(), cap, &lines, &index_flags, fused ? &aux : nullptr);
-      if (rc) return rc;
-      if (lines + 1 <= cap) break;
-      // the guess was too small (lines shorter than 24 bytes on average): once more with the exact size
-      (void)hipFreeAsync(line_off.release(), stream);
-      if (fused) { (void)hipFreeAsync(keys.release(), stream); (void)hipFreeAsync(idx.release(), stream); (void)hipFreeAsync(hdr.release(), stream); }
-      cap = lines + 1;
+      *index_aux = &aux;
     }
-  }
-  const bool has_cr = (index_flags & 1u) != 0;
+    mark("alloc line offsets, wait for the caller's stream");
+    return SCFQ_OK;
+  };
+  if ((rc = scfq_scratch::build_line_index(d_in, n, stream, g_derr, line_off, &lines, &has_cr, hashes_of_round))) return rc;
   st->total_reads = lines / 4;                       // n_reads = i div 4      src/fq_dedup.nim:49
   const uint64_t n_hdr = (lines + 3) / 4;            // header lines: 0-based index i mod 4 == 0 (:43,57)
   if (n_hdr >= (1ull << 31)) { std::snprintf(g_derr, sizeof g_derr, "more than 2^31 records in one input"); return SCFQ_EARG; }
   if (n_hdr == 0) return SCFQ_OK;
   mark("line index (K5, one pass)");
   const uint64_t n_groups = (n_hdr + kGatherGroup - 1) / kGatherGroup;
-  if (!fused && ((rc = keys.alloc(n_hdr * 8, stream)) || (rc = idx.alloc(n_hdr * 4, stream)) || (rc = hdr.alloc(n_hdr * 8, stream)))) return rc;
-  if ((rc = keys2.alloc(n_hdr * 8, stream)) ||
-      (rc = idx2.alloc(n_hdr * 4, stream)) || (rc = dup.alloc(n_hdr, stream)) || (rc = out_len.alloc(n_hdr * 8, stream)) ||
-      (rc = group_len.alloc((n_groups + 1) * 8, stream)) || (rc = group_off.alloc((n_groups + 1) * 8, stream)) || (rc = counters.alloc(32, stream)) ||
-      (rc = cand.alloc(n_hdr * 4, stream)))
+  if (!fused && ((rc = keys.alloc(n_hdr * 8, stream, g_derr)) || (rc = idx.alloc(n_hdr * 4, stream, g_derr)) || (rc = hdr.alloc(n_hdr * 8, stream, g_derr)))) return rc;
+  if ((rc = keys2.alloc(n_hdr * 8, stream, g_derr)) ||
+      (rc = idx2.alloc(n_hdr * 4, stream, g_derr)) || (rc = dup.alloc(n_hdr, stream, g_derr)) || (rc = out_len.alloc(n_hdr * 8, stream, g_derr)) ||
+      (rc = group_len.alloc((n_groups + 1) * 8, stream, g_derr)) || (rc = group_off.alloc((n_groups + 1) * 8, stream, g_derr)) || (rc = counters.alloc(32, stream, g_derr)) ||
+      (rc = cand.alloc(n_hdr * 4, stream, g_derr)))
     return rc;
   mark("alloc scratch");
-  DCHK(hipMemsetAsync(counters.p, 0, 32, stream));
+  SCFQ_SCRATCH_CHK(g_derr, hipMemsetAsync(counters.p, 0, 32, stream));
   const unsigned blocks = (unsigned)((n_hdr + 255) / 256);
   size_t scan_bytes = 0;
-  DCHK(rocprim::exclusive_scan(nullptr, scan_bytes, group_len.as<uint64_t>(), group_off.as<uint64_t>(), (uint64_t)0, (size_t)(n_groups + 1),
-                               rocprim::plus<uint64_t>(), stream));
+  SCFQ_SCRATCH_CHK(g_derr, rocprim::exclusive_scan(nullptr, scan_bytes, group_len.as<uint64_t>(), group_off.as<uint64_t>(), (uint64_t)0, (size_t)(n_groups + 1),
+                                                   rocprim::plus<uint64_t>(), stream));
   uint32_t* n_cand = reinterpret_cast<uint32_t*>(counters.as<unsigned long long>() + 2);
   auto hash_sort_mark = [&](auto key_tag) -> int {
     using K = decltype(key_tag);
@@ -655,39 +536,39 @@ int dedup_device(const uint8_t* d_in, uint64_t n, uint8_t* user_out, uint64_t us
       // (its list is not complete — a tile with five of them, or with 64+ lines: short reads — they are looked for)
       uint32_t* n_list = reinterpret_cast<uint32_t*>(counters.as<unsigned long long>() + 3);
       hipLaunchKernelGGL(dd_find_unknown<K>, dim3((unsigned)((n_hdr + 2047) / 2048)), dim3(256), 0, stream, keys.as<K>(), n_hdr, cand.as<uint32_t>(), n_list);
-      DCHK(hipGetLastError());
+      SCFQ_SCRATCH_CHK(g_derr, hipGetLastError());
       hipLaunchKernelGGL(dd_hash_listed<K>, dim3(blocks), dim3(256), 0, stream, d_in, n, line_off.as<uint64_t>(), cand.as<uint32_t>(), n_list,
                          (uint64_t)0, n_hdr, kHashSeed, hash_bits, keys.as<K>(), idx.as<uint32_t>(), hdr.as<uint64_t>(), has_cr);
     } else {
       hipLaunchKernelGGL(dd_hash_headers<K>, dim3(blocks), dim3(256), 0, stream, d_in, n, line_off.as<uint64_t>(), n_hdr,
                          kHashSeed, hash_bits, keys.as<K>(), idx.as<uint32_t>(), hdr.as<uint64_t>(), has_cr);
     }
-    DCHK(hipGetLastError());
+    SCFQ_SCRATCH_CHK(g_derr, hipGetLastError());
     mark("hash headers");
     size_t tmp_bytes = 0;
-    DCHK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys.as<K>(), keys2.as<K>(), idx.as<uint32_t>(), idx2.as<uint32_t>(), (size_t)n_hdr, 0u, hash_bits, stream));
-    if ((rc = tmp.alloc(std::max(tmp_bytes, scan_bytes), stream))) return rc;
-    DCHK(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, keys.as<K>(), keys2.as<K>(), idx.as<uint32_t>(), idx2.as<uint32_t>(), (size_t)n_hdr, 0u, hash_bits, stream));
+    SCFQ_SCRATCH_CHK(g_derr, rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys.as<K>(), keys2.as<K>(), idx.as<uint32_t>(), idx2.as<uint32_t>(), (size_t)n_hdr, 0u, hash_bits, stream));
+    if ((rc = tmp.alloc(std::max(tmp_bytes, scan_bytes), stream, g_derr))) return rc;
+    SCFQ_SCRATCH_CHK(g_derr, rocprim::radix_sort_pairs(tmp.p, tmp_bytes, keys.as<K>(), keys2.as<K>(), idx.as<uint32_t>(), idx2.as<uint32_t>(), (size_t)n_hdr, 0u, hash_bits, stream));
     mark("radix sort");
-    DCHK(hipMemsetAsync(dup.p, 0, n_hdr, stream));
+    SCFQ_SCRATCH_CHK(g_derr, hipMemsetAsync(dup.p, 0, n_hdr, stream));
     hipLaunchKernelGGL(dd_find_equal<K>, dim3((unsigned)((n_hdr + 2047) / 2048)), dim3(256), 0, stream, keys2.as<K>(), n_hdr, cand.as<uint32_t>(), n_cand);
-    DCHK(hipGetLastError());
+    SCFQ_SCRATCH_CHK(g_derr, hipGetLastError());
     // (the launch covers the worst case; blocks past the candidate count leave at once)
     hipLaunchKernelGGL(dd_mark_duplicates<K>, dim3(blocks), dim3(256), 0, stream, d_in, n, line_off.as<uint64_t>(), hdr.as<uint64_t>(),
                        keys2.as<K>(), idx2.as<uint32_t>(), cand.as<uint32_t>(), n_cand, dup.as<uint8_t>(), has_cr);
-    DCHK(hipGetLastError());
+    SCFQ_SCRATCH_CHK(g_derr, hipGetLastError());
     hipLaunchKernelGGL(dd_count_marks, dim3(512), dim3(256), 0, stream, dup.as<uint8_t>(), n_hdr, cand.as<uint32_t>(), n_cand, counters.as<unsigned long long>());
-    DCHK(hipGetLastError());
+    SCFQ_SCRATCH_CHK(g_derr, hipGetLastError());
     return SCFQ_OK;
   };
   if ((rc = hash_bits <= 32 ? hash_sort_mark(uint32_t{}) : hash_sort_mark(uint64_t{}))) return rc;
   mark("mark duplicates");
   hipLaunchKernelGGL(dd_record_lengths, dim3(blocks), dim3(256), 0, stream, d_in, n, line_off.as<uint64_t>(), lines, n_hdr,
                      dup.as<uint8_t>(), out_len.as<uint64_t>(), group_len.as<uint64_t>(), has_cr);
-  DCHK(hipGetLastError());
-  DCHK(hipMemsetAsync(group_len.as<uint64_t>() + n_groups, 0, 8, stream));       // the scan's last output is the total
-  DCHK(rocprim::exclusive_scan(tmp.p, scan_bytes, group_len.as<uint64_t>(), group_off.as<uint64_t>(), (uint64_t)0, (size_t)(n_groups + 1),
-                               rocprim::plus<uint64_t>(), stream));
+  SCFQ_SCRATCH_CHK(g_derr, hipGetLastError());
+  SCFQ_SCRATCH_CHK(g_derr, hipMemsetAsync(group_len.as<uint64_t>() + n_groups, 0, 8, stream));       // the scan's last output is the total
+  SCFQ_SCRATCH_CHK(g_derr, rocprim::exclusive_scan(tmp.p, scan_bytes, group_len.as<uint64_t>(), group_off.as<uint64_t>(), (uint64_t)0, (size_t)(n_groups + 1),
+                                                   rocprim::plus<uint64_t>(), stream));
   mark2("lengths + scan enqueued");
   uint64_t h[3] = {0, 0, 0};
   // a caller's buffer that holds the whole input holds any result: the gather goes out behind the scan at once, and the one
@@ -696,13 +577,13 @@ int dedup_device(const uint8_t* d_in, uint64_t n, uint8_t* user_out, uint64_t us
   if (gather_first) {
     hipLaunchKernelGGL(dd_gather, dim3((unsigned)((n_groups + 3) / 4)), dim3(256), 0, stream, d_in, n, line_off.as<uint64_t>(), lines, n_hdr,
                        group_off.as<uint64_t>(), out_len.as<uint64_t>(), user_out);
-    DCHK(hipGetLastError());
+    SCFQ_SCRATCH_CHK(g_derr, hipGetLastError());
   }
   mark2("gather enqueued");
-  DCHK(hipMemcpyAsync(&h[0], group_off.as<uint64_t>() + n_groups, 8, hipMemcpyDeviceToHost, stream));
-  DCHK(hipMemcpyAsync(&h[1], counters.p, 16, hipMemcpyDeviceToHost, stream));
+  SCFQ_SCRATCH_CHK(g_derr, hipMemcpyAsync(&h[0], group_off.as<uint64_t>() + n_groups, 8, hipMemcpyDeviceToHost, stream));
+  SCFQ_SCRATCH_CHK(g_derr, hipMemcpyAsync(&h[1], counters.p, 16, hipMemcpyDeviceToHost, stream));
   mark2("readbacks enqueued");
-  DCHK(hipStreamSynchronize(stream));
+  SCFQ_SCRATCH_CHK(g_derr, hipStreamSynchronize(stream));
   mark(gather_first ? "lengths + scan + gather + readback" : "lengths + scan + readback");
   st->duplicates = h[1];
   st->hash_collisions = h[2];
@@ -714,15 +595,15 @@ int dedup_device(const uint8_t* d_in, uint64_t n, uint8_t* user_out, uint64_t us
   DevBuf own;
   uint8_t* o = user_out;
   if (!o) {
-    if ((rc = own.alloc(h[0], stream))) return rc;
+    if ((rc = own.alloc(h[0], stream, g_derr))) return rc;
     o = own.as<uint8_t>();
   } else if (user_cap < h[0]) {
     return SCFQ_EARG;
   }
   hipLaunchKernelGGL(dd_gather, dim3((unsigned)((n_groups + 3) / 4)), dim3(256), 0, stream, d_in, n, line_off.as<uint64_t>(), lines, n_hdr,
                      group_off.as<uint64_t>(), out_len.as<uint64_t>(), o);
-  DCHK(hipGetLastError());
-  DCHK(hipStreamSynchronize(stream));
+  SCFQ_SCRATCH_CHK(g_derr, hipGetLastError());
+  SCFQ_SCRATCH_CHK(g_derr, hipStreamSynchronize(stream));
   mark("gather");
   if (!user_out) *d_out = static_cast<uint8_t*>(own.release());
   return SCFQ_OK;
@@ -745,41 +626,6 @@ int write_all(int fd, const uint8_t* p, uint64_t n) {
 
 }  // namespace
 
-// the pool, the idle streams and the caller-stream rule for the other record pipeline (scfq_readstats.hip): scfq_scratch.hpp
-namespace scfq_scratch {
-int pool_alloc(void** p, size_t bytes, hipStream_t stream) {
-  DevBuf b;
-  const int rc = b.alloc(bytes, stream);
-  *p = b.release();
-  return rc;
-}
-int lease_stream(hipStream_t* s, int* dev) {
-  StreamLease l;
-  const int rc = l.acquire();
-  if (rc) return rc;
-  *s = l.s;
-  *dev = l.dev;
-  l.s = nullptr;
-  return SCFQ_OK;
-}
-void return_stream(hipStream_t s, int dev, bool clean) {
-  StreamLease l;
-  l.s = s;
-  l.dev = dev;
-  l.clean = clean;
-}
-int order_after_caller(hipStream_t stream) { return wait_for_caller(stream); }
-}  // namespace scfq_scratch
-
-// called by scfq_shutdown(): the pools go back to the driver
-extern "C" void scfq_dedup_release_pools(void) {
-  std::lock_guard<std::mutex> lk(g_pool_mu);
-  for (auto& kv : g_idle_streams) { if (hipSetDevice(kv.first) == hipSuccess) for (hipStream_t st : kv.second) (void)hipStreamDestroy(st); }
-  g_idle_streams.clear();
-  for (auto& kv : g_pools) { if (hipSetDevice(kv.first) == hipSuccess) (void)hipMemPoolDestroy(kv.second); }
-  g_pools.clear();
-}
-
 extern "C" {
 
 const char* scfq_dedup_error_detail(void) { return g_derr; }
@@ -787,62 +633,49 @@ const char* scfq_dedup_error_detail(void) { return g_derr; }
 int scfq_dedup_buffer(const void* ptr, uint64_t n, int is_device, void* out, uint64_t out_cap, int out_is_device,
                       uint64_t* out_bytes, scfq_dedup_stats* st) {
   if ((!ptr && n) || !st || st->struct_size != sizeof(scfq_dedup_stats) || !out_bytes) return SCFQ_EARG;
-  const uint64_t keep_size = st->struct_size;
-  std::memset(st, 0, sizeof(*st));
-  st->struct_size = keep_size;
+  scfq_scratch::clear_keep_size(st);
   *out_bytes = 0;
-  StreamLease lease;
-  { const int lrc = lease.acquire(); if (lrc) return lrc; }
-  const hipStream_t stream = lease.s;
-  DevBuf staged;
-  const uint8_t* d_in = static_cast<const uint8_t*>(ptr);
-  if (is_device || (out && out_is_device)) { int rc = wait_for_caller(stream); if (rc) return rc; }
-  if (!is_device && n) {
-    int rc = staged.alloc(n, stream);
-    if (rc) return rc;
-    DCHK(hipMemcpyAsync(staged.p, ptr, n, hipMemcpyHostToDevice, stream));
-    DCHK(hipStreamSynchronize(stream));
-    d_in = staged.as<uint8_t>();
-  }
-  uint8_t* d_out = nullptr;
-  uint64_t nb = 0;
   // device destination: gather straight into the caller's buffer; host destination: gather into pool memory, copy down
   const bool direct = out && out_is_device;
-  int rc = dedup_device(d_in, n, direct ? static_cast<uint8_t*>(out) : nullptr, direct ? out_cap : 0, /*sized_only=*/!out, &d_out, &nb, st, stream);
+  scfq_scratch::ResidentInput in;
+  int rc = in.from_buffer(ptr, n, is_device != 0, is_device || direct, g_derr);
+  if (rc) return rc;
+  const hipStream_t stream = in.stream;
+  uint8_t* d_out = nullptr;
+  uint64_t nb = 0;
+  rc = dedup_device(in.d_in, n, direct ? static_cast<uint8_t*>(out) : nullptr, direct ? out_cap : 0, /*sized_only=*/!out, &d_out, &nb, st, stream);
   *out_bytes = nb;
   if (rc) return rc;
-  if (!out || direct || nb == 0) { if (d_out) (void)hipFreeAsync(d_out, stream); return SCFQ_OK; }
-  struct OutGuard { void* p; hipStream_t s; ~OutGuard() { if (p) (void)hipFreeAsync(p, s); } } og{d_out, stream};
+  DevBuf result;
+  result.adopt(d_out, stream);
+  // (every successful return of dedup_device is behind a wait for the stream, or, without records, behind the index's)
+  if (!out || direct || nb == 0) { in.mark_clean(); return SCFQ_OK; }
   if (nb > out_cap) return SCFQ_EARG;      // caller sizes (out = NULL) and calls again
-  DCHK(hipMemcpyAsync(out, d_out, nb, hipMemcpyDeviceToHost, stream));
-  DCHK(hipStreamSynchronize(stream));
+  SCFQ_SCRATCH_CHK(g_derr, hipMemcpyAsync(out, d_out, nb, hipMemcpyDeviceToHost, stream));
+  SCFQ_SCRATCH_CHK(g_derr, hipStreamSynchronize(stream));
+  in.mark_clean();
   return SCFQ_OK;
 }
 
 int scfq_dedup_file(const char* path, const scfq_opts* opts, int out_fd, scfq_dedup_stats* st) {
   if (!path || !st || st->struct_size != sizeof(scfq_dedup_stats)) return SCFQ_EARG;
-  const uint64_t keep_size = st->struct_size;
-  std::memset(st, 0, sizeof(*st));
-  st->struct_size = keep_size;
-  void* d_in = nullptr;
-  uint64_t n = 0;
-  int rc = scfq_stage_file(path, opts, &d_in, &n);      // whole (inflated) input into HBM
+  scfq_scratch::clear_keep_size(st);
+  scfq_scratch::ResidentInput in;
+  int rc = in.from_file(path, opts, g_derr);
   if (rc) return rc;
-  struct InGuard { void* p; ~InGuard() { if (p) (void)hipFree(p); } } ig{d_in};
-  StreamLease lease;
-  { const int lrc = lease.acquire(); if (lrc) return lrc; }
-  const hipStream_t stream = lease.s;
+  const hipStream_t stream = in.stream;
   uint8_t* d_out = nullptr;
   uint64_t nb = 0;
-  rc = dedup_device(static_cast<const uint8_t*>(d_in), n, nullptr, 0, /*sized_only=*/out_fd < 0, &d_out, &nb, st, stream);
+  rc = dedup_device(in.d_in, in.n, nullptr, 0, /*sized_only=*/out_fd < 0, &d_out, &nb, st, stream);
   if (rc) return rc;
-  struct OutGuard { void* p; hipStream_t s; ~OutGuard() { if (p) (void)hipFreeAsync(p, s); } } og{d_out, stream};
-  if (out_fd < 0 || nb == 0) return SCFQ_OK;
+  DevBuf result;
+  result.adopt(d_out, stream);
+  if (out_fd < 0 || nb == 0) { in.mark_clean(); return SCFQ_OK; }
   // HBM -> two pinned buffers -> write(): the copy of chunk k+1 overlaps the write of chunk k
   const uint64_t chunk = 32ull << 20;
   uint8_t* pin[2] = {nullptr, nullptr};
   hipEvent_t ev[2] = {nullptr, nullptr};
-  for (int b = 0; b < 2; ++b) { DCHK(hipHostMalloc(&pin[b], chunk, hipHostMallocDefault)); DCHK(hipEventCreateWithFlags(&ev[b], hipEventDisableTiming)); }
+  for (int b = 0; b < 2; ++b) { SCFQ_SCRATCH_CHK(g_derr, hipHostMalloc(&pin[b], chunk, hipHostMallocDefault)); SCFQ_SCRATCH_CHK(g_derr, hipEventCreateWithFlags(&ev[b], hipEventDisableTiming)); }
   struct PinGuard { uint8_t** p; hipEvent_t* e; ~PinGuard() { for (int b = 0; b < 2; ++b) { if (p[b]) (void)hipHostFree(p[b]); if (e[b]) (void)hipEventDestroy(e[b]); } } } pg{pin, ev};
   const uint64_t n_chunks = (nb + chunk - 1) / chunk;
   auto issue = [&](uint64_t k) -> hipError_t {
@@ -850,14 +683,14 @@ int scfq_dedup_file(const char* path, const scfq_opts* opts, int out_fd, scfq_de
     hipError_t e = hipMemcpyAsync(pin[k & 1], d_out + lo, len, hipMemcpyDeviceToHost, stream);
     return e != hipSuccess ? e : hipEventRecord(ev[k & 1], stream);
   };
-  DCHK(issue(0));
+  SCFQ_SCRATCH_CHK(g_derr, issue(0));
   for (uint64_t k = 0; k < n_chunks; ++k) {
-    DCHK(hipEventSynchronize(ev[k & 1]));
-    if (k + 1 < n_chunks) DCHK(issue(k + 1));
+    SCFQ_SCRATCH_CHK(g_derr, hipEventSynchronize(ev[k & 1]));
+    if (k + 1 < n_chunks) SCFQ_SCRATCH_CHK(g_derr, issue(k + 1));
     const uint64_t lo = k * chunk, len = std::min(chunk, nb - lo);
     if ((rc = write_all(out_fd, pin[k & 1], len))) return rc;
   }
-  return SCFQ_OK;
+  return SCFQ_OK;      // (the last chunk was waited for by its event, not by the stream: the lease waits)
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 // (min / max / N50 / N90, length, GC and mean-quality histograms).  Not in the reference; definitions in include/sc_fqcount.h.
 //
 // The whole (inflated) input sits in HBM, as for fq-dedup:
-//   K5  line index            (scfq_index_lines_ex2: line_off[0 .. lines], and whether the input holds "\r\n" at all)
+//   K5  line index            (scfq_scratch::build_line_index: line_off[0 .. lines], and whether the input holds "\r\n" at all)
 //   R0  rs_borders            a thread per tile: first[t] = the first line that starts at or after the tile's first byte, and the one
 //                             table entry that tile shares with the tile before it is zeroed
 //   R1  rs_reduce             the segmented reduction, partitioned by BYTES: a block per 32 KiB tile.  Its stretch of line_off goes to
@@ -26,7 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
-#include "scfq_index_aux.hpp"
+#include "scfq_record_device.hpp"
 #include "scfq_scratch.hpp"
 
 #include <algorithm>
@@ -36,34 +36,10 @@
 
 namespace {
 
-thread_local char g_rerr[512] = "";
+thread_local char g_rerr[scfq_scratch::kErrBytes] = "";
 thread_local double g_stage_ms[4] = {0, 0, 0, 0};
 
-#define RCHK(call)                                                                                          \
-  do {                                                                                                      \
-    hipError_t e_ = (call);                                                                                 \
-    if (e_ != hipSuccess) {                                                                                 \
-      std::snprintf(g_rerr, sizeof g_rerr, "%s -> %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-      if (std::getenv("SCFQ_VERBOSE")) std::fprintf(stderr, "scfq: %s\n", g_rerr);                          \
-      return SCFQ_EHIP;                                                                                     \
-    }                                                                                                       \
-  } while (0)
-
-struct Lease {
-  hipStream_t s = nullptr;
-  int dev = -1;
-  bool clean = false;
-  ~Lease() { if (s) scfq_scratch::return_stream(s, dev, clean); }
-};
-
-struct Buf {   // pool memory, returned stream-ordered on scope exit
-  void* p = nullptr;
-  hipStream_t s = nullptr;
-  ~Buf() { if (p) (void)hipFreeAsync(p, s); }
-  template <typename T> T* as() { return static_cast<T*>(p); }
-  int alloc(size_t bytes, hipStream_t stream) { s = stream; return scfq_scratch::pool_alloc(&p, bytes, stream); }
-  void drop() { if (p) (void)hipFreeAsync(p, s); p = nullptr; }
-};
+using scfq_scratch::DevBuf;
 
 constexpr uint32_t kRsTile = 32768;        // bytes of input a block of R1 owns
 constexpr uint32_t kRsThreads = 256;
@@ -88,12 +64,11 @@ __device__ __forceinline__ uint64_t tile_lo(uint64_t t, uint32_t shift, uint64_t
   return a <= shift ? 0 : std::min<uint64_t>(a - shift, n);
 }
 
-// text length of line k (0 for a line the input does not have): line_span of scfq_dedup.hip
+// text length of line k (0 for a line the input does not have)
 __device__ __forceinline__ uint64_t line_text_len(const uint8_t* base, uint64_t n, const uint64_t* line_off, uint64_t lines, uint64_t k, bool has_cr) {
   if (k >= lines) return 0;
-  const uint64_t s = line_off[k], nl = line_off[k + 1] - 1;
-  uint64_t e = nl;
-  if (has_cr && nl < n && e > s && base[e - 1] == '\r') --e;
+  uint64_t s, e;
+  line_span(base, n, line_off, k, s, e, has_cr);
   return e - s;
 }
 
@@ -293,11 +268,6 @@ constexpr uint32_t kSumWords = kSumHead + kHistWords;
 __device__ __forceinline__ uint64_t div_floor(uint64_t a, uint64_t b) {      // (b > 0) 64-bit division is a long routine on this device
   return ((a | b) >> 32) == 0 ? (uint64_t)((uint32_t)a / (uint32_t)b) : a / b;
 }
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor((unsigned long long)v, o, 64);
-  return v;
-}
 
 __global__ __launch_bounds__(256) void rs_summarise(const scfq_read_rec* rec, uint64_t reads, unsigned long long* sum) {
   __shared__ uint32_t hist[kHistWords];
@@ -364,55 +334,19 @@ __global__ __launch_bounds__(256) void rs_find_nx(const uint64_t* sorted, const 
   if (a >= bases * 90 && before < bases * 90) { out[2] = sorted[i]; out[3] = i + 1; }
 }
 
-struct StageClock {      // HIP-event brackets, only with SCFQ_READSTATS_TIMING=1
-  bool on;
-  hipStream_t s;
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  bool set[5] = {false, false, false, false, false};
-  StageClock(hipStream_t stream) : s(stream) {
-    static const bool env = [] { const char* e = std::getenv("SCFQ_READSTATS_TIMING"); return e && std::atoi(e) != 0; }();
-    on = env;
-    if (on) for (auto& e : ev) if (hipEventCreate(&e) != hipSuccess) { on = false; break; }
-  }
-  ~StageClock() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
-  void mark(int k) { if (on && hipEventRecord(ev[k], s) == hipSuccess) set[k] = true; }
-  double between(int a, int b) {
-    float ms = 0;
-    return (on && set[a] && set[b] && hipEventElapsedTime(&ms, ev[a], ev[b]) == hipSuccess) ? (double)ms : 0.0;
-  }
-};
-
-void clear_summary(scfq_read_summary* out) {
-  const uint64_t keep = out->struct_size;
-  std::memset(out, 0, sizeof *out);
-  out->struct_size = keep;
-  out->abi_version = SCFQ_ABI_VERSION;
-}
-
 // d_in: the whole input, resident; user_rec / cap: the caller's table or nullptr
 int readstats_device(const uint8_t* d_in, uint64_t n, scfq_read_rec* user_rec, uint64_t cap, scfq_read_summary* out, hipStream_t stream) {
   for (double& m : g_stage_ms) m = 0;
   out->input_bytes = n;
   uint64_t lines = 0;
-  uint32_t index_flags = 1;
-  Buf line_off, table, first, sum, keys, keys2, acc, tmp, nx;
+  DevBuf line_off, table, first, sum, keys, keys2, acc, tmp, nx;
   int rc = SCFQ_OK;
+  bool has_cr = true;
   {
-    // the index's size is guessed first, as fq-dedup does: only a wrong guess costs a second pass with the exact size
-    uint64_t lcap = n / 24 + 1024;
     const auto t_a = std::chrono::steady_clock::now();
-    for (int round = 0; round < 2; ++round) {
-      if ((rc = line_off.alloc(lcap * 8, stream))) return rc;
-      RCHK(hipStreamSynchronize(stream));       // scfq_index_lines works on the library's own stream
-      rc = scfq_index_lines_ex2(d_in, n, line_off.as<uint64_t>(), lcap, &lines, &index_flags, nullptr);
-      if (rc) return rc;
-      if (lines + 1 <= lcap) break;
-      line_off.drop();
-      lcap = lines + 1;
-    }
+    if ((rc = scfq_scratch::build_line_index(d_in, n, stream, g_rerr, line_off, &lines, &has_cr))) return rc;
     g_stage_ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_a).count();
   }
-  const bool has_cr = (index_flags & 1u) != 0;
   const uint64_t reads = (lines + 3) / 4;
   out->lines = lines;
   out->reads = reads;
@@ -421,31 +355,32 @@ int readstats_device(const uint8_t* d_in, uint64_t n, scfq_read_rec* user_rec, u
   if (reads == 0) return SCFQ_OK;
   scfq_read_rec* rec = user_rec;
   if (!rec) {
-    if ((rc = table.alloc(reads * sizeof(scfq_read_rec), stream))) return rc;
+    if ((rc = table.alloc(reads * sizeof(scfq_read_rec), stream, g_rerr))) return rc;
     rec = table.as<scfq_read_rec>();
   }
   const uint32_t shift = (uint32_t)((uintptr_t)d_in & 15u);
   const uint64_t n_tiles = (n + shift + kRsTile - 1) / kRsTile;
   if (n_tiles >= (1ull << 31)) { std::snprintf(g_rerr, sizeof g_rerr, "input too large for one launch"); return SCFQ_EARG; }
-  if ((rc = first.alloc((n_tiles + 1) * 8, stream)) || (rc = sum.alloc(kSumWords * 8, stream))) return rc;
-  StageClock clk(stream);
+  if ((rc = first.alloc((n_tiles + 1) * 8, stream, g_rerr)) || (rc = sum.alloc(kSumWords * 8, stream, g_rerr))) return rc;
+  static const bool timing = scfq_scratch::env_switch("SCFQ_READSTATS_TIMING");
+  scfq_scratch::StageClock clk(stream, timing);
   clk.mark(0);
   hipLaunchKernelGGL(rs_borders, dim3((unsigned)((n_tiles + 1 + 255) / 256)), dim3(256), 0, stream, line_off.as<uint64_t>(), lines, n, shift, n_tiles,
                      first.as<uint64_t>(), rec);
-  RCHK(hipGetLastError());
+  SCFQ_SCRATCH_CHK(g_rerr, hipGetLastError());
   hipLaunchKernelGGL(rs_reduce, dim3((unsigned)n_tiles), dim3(kRsThreads), 0, stream, d_in, n, line_off.as<uint64_t>(), lines, shift, n_tiles,
                      first.as<uint64_t>(), has_cr, rec);
-  RCHK(hipGetLastError());
+  SCFQ_SCRATCH_CHK(g_rerr, hipGetLastError());
   clk.mark(1);
-  RCHK(hipMemsetAsync(sum.p, 0, kSumWords * 8, stream));
-  RCHK(hipMemsetAsync(sum.as<uint64_t>() + 5, 0xff, 8, stream));      // min_len starts at all ones
+  SCFQ_SCRATCH_CHK(g_rerr, hipMemsetAsync(sum.p, 0, kSumWords * 8, stream));
+  SCFQ_SCRATCH_CHK(g_rerr, hipMemsetAsync(sum.as<uint64_t>() + 5, 0xff, 8, stream));      // min_len starts at all ones
   hipLaunchKernelGGL(rs_summarise, dim3((unsigned)std::min<uint64_t>((reads + 255) / 256, 2048)), dim3(256), 0, stream, rec, reads,
                      sum.as<unsigned long long>());
-  RCHK(hipGetLastError());
+  SCFQ_SCRATCH_CHK(g_rerr, hipGetLastError());
   clk.mark(2);
   static thread_local uint64_t h[kSumWords];
-  RCHK(hipMemcpyAsync(h, sum.p, kSumWords * 8, hipMemcpyDeviceToHost, stream));
-  RCHK(hipStreamSynchronize(stream));
+  SCFQ_SCRATCH_CHK(g_rerr, hipMemcpyAsync(h, sum.p, kSumWords * 8, hipMemcpyDeviceToHost, stream));
+  SCFQ_SCRATCH_CHK(g_rerr, hipStreamSynchronize(stream));
   out->bases = h[0]; out->gc_bases = h[1]; out->n_bases = h[2]; out->qual_bytes = h[3]; out->qual_sum = h[4];
   out->min_len = h[5]; out->max_len = h[6]; out->no_qual = h[7];
   std::memcpy(out->len_hist, h + kSumHead, SCFQ_LEN_HIST_BINS * 8);
@@ -459,23 +394,23 @@ int readstats_device(const uint8_t* d_in, uint64_t n, scfq_read_rec* user_rec, u
   } else if (out->bases != 0) {
     if (out->bases >= (1ull << 57)) { std::snprintf(g_rerr, sizeof g_rerr, "more than 2^57 bases in one input"); return SCFQ_EARG; }
     const unsigned bits = 64u - (unsigned)__builtin_clzll(out->max_len);
-    if ((rc = keys.alloc(reads * 8, stream)) || (rc = keys2.alloc(reads * 8, stream)) || (rc = acc.alloc(reads * 8, stream)) || (rc = nx.alloc(32, stream))) return rc;
+    if ((rc = keys.alloc(reads * 8, stream, g_rerr)) || (rc = keys2.alloc(reads * 8, stream, g_rerr)) || (rc = acc.alloc(reads * 8, stream, g_rerr)) || (rc = nx.alloc(32, stream, g_rerr))) return rc;
     const unsigned blocks = (unsigned)((reads + 255) / 256);
     hipLaunchKernelGGL(rs_lengths, dim3(blocks), dim3(256), 0, stream, rec, reads, keys.as<uint64_t>());
-    RCHK(hipGetLastError());
+    SCFQ_SCRATCH_CHK(g_rerr, hipGetLastError());
     size_t sort_bytes = 0, scan_bytes = 0;
-    RCHK(rocprim::radix_sort_keys_desc(nullptr, sort_bytes, keys.as<uint64_t>(), keys2.as<uint64_t>(), (size_t)reads, 0u, bits, stream));
-    RCHK(rocprim::inclusive_scan(nullptr, scan_bytes, keys2.as<uint64_t>(), acc.as<uint64_t>(), (size_t)reads, rocprim::plus<uint64_t>(), stream));
-    if ((rc = tmp.alloc(std::max(sort_bytes, scan_bytes), stream))) return rc;
-    RCHK(rocprim::radix_sort_keys_desc(tmp.p, sort_bytes, keys.as<uint64_t>(), keys2.as<uint64_t>(), (size_t)reads, 0u, bits, stream));
-    RCHK(rocprim::inclusive_scan(tmp.p, scan_bytes, keys2.as<uint64_t>(), acc.as<uint64_t>(), (size_t)reads, rocprim::plus<uint64_t>(), stream));
-    RCHK(hipMemsetAsync(nx.p, 0, 32, stream));
+    SCFQ_SCRATCH_CHK(g_rerr, rocprim::radix_sort_keys_desc(nullptr, sort_bytes, keys.as<uint64_t>(), keys2.as<uint64_t>(), (size_t)reads, 0u, bits, stream));
+    SCFQ_SCRATCH_CHK(g_rerr, rocprim::inclusive_scan(nullptr, scan_bytes, keys2.as<uint64_t>(), acc.as<uint64_t>(), (size_t)reads, rocprim::plus<uint64_t>(), stream));
+    if ((rc = tmp.alloc(std::max(sort_bytes, scan_bytes), stream, g_rerr))) return rc;
+    SCFQ_SCRATCH_CHK(g_rerr, rocprim::radix_sort_keys_desc(tmp.p, sort_bytes, keys.as<uint64_t>(), keys2.as<uint64_t>(), (size_t)reads, 0u, bits, stream));
+    SCFQ_SCRATCH_CHK(g_rerr, rocprim::inclusive_scan(tmp.p, scan_bytes, keys2.as<uint64_t>(), acc.as<uint64_t>(), (size_t)reads, rocprim::plus<uint64_t>(), stream));
+    SCFQ_SCRATCH_CHK(g_rerr, hipMemsetAsync(nx.p, 0, 32, stream));
     hipLaunchKernelGGL(rs_find_nx, dim3(blocks), dim3(256), 0, stream, keys2.as<uint64_t>(), acc.as<uint64_t>(), reads, out->bases, nx.as<uint64_t>());
-    RCHK(hipGetLastError());
+    SCFQ_SCRATCH_CHK(g_rerr, hipGetLastError());
     clk.mark(3);
     uint64_t r4[4] = {0, 0, 0, 0};
-    RCHK(hipMemcpyAsync(r4, nx.p, 32, hipMemcpyDeviceToHost, stream));
-    RCHK(hipStreamSynchronize(stream));
+    SCFQ_SCRATCH_CHK(g_rerr, hipMemcpyAsync(r4, nx.p, 32, hipMemcpyDeviceToHost, stream));
+    SCFQ_SCRATCH_CHK(g_rerr, hipStreamSynchronize(stream));
     out->n50 = r4[0]; out->l50 = r4[1]; out->n90 = r4[2]; out->l90 = r4[3];
   }
   g_stage_ms[1] = clk.between(0, 1);
@@ -490,45 +425,30 @@ extern "C" {
 
 const char* scfq_read_stats_error_detail(void) { return g_rerr; }
 
-int scfq_debug_read_stats_stages(double* ms, uint32_t cap) {
-  for (uint32_t k = 0; ms && k < cap && k < 4; ++k) ms[k] = g_stage_ms[k];
-  return 4;
-}
+int scfq_debug_read_stats_stages(double* ms, uint32_t cap) { return scfq_scratch::copy_stage_ms(g_stage_ms, ms, cap); }
 
 int scfq_read_stats_buffer(const void* ptr, uint64_t n, int is_device, scfq_read_rec* records_device, uint64_t cap, scfq_read_summary* out) {
   if (!out || out->struct_size != sizeof(scfq_read_summary) || (!ptr && n)) return SCFQ_EARG;
-  clear_summary(out);
+  scfq_scratch::clear_keep_size(out);
   g_rerr[0] = '\0';
-  Lease lease;
-  { const int rc = scfq_scratch::lease_stream(&lease.s, &lease.dev); if (rc) return rc; }
-  const hipStream_t stream = lease.s;
-  Buf staged;
-  const uint8_t* d_in = static_cast<const uint8_t*>(ptr);
-  if (is_device || records_device) { const int rc = scfq_scratch::order_after_caller(stream); if (rc) return rc; }
-  if (!is_device && n) {
-    const int rc = staged.alloc(n, stream);
-    if (rc) return rc;
-    RCHK(hipMemcpyAsync(staged.p, ptr, n, hipMemcpyHostToDevice, stream));
-    RCHK(hipStreamSynchronize(stream));
-    d_in = staged.as<uint8_t>();
-  }
-  const int rc = readstats_device(d_in, n, records_device, cap, out, stream);
-  if (rc == SCFQ_OK) lease.clean = true;      // (its last act was to wait for the stream)
+  scfq_scratch::ResidentInput in;
+  int rc = in.from_buffer(ptr, n, is_device != 0, is_device || records_device, g_rerr);
+  if (rc) return rc;
+  rc = readstats_device(in.d_in, n, records_device, cap, out, in.stream);
+  if (rc == SCFQ_OK) in.mark_clean();      // (its last act was to wait for the stream)
   return rc;
 }
 
 int scfq_read_stats_file(const char* path, const scfq_opts* opts, scfq_read_summary* out) {
   if (!path || !out || out->struct_size != sizeof(scfq_read_summary)) return SCFQ_EARG;
-  clear_summary(out);
+  scfq_scratch::clear_keep_size(out);
   g_rerr[0] = '\0';
-  void* d_in = nullptr;
-  uint64_t n = 0;
-  int rc = scfq_stage_file(path, opts, &d_in, &n);      // whole (inflated) input into HBM
+  scfq_scratch::ResidentInput in;
+  int rc = in.from_file(path, opts, g_rerr);
   if (rc) return rc;
-  struct InGuard { void* p; ~InGuard() { if (p) (void)hipFree(p); } } ig{d_in};
-  Lease lease;
-  if ((rc = scfq_scratch::lease_stream(&lease.s, &lease.dev))) return rc;
-  return readstats_device(static_cast<const uint8_t*>(d_in), n, nullptr, 0, out, lease.s);
+  rc = readstats_device(in.d_in, in.n, nullptr, 0, out, in.stream);
+  if (rc == SCFQ_OK) in.mark_clean();      // (its last act was to wait for the stream)
+  return rc;
 }
 
 }  // extern "C"
