@@ -358,6 +358,55 @@ int scfq_cycles_file(const char* path, const scfq_opts* opts, scfq_cycle_row* ro
 int scfq_format_cycle_row_tsv(const scfq_cycle_row* r, char* buf, uint64_t cap);
 const char* scfq_cycles_error_detail(void);   /* static, thread-local */
 
+/* ---- `sc fq-kmers` (addition; not in the reference): the k-mer spectrum of the sequence lines ------------------------
+ * Lines and records are those of fq-readstats above. For 1 <= k <= SCFQ_KMERS_MAX_K a window is k consecutive text bytes
+ * of one sequence line (4i+1): a line of length L has max(0, L - k + 1) of them, and counts in short_lines when L < k. A
+ * window is a k-mer iff every byte is exactly 'A', 'C', 'G' or 'T' (case-sensitive, as scfq_counts.gc_bases); any other
+ * byte ('N', lower case, an interior '\r', high bytes) makes it skipped: windows = kmers + skipped. With the codes A = 0,
+ * C = 1, G = 2, T = 3 and the first base most significant, index = sum of code[i] * 4^(k-1-i): index order is
+ * lexicographic order, the table has 4^k entries. SCFQ_KMERS_CANONICAL counts a k-mer at min(index, rc(index)), rc being
+ * the reverse complement (3 - code, reversed); a palindrome is counted once per occurrence, entries that are not their
+ * own minimum stay 0. All values are integers and exact. Device pipeline over the HBM-resident input: line index (K5),
+ * M1 — the counting kernel, partitioned by BYTES (a block owns a run of aligned 8 KiB steps and follows the lines through
+ * the newlines it sees), 32-bit counters in LDS for k <= 7, 64-bit atomic adds on the table in HBM for k >= 8 — and M2,
+ * a pass over the table for distinct and max_count. */
+#define SCFQ_KMERS_MAX_K     12
+#define SCFQ_KMERS_CANONICAL 0x1u
+typedef struct scfq_kmer_summary {
+  uint64_t struct_size;   /* caller sets to sizeof(scfq_kmer_summary) before the call */
+  uint64_t abi_version;   /* library writes SCFQ_ABI_VERSION */
+  uint64_t reads;         /* ceil(lines / 4) */
+  uint64_t lines;
+  uint64_t input_bytes;   /* bytes scanned (inflated bytes for .gz) */
+  uint64_t k;
+  uint64_t flags;
+  uint64_t windows;       /* kmers + skipped */
+  uint64_t kmers;         /* the sum of the table */
+  uint64_t skipped;       /* windows with a byte that is not A C G T */
+  uint64_t short_lines;   /* sequence lines shorter than k */
+  uint64_t distinct;      /* non-zero entries of the table */
+  uint64_t max_count;     /* the largest entry */
+  uint64_t table_entries; /* 4^k */
+} scfq_kmer_summary;
+
+/* Input in host (is_device = 0) or device memory. table_host: HOST memory for `cap` entries. cap = 0 is the sizing and
+ * summary call: the whole summary is filled (distinct and max_count included), table_host is not touched and may be NULL.
+ * With cap >= 4^k entries [0, 4^k) are written and entries [4^k, cap) are not touched. The summary does not depend on cap.
+ * SCFQ_EARG with text in scfq_kmers_error_detail(): 0 < cap < 4^k, k = 0 or k > SCFQ_KMERS_MAX_K, unknown flag bits;
+ * SCFQ_EARG also for a NULL out or a wrong struct_size, NULL ptr with n > 0, NULL table_host with cap > 0. Device pointers
+ * follow the scfq_set_wait_stream contract of scfq_index_lines. One device, the whole input resident, fewer than 2^31
+ * records, as scfq_cycles_buffer; there is no CPU fallback (SCFQ_EHIP without a device). */
+int scfq_kmers_buffer(const void* ptr, uint64_t n, int is_device, uint32_t k, uint32_t flags, uint64_t* table_host,
+                      uint64_t cap, scfq_kmer_summary* out);
+/* Stages the whole (inflated) input with scfq_stage_file, ".gz" and BGZF by suffix as everywhere else. */
+int scfq_kmers_file(const char* path, const scfq_opts* opts, uint32_t k, uint32_t flags, uint64_t* table_host,
+                    uint64_t cap, scfq_kmer_summary* out);
+/* "<kmer>\t<count>" without trailing newline, e.g. "ACGT\t12": the k letters of `index`, first base first. Returns the
+ * number of bytes needed (excluding NUL); writes at most cap bytes incl. NUL, as scfq_format_cycle_row_tsv. SCFQ_EARG for
+ * k = 0, k > SCFQ_KMERS_MAX_K or index >= 4^k. */
+int scfq_format_kmer_tsv(uint32_t k, uint64_t index, uint64_t count, char* buf, uint64_t cap);
+const char* scfq_kmers_error_detail(void);    /* static, thread-local */
+
 /* Whole (inflated) input of `path` into a device buffer the caller frees with scfq_device_free(). */
 int scfq_stage_file(const char* path, const scfq_opts* opts, void** device_ptr_out, uint64_t* n_out);
 int scfq_device_free(void* device_ptr);

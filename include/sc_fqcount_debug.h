@@ -64,6 +64,11 @@ int scfq_debug_read_stats_stages(double* ms, uint32_t cap);
  * ms[3] finish (rows, tail, total; without the copy to the host) — [1..3] are HIP-event times, taken only while
  * SCFQ_CYCLES_TIMING=1 is in the environment (zeros otherwise). Writes min(cap, 4) values, returns 4. */
 int scfq_debug_cycles_stages(double* ms, uint32_t cap);
+/* Stage times of the calling thread's last scfq_kmers_buffer / scfq_kmers_file, in milliseconds: ms[0] line index (host
+ * clock around the synchronous index call), ms[1] M1, the counting kernel, ms[2] finish (distinct, max_count, sum), ms[3] the
+ * copies to the host (table and summary) — [1..3] are HIP-event times, taken only while SCFQ_KMERS_TIMING=1 is in the
+ * environment (zeros otherwise). Writes min(cap, 4) values, returns 4. */
+int scfq_debug_kmers_stages(double* ms, uint32_t cap);
 
 #ifdef __cplusplus
 }

@@ -132,7 +132,8 @@ static void help_top(FILE* f) {
                "Usage:\n  sc COMMAND\n\nCommands:\n\nFASTQ\n  fq-count         Counts lines in a FASTQ\n"
                "  fq-dedup         Removes exact duplicates from FASTQ Files\n  fq-meta          Output metadata for FASTQ\n"
                "  fq-readstats     Per-read length, N50, GC and quality of a FASTQ\n"
-               "  fq-cycles        Per-position base composition and quality of a FASTQ\n\n"
+               "  fq-cycles        Per-position base composition and quality of a FASTQ\n"
+               "  fq-kmers         K-mer spectrum of the sequence lines of a FASTQ\n\n"
                "Options:\n  -h, --help                 Show this help\n  -v, --version              Show version\n"
                "      --debug                Debug mode\n",
                kVersion);
@@ -468,6 +469,102 @@ static int cmd_fq_cycles(const std::vector<std::string>& params) {
   return 0;
 }
 
+// command "fq-kmers" (addition, not in the reference): -t/--header, -b/--basename, -a/--absolute as fq-count, --k=N, --canonical, --top=N,
+// --totals, [fastq ...]
+static const char* kKmersHeader = "kmer\tcount";
+static const char* kKmersTotalsHeader = "k\twindows\tkmers\tskipped\tshort_lines\tdistinct\tmax_count";
+static int cmd_fq_kmers(const std::vector<std::string>& params) {
+  auto help = [](FILE* f) {
+    std::fputs("K-mer spectrum of the sequence lines of a FASTQ\n\nUsage:\n  fq-kmers [options] [fastq ...]\n\nArguments:\n"
+               "  [fastq ...]      Input FASTQ\n\nOptions:\n  -t, --header               Output the header\n"
+               "  -b, --basename             Add basename column\n  -a, --absolute             Add column for absolute path\n"
+               "      --k=N                  Length of the k-mers, 1 .. 12 (default: 7); only windows of A C G T count\n"
+               "      --canonical            Count a k-mer and its reverse complement as the smaller of the two\n"
+               "      --top=N                The N largest counts, ties in k-mer order (default: every k-mer that occurs, in\n"
+               "                             k-mer order)\n"
+               "      --totals               One row per file instead: k windows kmers skipped short_lines distinct max_count\n"
+               "  -h, --help                 Show this help\n", f);
+  };
+  if (params.size() == 1) { help(stdout); return 0; }
+  bool header = false, basename = false, absolute = false, only_positional = false, canonical = false, totals = false, has_top = false;
+  uint32_t k = 7;
+  uint64_t top = 0;
+  std::vector<std::string> files;
+  auto number = [&](const std::string& v, const char* opt, uint64_t lo, uint64_t hi) -> uint64_t {
+    const bool digits = !v.empty() && v.size() <= 18 && v.find_first_not_of("0123456789") == std::string::npos;
+    if (!digits || std::stoull(v) < lo || std::stoull(v) > hi) { help(stdout); quit_error(std::string("Error: Bad value for ") + opt + ": " + v, 1); }
+    return std::stoull(v);
+  };
+  for (size_t i = 1; i < params.size(); ++i) {
+    const std::string& a = params[i];
+    if (only_positional || a.empty() || a[0] != '-' || a == "-") { files.push_back(a); continue; }
+    if (a == "--") { only_positional = true; continue; }
+    if (a == "-h" || a == "--help") { help(stdout); return 0; }
+    if (a == "--header") header = true;
+    else if (a == "--basename") basename = true;
+    else if (a == "--absolute") absolute = true;
+    else if (a == "--canonical") canonical = true;
+    else if (a == "--totals") totals = true;
+    else if (a.compare(0, 4, "--k=") == 0) k = (uint32_t)number(a.substr(4), "--k", 1, SCFQ_KMERS_MAX_K);
+    else if (a.compare(0, 6, "--top=") == 0) { top = number(a.substr(6), "--top", 0, ~0ull); has_top = true; }
+    else if (a.size() >= 2 && a[1] != '-') {
+      for (size_t j = 1; j < a.size(); ++j) {
+        if (a[j] == 't') header = true;
+        else if (a[j] == 'b') basename = true;
+        else if (a[j] == 'a') absolute = true;
+        else if (a[j] == 'h') { help(stdout); return 0; }
+        else { help(stdout); quit_error(std::string("Error: Unknown option: -") + a[j], 1); }
+      }
+    } else {
+      help(stdout);
+      quit_error("Error: Unknown option: " + a, 1);
+    }
+  }
+  if (header) std::printf("%s\n", output_header(totals ? kKmersTotalsHeader : kKmersHeader, basename, absolute).c_str());
+  else if (files.empty()) quit_error("No FASTQ specified", 3);
+  const uint64_t entries = 1ull << (2 * k);
+  std::vector<uint64_t> table(totals ? 0 : entries);
+  std::vector<uint64_t> order;
+  for (const auto& fastq : files) {
+    if (fastq.size() < 3) quit_error("index out of bounds", 1);
+    scfq_kmer_summary s;
+    std::memset(&s, 0, sizeof s);
+    s.struct_size = sizeof s;
+    const int rc = scfq_kmers_file(fastq.c_str(), nullptr, k, canonical ? SCFQ_KMERS_CANONICAL : 0u, table.empty() ? nullptr : table.data(),
+                                   table.size(), &s);
+    if (rc == SCFQ_EOPEN) quit_error("Unable to open file: " + fastq, fastq.compare(fastq.size() - 3, 3, ".gz") == 0 ? 1 : 2);   // as fq-count
+    if (rc != SCFQ_OK) {
+      std::string msg = scfq_strerror(rc);
+      const char* d = *scfq_kmers_error_detail() ? scfq_kmers_error_detail() : scfq_last_error_detail();
+      if (d && *d) { msg += ": "; msg += d; }
+      quit_error(msg, 1);
+    }
+    char row[64];
+    if (totals) {
+      const std::string line = std::to_string(s.k) + "\t" + std::to_string(s.windows) + "\t" + std::to_string(s.kmers) + "\t" +
+                               std::to_string(s.skipped) + "\t" + std::to_string(s.short_lines) + "\t" + std::to_string(s.distinct) + "\t" +
+                               std::to_string(s.max_count);
+      std::printf("%s\n", output_w_fnames(line, fastq, basename, absolute).c_str());
+      continue;
+    }
+    order.clear();
+    for (uint64_t e = 0; e < entries; ++e) if (table[e]) order.push_back(e);
+    if (has_top) {
+      // the N largest counts, ties by ascending index (order is ascending already)
+      const size_t keep = (size_t)std::min<uint64_t>(top, order.size());
+      std::partial_sort(order.begin(), order.begin() + keep, order.end(),
+                        [&](uint64_t a, uint64_t b) { return table[a] != table[b] ? table[a] > table[b] : a < b; });
+      order.resize(keep);
+    }
+    for (const uint64_t e : order) {
+      scfq_format_kmer_tsv(k, e, table[e], row, sizeof row);
+      std::printf("%s\n", output_w_fnames(row, fastq, basename, absolute).c_str());
+    }
+  }
+  std::fflush(stdout);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   scfq_debug_stage_mark("sc: main entered");
   signal(SIGPIPE, SIG_IGN);   // sc.nim:45-46
@@ -481,6 +578,7 @@ int main(int argc, char** argv) {
   if (params[0] == "fq-meta") return cmd_fq_meta(params);
   if (params[0] == "fq-readstats") return cmd_fq_readstats(params);
   if (params[0] == "fq-cycles") return cmd_fq_cycles(params);
+  if (params[0] == "fq-kmers") return cmd_fq_kmers(params);
   if (params[0] != "fq-count") {
     help_top(stdout);
     quit_error("Unknown command: " + params[0] + " (this build provides the FASTQ commands only)", 1);

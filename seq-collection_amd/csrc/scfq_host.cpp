@@ -146,6 +146,20 @@ int scfq_format_cycle_row_tsv(const scfq_cycle_row* r, char* buf, uint64_t cap) 
   return m;
 }
 
+// the fq-kmers row: the k letters of the index, first base first, and the count
+int scfq_format_kmer_tsv(uint32_t k, uint64_t index, uint64_t count, char* buf, uint64_t cap) {
+  if (k < 1 || k > SCFQ_KMERS_MAX_K || index >> (2 * k)) return SCFQ_EARG;
+  char tmp[64];
+  for (uint32_t i = 0; i < k; ++i) tmp[i] = "ACGT"[(index >> (2 * (k - 1 - i))) & 3u];
+  const int m = (int)k + std::snprintf(tmp + k, sizeof tmp - k, "\t%llu", (unsigned long long)count);
+  if (buf && cap) {
+    const uint64_t ncopy = ((uint64_t)m < cap - 1) ? (uint64_t)m : cap - 1;
+    std::memcpy(buf, tmp, ncopy);
+    buf[ncopy] = 0;
+  }
+  return m;
+}
+
 const char* scfq_strerror(int rc) {
   switch (rc) {
     case SCFQ_OK: return "ok";

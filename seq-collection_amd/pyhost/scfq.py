@@ -48,6 +48,7 @@ EXPORTS = [
     "scfq_read_stats_buffer", "scfq_read_stats_file", "scfq_format_read_stats_tsv", "scfq_read_stats_error_detail",
     "scfq_debug_read_stats_stages",
     "scfq_cycles_buffer", "scfq_cycles_file", "scfq_format_cycle_row_tsv", "scfq_cycles_error_detail", "scfq_debug_cycles_stages",
+    "scfq_kmers_buffer", "scfq_kmers_file", "scfq_format_kmer_tsv", "scfq_kmers_error_detail", "scfq_debug_kmers_stages",
 ]
 
 
@@ -119,6 +120,17 @@ class CycleRow(ctypes.Structure):
 class CycleSummary(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in ("struct_size", "abi_version", "reads", "lines", "input_bytes", "max_seq_len", "max_qual_len",
                                                "cycles")] + [("tail", CycleRow), ("total", CycleRow)]
+
+
+KMERS_MAX_K = 12
+SCFQ_KMERS_CANONICAL = 0x1
+KMER_SUMMARY_FIELDS = ("struct_size", "abi_version", "reads", "lines", "input_bytes", "k", "flags", "windows", "kmers", "skipped",
+                       "short_lines", "distinct", "max_count", "table_entries")
+
+
+class KmerSummary(ctypes.Structure):
+    """scfq_kmer_summary (fourteen uint64)"""
+    _fields_ = [(n, ctypes.c_uint64) for n in KMER_SUMMARY_FIELDS]
 
 
 class SynthInfo(ctypes.Structure):
@@ -222,6 +234,13 @@ def lib():
         L.scfq_format_cycle_row_tsv.argtypes = [ctypes.POINTER(CycleRow), ctypes.c_char_p, ctypes.c_uint64]
         L.scfq_cycles_error_detail.restype = ctypes.c_char_p
         L.scfq_debug_cycles_stages.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]
+        L.scfq_kmers_buffer.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                        ctypes.c_uint64, ctypes.POINTER(KmerSummary)]
+        L.scfq_kmers_file.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64,
+                                      ctypes.POINTER(KmerSummary)]
+        L.scfq_format_kmer_tsv.argtypes = [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_uint64]
+        L.scfq_kmers_error_detail.restype = ctypes.c_char_p
+        L.scfq_debug_kmers_stages.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]
         _lib = L
     return _lib
 
@@ -540,6 +559,59 @@ def cycles_stages():
     times and zeros unless SCFQ_CYCLES_TIMING=1 is in the environment"""
     ms = (ctypes.c_double * 4)()
     lib().scfq_debug_cycles_stages(ms, 4)
+    return list(ms)
+
+
+def _new_kmer_summary():
+    s = KmerSummary()
+    s.struct_size = ctypes.sizeof(KmerSummary)
+    return s
+
+
+def _kmers_call(fn, what, k, flags, table, *head):
+    """table: None (the sizing and summary call), True (a fresh table of 4^k entries) or a caller's contiguous uint64 array of
+    `cap` entries, filled in place ([4^k, cap) untouched)"""
+    import numpy as np
+    if table is True:
+        table = np.zeros(4 ** k if 1 <= k <= KMERS_MAX_K else 1, dtype=np.uint64)
+    if table is not None:
+        assert isinstance(table, np.ndarray) and table.dtype == np.uint64 and table.ndim == 1 and table.flags.c_contiguous
+    cap = 0 if table is None else table.shape[0]
+    s = _new_kmer_summary()
+    rc = fn(*head, k, flags, ctypes.c_void_p(table.ctypes.data) if cap else None, cap, ctypes.byref(s))
+    if rc != 0:
+        raise ScfqError(rc, what, lib().scfq_kmers_error_detail().decode() or lib().scfq_last_error_detail().decode())
+    return s, (None if table is None else table[:s.table_entries])
+
+
+def kmers_device(dev_ptr, n, k, flags=0, table=None):
+    """fq-kmers of a device-resident FASTQ.  table: None (the sizing and summary call), True (a fresh table) or a uint64 array
+    of at least 4^k entries.  Returns (KmerSummary, the 4^k entries as a uint64 array or None)."""
+    return _kmers_call(lib().scfq_kmers_buffer, "scfq_kmers_buffer", k, flags, table, ctypes.c_void_p(dev_ptr), n, 1)
+
+
+def kmers_host(data, k, flags=0, table=None):
+    """fq-kmers of a host buffer (bytes / numpy uint8)"""
+    addr, n, keep = _host_ptr(data)
+    return _kmers_call(lib().scfq_kmers_buffer, "scfq_kmers_buffer", k, flags, table, addr, n, 0)
+
+
+def kmers_file(path, k, flags=0, table=None):
+    return _kmers_call(lib().scfq_kmers_file, "scfq_kmers_file", k, flags, table, os.fsencode(path), None)
+
+
+def format_kmer_tsv(k, index, count):
+    """"ACGT\\t12": the k letters of `index` and the count"""
+    buf = ctypes.create_string_buffer(64)
+    _check(min(0, lib().scfq_format_kmer_tsv(k, index, count, buf, 64)), "scfq_format_kmer_tsv")
+    return buf.value.decode()
+
+
+def kmers_stages():
+    """(index, counting kernel, finish, copies to the host) milliseconds of this thread's last kmers call; the last three are
+    HIP-event times and zeros unless SCFQ_KMERS_TIMING=1 is in the environment"""
+    ms = (ctypes.c_double * 4)()
+    lib().scfq_debug_kmers_stages(ms, 4)
     return list(ms)
 
 
