@@ -14,6 +14,7 @@
 #include "scfq_bgzf.hpp"
 #include "scfq_gzfast.hpp"
 #include "scfq_pgz.hpp"
+#include "scfq_shard_rules.hpp"
 #include "bgzf_inflate_kernel.hpp"
 #include "gz_inflate_kernels.hpp"
 #include "scfq_arena.hpp"
@@ -217,6 +218,27 @@ struct Ctx {
 struct SessionLock {
   std::unique_lock<std::mutex> lk;
   void acquire(Ctx*) {}   // the context returned by get_ctx() is already locked into this object
+};
+
+int get_ctx(Ctx** out, SessionLock& sl);
+int begin_session(Ctx* c, bool from_start);
+int end_session(Ctx* c, bool hist, scfq_partial* out, uint64_t* hist_out);
+
+// What an entry point holds while it counts: the device the options name, one of its contexts, and that context's lock until the object
+// goes out of scope.  open() is the whole prologue; set_device() / take() are its steps for the paths that take the context first and begin
+// later (scfq_stage_file never begins; the sharded schemes set the device whether or not their share of the file holds anything).
+struct Session {
+  Ctx* c = nullptr;
+  SessionLock sl;
+  static int set_device(const scfq_opts& o) { return o.n_devices >= 1 && hipSetDevice(o.device_ids[0]) != hipSuccess ? SCFQ_EHIP : SCFQ_OK; }
+  int take() { return get_ctx(&c, sl); }                                     // a context of the CURRENT device
+  int open(bool from_start) { const int rc = take(); return rc ? rc : begin_session(c, from_start); }
+  int open(const scfq_opts& o, bool from_start) { const int rc = set_device(o); return rc ? rc : open(from_start); }
+  int restart(bool from_start) { return begin_session(c, from_start); }      // drops what the session accumulated so far
+  int finish(bool want_hist, scfq_partial* p, uint64_t* hist) { return end_session(c, want_hist, p, hist); }
+  int finish(bool want_hist, scfq_partial* p, std::vector<uint64_t>& hist) { return finish(want_hist, p, want_hist ? hist.data() : nullptr); }
+  // before a host reader takes over from a device path that declined: nothing of it is left in flight
+  void drain() { (void)hipStreamSynchronize(c->compute); (void)hipStreamSynchronize(c->copy); }
 };
 
 int env_int(const char* name, int dflt);
@@ -1181,14 +1203,12 @@ int ingest_bgzf_device(Ctx* c, const uint8_t* img, uint64_t fsize, uint32_t flag
 
 int partial_on_current_device(const void* ptr, uint64_t n, int is_device, int prev_byte, const scfq_opts* opts,
                               scfq_partial* out, uint64_t* hist) {
-  Ctx* c = nullptr;
-  SessionLock sl;
-  int rc = get_ctx(&c, sl);
-  if (rc) return rc;
   const uint32_t flags = opt_flags(opts);
   const bool timing = flags & SCFQ_TIMING;
-  rc = begin_session(c, prev_byte == -1 && !(flags & SCFQ_PREV_IN_MEMORY));   // -1: the range starts the input
+  Session s;
+  int rc = s.open(prev_byte == -1 && !(flags & SCFQ_PREV_IN_MEMORY));   // -1: the range starts the input
   if (rc) return rc;
+  Ctx* c = s.c;
   if (is_device && (rc = wait_for_caller(c, opts))) return rc;
   if (is_device) {
     const int prev = (flags & SCFQ_PREV_IN_MEMORY) ? -2 : prev_byte;
@@ -1200,7 +1220,26 @@ int partial_on_current_device(const void* ptr, uint64_t n, int is_device, int pr
     rc = ingest(c, src, prev, flags, std::min<uint64_t>(opt_chunk(opts), std::max<uint64_t>((n + 4095) & ~4095ull, 4096)), timing);
   }
   if (rc) return rc;
-  return end_session(c, flags & SCFQ_QUAL_HIST, out, hist);
+  return s.finish(flags & SCFQ_QUAL_HIST, out, hist);
+}
+
+// A host input over several devices: one thread per listed device counts that device's byte range [lo, hi) of `total` — share(lo, hi,
+// &partial, hist) runs with the device made current — and the partials fold in list order (fold_device_partials).
+template <typename F>
+int count_on_devices(const scfq_opts& o, int nd, uint64_t total, bool want_hist, scfq_partial* p, std::vector<uint64_t>& hist, F&& share) {
+  std::vector<scfq_partial> parts(nd);
+  std::vector<std::vector<uint64_t>> hists(nd, std::vector<uint64_t>(want_hist ? SCFQ_HIST_WORDS : 0));
+  std::vector<int> rcs(nd, 0);
+  std::vector<std::thread> th;
+  for (int d = 0; d < nd; ++d) {
+    th.emplace_back([&, d] {
+      if (hipSetDevice(o.device_ids[d]) != hipSuccess) { rcs[d] = SCFQ_EHIP; return; }
+      rcs[d] = share(total * (uint64_t)d / nd, total * (uint64_t)(d + 1) / nd, &parts[d], hists[d]);
+    });
+  }
+  for (auto& t : th) t.join();
+  for (int d = 0; d < nd; ++d) if (rcs[d]) return rcs[d];
+  return fold_device_partials(o, nd, parts, hists, want_hist, p, want_hist ? hist.data() : nullptr);
 }
 
 }  // namespace
@@ -1310,25 +1349,12 @@ static int count_buffer_once(const void* ptr, uint64_t n, int is_device, const s
   scfq_partial p;
   if (!is_device && o.n_devices > 1 && n >= (uint64_t)o.n_devices * scfq::kTile) {
     // byte-range shards, one per device, arbitrary (unaligned) cut points; ordered host fold
-    const int nd = o.n_devices;
-    std::vector<scfq_partial> parts(nd);
-    std::vector<std::vector<uint64_t>> hists(nd, std::vector<uint64_t>(want_hist ? SCFQ_HIST_WORDS : 0));
-    std::vector<int> rcs(nd, 0);
-    std::vector<std::thread> th;
     const uint8_t* base = static_cast<const uint8_t*>(ptr);
-    for (int d = 0; d < nd; ++d) {
-      th.emplace_back([&, d] {
-        if (hipSetDevice(o.device_ids[d]) != hipSuccess) { rcs[d] = SCFQ_EHIP; return; }
-        const uint64_t lo = n * (uint64_t)d / nd, hi = n * (uint64_t)(d + 1) / nd;
-        scfq_opts od = o;
-        od.n_devices = 0;
-        rcs[d] = partial_on_current_device(base + lo, hi - lo, 0, lo ? base[lo - 1] : -1, &od, &parts[d],
-                                           want_hist ? hists[d].data() : nullptr);
-      });
-    }
-    for (auto& t : th) t.join();
-    for (int d = 0; d < nd; ++d) if (rcs[d]) return rcs[d];
-    rc = fold_device_partials(o, nd, parts, hists, want_hist, &p, want_hist ? hist.data() : nullptr);
+    scfq_opts od = o;
+    od.n_devices = 0;
+    rc = count_on_devices(o, o.n_devices, n, want_hist, &p, hist, [&](uint64_t lo, uint64_t hi, scfq_partial* part, std::vector<uint64_t>& h) {
+      return partial_on_current_device(base + lo, hi - lo, 0, lo ? base[lo - 1] : -1, &od, part, want_hist ? h.data() : nullptr);
+    });
     if (rc) return rc;
   } else {
     if (!is_device && o.n_devices >= 1) HIPCHK(hipSetDevice(o.device_ids[0]));
@@ -1366,139 +1392,78 @@ static int count_file_partial(const char* path, const scfq_opts* opts, scfq_part
     ~Hand() { *po = *p; if (ho && !h->empty()) std::memcpy(ho, h->data(), SCFQ_HIST_WORDS * sizeof(uint64_t)); }
   } hand{&p, &hist, p_out, hist_out};
   scfq_partial_identity(&p, nullptr);
-  const size_t plen = std::strlen(path);
-  // fastq[^3 .. ^1] == ".gz"      src/fq_count.nim:31 (case-sensitive, last three bytes)
-  const bool is_gz = plen >= 3 && std::memcmp(path + plen - 3, ".gz", 3) == 0;
-  if (is_gz) {
+  if (is_gz_name(path)) {
     {   // BGZF (bgzip) files: block-parallel inflate; every other gzip layout: serial gzread below
-      const int bfd = open(path, O_RDONLY);
-      struct stat bsb;
-      if (bfd >= 0 && fstat(bfd, &bsb) == 0 && S_ISREG(bsb.st_mode) && !std::getenv("SCFQ_NO_BGZF") && scfq_bgzf::probe(bfd)) {
-        if (o.n_devices >= 1 && hipSetDevice(o.device_ids[0]) != hipSuccess) { close(bfd); return SCFQ_EHIP; }
-        void* m = MAP_FAILED;
-        if (bgzf_device_enabled() && bsb.st_size > 0) {
-          m = mmap(nullptr, (size_t)bsb.st_size, PROT_READ, MAP_PRIVATE, bfd, 0);
-          if (m != MAP_FAILED) (void)madvise(m, (size_t)bsb.st_size, MADV_SEQUENTIAL);
-        }
-        Ctx* c = nullptr;
-        SessionLock sl;
-        rc = get_ctx(&c, sl);
-        if (!rc) rc = begin_session(c, true);
+      InputFile in(path);
+      if (is_bgzf_input(in)) {
+        if ((rc = Session::set_device(o))) return rc;
+        if (bgzf_device_enabled() && in.size() > 0) in.map();
+        Session s;
+        rc = s.open(true);
         bool on_device = false;
-        if (!rc && bgzf_device_enabled() && bsb.st_size > 0) {
+        if (!rc && in.mapped()) {
           // pure BGZF (every member <= 64 KiB with its size in the header): compressed bytes over PCIe, inflate on the device
-          if (m != MAP_FAILED) {
-            // (no purity walk up front: touching every member header of a mapped 1 GB file costs 15 ms of page faults;
-            // the chunk planner walks them anyway, under the device's work, and reports what it cannot take)
-            rc = ingest_bgzf_device(c, static_cast<const uint8_t*>(m), (uint64_t)bsb.st_size, o.flags, opt_chunk(&o), timing, -1, bfd, 0,
-                                    [&] { munmap(m, (size_t)bsb.st_size); m = MAP_FAILED; });
-            on_device = (rc != kFallbackToHost && rc != kNotPureBgzf);
-            if (rc == kNotPureBgzf) rc = begin_session(c, true);      // drop what the device path accumulated
-            else if (!on_device) rc = SCFQ_OK;
-          }
+          // (no purity walk up front: touching every member header of a mapped 1 GB file costs 15 ms of page faults;
+          // the chunk planner walks them anyway, under the device's work, and reports what it cannot take)
+          rc = ingest_bgzf_device(s.c, in.img(), in.size(), o.flags, opt_chunk(&o), timing, -1, in.fd, 0, [&] { in.unmap(); });
+          on_device = (rc != kFallbackToHost && rc != kNotPureBgzf);
+          if (rc == kNotPureBgzf) rc = s.restart(true);      // drop what the device path accumulated
+          else if (!on_device) rc = SCFQ_OK;
         }
-        if (m != MAP_FAILED) munmap(m, (size_t)bsb.st_size);
+        in.unmap();
         if (!rc && !on_device) {
-          BgzfSource src(bfd, (uint64_t)bsb.st_size);
-          rc = ingest(c, src, -1, o.flags, opt_chunk(&o), timing);
+          BgzfSource src(in.fd, in.size());
+          rc = ingest(s.c, src, -1, o.flags, opt_chunk(&o), timing);
         }
-        close(bfd);
-        if (rc) return rc;
-        rc = end_session(c, want_hist, &p, want_hist ? hist.data() : nullptr);
-        if (rc) return rc;
-        return SCFQ_OK;
+        in.reset();
+        return rc ? rc : s.finish(want_hist, &p, hist);
       }
-      if (bfd >= 0) close(bfd);
     }
     // ordinary gzip members: inflate on the device (compressed bytes over PCIe); anything the device path cannot prove
     // consistent — and small files, FIFOs — goes to the host readers below, which are gzread byte for byte
     if (gz_device_enabled()) {
-      const int gfd = open(path, O_RDONLY);
-      struct stat gsb;
+      InputFile in(path);
       static const uint64_t min_bytes = (uint64_t)std::max(0, env_int("SCFQ_GZ_DEVICE_MIN_MB", 4)) << 20;
-      if (gfd >= 0 && fstat(gfd, &gsb) == 0 && S_ISREG(gsb.st_mode) && (uint64_t)gsb.st_size >= std::max<uint64_t>(min_bytes, 64)) {
-        void* m = mmap(nullptr, (size_t)gsb.st_size, PROT_READ, MAP_PRIVATE, gfd, 0);
-        if (m != MAP_FAILED) {
-          (void)madvise(m, (size_t)gsb.st_size, MADV_SEQUENTIAL);
-          struct Unmap { void* m; size_t n; int fd; ~Unmap() { munmap(m, n); close(fd); } } um{m, (size_t)gsb.st_size, gfd};
-          if (o.n_devices >= 1 && hipSetDevice(o.device_ids[0]) != hipSuccess) return SCFQ_EHIP;
-          Ctx* c = nullptr;
-          SessionLock sl;
-          rc = get_ctx(&c, sl);
-          if (!rc) rc = begin_session(c, true);
-          if (!rc) rc = ingest_gz_device(c, static_cast<const uint8_t*>(m), (uint64_t)gsb.st_size, o.flags, timing, nullptr, gfd, 0);
-          if (rc == SCFQ_OK) return end_session(c, want_hist, &p, want_hist ? hist.data() : nullptr);
-          if (rc != kFallbackToHost) return rc;
-          (void)hipStreamSynchronize(c->compute);
-          (void)hipStreamSynchronize(c->copy);
-          rc = SCFQ_OK;
-        } else {
-          close(gfd);
-        }
-      } else if (gfd >= 0) {
-        close(gfd);
+      if (in.regular() && in.size() >= std::max<uint64_t>(min_bytes, 64) && in.map()) {
+        Session s;
+        rc = s.open(o, true);
+        if (!rc) rc = ingest_gz_device(s.c, in.img(), in.size(), o.flags, timing, nullptr, in.fd, 0);
+        if (rc == SCFQ_OK) return s.finish(want_hist, &p, hist);
+        if (rc != kFallbackToHost) return rc;
+        s.drain();
       }
     }
     gzFile f = nullptr;
     std::unique_ptr<Source> gsrc = open_gz_source(path, opt_chunk(&o), &f);
     if (!gsrc) return SCFQ_EOPEN;
-    struct GzCloser { gzFile* f; std::unique_ptr<Source>* s; ~GzCloser() { s->reset(); if (*f) gzclose(*f); } } gzc{&f, &gsrc};
-    if (o.n_devices >= 1 && hipSetDevice(o.device_ids[0]) != hipSuccess) return SCFQ_EHIP;
-    Ctx* c = nullptr;
-    SessionLock sl;
-    rc = get_ctx(&c, sl);
-    if (!rc) rc = begin_session(c, true);
-    if (!rc) rc = ingest(c, *gsrc, -1, o.flags, opt_chunk(&o), timing);
-    if (rc) return rc;
-    rc = end_session(c, want_hist, &p, want_hist ? hist.data() : nullptr);
-    if (rc) return rc;
-    return SCFQ_OK;
+    GzCloser gzc{&f, &gsrc};
+    Session s;
+    rc = s.open(o, true);
+    if (!rc) rc = ingest(s.c, *gsrc, -1, o.flags, opt_chunk(&o), timing);
+    return rc ? rc : s.finish(want_hist, &p, hist);
   }
-  int fd = open(path, O_RDONLY);
-  if (fd < 0) return SCFQ_EOPEN;
-  struct stat sb;
-  if (fstat(fd, &sb) != 0 || S_ISDIR(sb.st_mode)) { close(fd); return SCFQ_EOPEN; }
-  const bool regular = S_ISREG(sb.st_mode);
-  const uint64_t size = regular ? (uint64_t)sb.st_size : 0;
+  InputFile in(path);
+  if (!in.statted() || in.directory()) return SCFQ_EOPEN;
+  const uint64_t size = in.size();
   // SCFQ_EXCHANGE_AT_1=1 (rehearsal on a one-GPU box): a one-device list takes the sharded path too, exchange included
   static const bool at1 = env_int("SCFQ_EXCHANGE_AT_1", 0) != 0;
-  const int nd = (regular && o.n_devices > 1 && size >= (uint64_t)o.n_devices * (1u << 20)) ? o.n_devices : 1;
-  if (nd > 1 || (at1 && regular && o.n_devices == 1)) {
-    std::vector<scfq_partial> parts(nd);
-    std::vector<std::vector<uint64_t>> hists(nd, std::vector<uint64_t>(want_hist ? SCFQ_HIST_WORDS : 0));
-    std::vector<int> rcs(nd, 0);
-    std::vector<std::thread> th;
-    for (int d = 0; d < nd; ++d) {
-      th.emplace_back([&, d] {
-        if (hipSetDevice(o.device_ids[d]) != hipSuccess) { rcs[d] = SCFQ_EHIP; return; }
-        const uint64_t lo = size * (uint64_t)d / nd, hi = size * (uint64_t)(d + 1) / nd;
-        int prev = -1;
-        if (lo) { uint8_t pb; if (pread(fd, &pb, 1, (off_t)(lo - 1)) != 1) { rcs[d] = SCFQ_EIO; return; } prev = pb; }
-        Ctx* c = nullptr;
-        SessionLock sl;
-        int r = get_ctx(&c, sl);
-        if (!r) r = begin_session(c, lo == 0);
-        if (!r) { FdSource src(fd, lo, hi); r = ingest(c, src, prev, o.flags, opt_chunk(&o), timing); }
-        if (!r) r = end_session(c, want_hist, &parts[d], want_hist ? hists[d].data() : nullptr);
-        rcs[d] = r;
-      });
-    }
-    for (auto& t : th) t.join();
-    close(fd);
-    for (int d = 0; d < nd; ++d) if (rcs[d]) return rcs[d];
-    rc = fold_device_partials(o, nd, parts, hists, want_hist, &p, want_hist ? hist.data() : nullptr);
-    if (rc) return rc;
-    return SCFQ_OK;
+  const int nd = (in.regular() && o.n_devices > 1 && size >= (uint64_t)o.n_devices * (1u << 20)) ? o.n_devices : 1;
+  if (nd > 1 || (at1 && in.regular() && o.n_devices == 1)) {
+    return count_on_devices(o, nd, size, want_hist, &p, hist, [&](uint64_t lo, uint64_t hi, scfq_partial* part, std::vector<uint64_t>& h) {
+      int prev = -1;
+      if (lo) { uint8_t pb; if (pread(in.fd, &pb, 1, (off_t)(lo - 1)) != 1) return (int)SCFQ_EIO; prev = pb; }
+      Session s;
+      int r = s.open(lo == 0);
+      if (!r) { FdSource src(in.fd, lo, hi); r = ingest(s.c, src, prev, o.flags, opt_chunk(&o), timing); }
+      return r ? r : s.finish(want_hist, part, h);
+    });
   }
-  if (o.n_devices >= 1 && hipSetDevice(o.device_ids[0]) != hipSuccess) { close(fd); return SCFQ_EHIP; }
-  Ctx* c = nullptr;
-  SessionLock sl;
-  rc = get_ctx(&c, sl);
-  if (!rc) rc = begin_session(c, true);
+  Session s;
+  rc = s.open(o, true);
   if (!rc) {
-    if (regular) {
-      FdSource src(fd, 0, size);
-      rc = ingest(c, src, -1, o.flags, std::min<uint64_t>(opt_chunk(&o), std::max<uint64_t>((size + 4095) & ~4095ull, 4096)), timing);
+    if (in.regular()) {
+      FdSource src(in.fd, 0, size);
+      rc = ingest(s.c, src, -1, o.flags, std::min<uint64_t>(opt_chunk(&o), std::max<uint64_t>((size + 4095) & ~4095ull, 4096)), timing);
     } else {
       // FIFO / character device: sequential read()
       struct SeqSource : Source {
@@ -1514,563 +1479,30 @@ static int count_file_partial(const char* path, const scfq_opts* opts, scfq_part
           }
           return (int64_t)got;
         }
-      } src(fd);
-      rc = ingest(c, src, -1, o.flags, opt_chunk(&o), timing);
+      } src(in.fd);
+      rc = ingest(s.c, src, -1, o.flags, opt_chunk(&o), timing);
     }
   }
-  close(fd);
-  if (rc) return rc;
-  rc = end_session(c, want_hist, &p, want_hist ? hist.data() : nullptr);
-  if (rc) return rc;
-  return SCFQ_OK;
+  in.reset();
+  return rc ? rc : s.finish(want_hist, &p, hist);
 }
 
 }  // extern "C"
-namespace {
-// BGZF shards.  A BGZF file is cut where its members are: the first position at or after `from` where eight members follow one
-// another (or a shorter run that ends exactly with the file) — every rank finds the SAME positions with this rule, from the bytes
-// alone.  n when there is none.
-uint64_t bgzf_boundary(const uint8_t* img, uint64_t n, uint64_t from) {
-  for (uint64_t p = from; p + 18 <= n;) {
-    const void* hit = std::memchr(img + p, 0x1f, (size_t)(n - 17 - p));
-    if (!hit) break;
-    p = (uint64_t)(static_cast<const uint8_t*>(hit) - img);
-    uint64_t q = p;
-    int k = 0;
-    while (k < 8 && q < n) {
-      uint32_t hl = 0;
-      const uint32_t bs = scfq_bgzf::block_size(img + q, n - q, &hl);
-      if (!bs || q + bs > n || scfq_bgzf::rd32(img + q + bs - 4) > (1u << 16)) break;
-      q += bs;
-      ++k;
-    }
-    if (k == 8 || (k > 0 && q == n)) return p;
-    ++p;
-  }
-  return n;
-}
-// Where rank r's members start (r > 0) and the byte in front of its first inflated byte: the boundary rule gives a member; the rank's
-// range starts BEHIND the first non-empty member from there, which the rank inflates on the host (one member of at most 64 KiB)
-// for its last byte.  Both neighbours compute the same cut.  false: a member that does not inflate (the file is damaged).
-bool bgzf_cut(const uint8_t* img, uint64_t n, uint64_t from, uint64_t* cut, int* prev) {
-  uint64_t p = bgzf_boundary(img, n, from);
-  *prev = -1;
-  while (p < n) {
-    uint32_t hl = 0;
-    const uint32_t bs = scfq_bgzf::block_size(img + p, n - p, &hl);
-    if (!bs || p + bs > n) { *cut = n; return false; }
-    const uint32_t isize = scfq_bgzf::rd32(img + p + bs - 4);
-    if (isize == 0) { p += bs; continue; }               // (an empty member — the end-of-file marker — has no last byte)
-    if (isize > (1u << 16)) { *cut = n; return false; }
-    std::vector<scfq_bgzf::Block> one{{p, bs, hl, isize, scfq_bgzf::rd32(img + p + bs - 8), 0}};
-    std::vector<uint8_t> out(isize);
-    if (scfq_bgzf::inflate_blocks(img, one, 0, 1, out.data())) { *cut = n; return false; }
-    *prev = out[isize - 1];
-    *cut = p + bs;
-    return true;
-  }
-  *cut = n;
-  return true;
-}
-// ---- ordinary gzip shards: a file of SEVERAL members is cut where members start ------------------------------------------------
-// (`cat a.fq.gz b.fq.gz`, `pigz -i`, per-lane or per-tile members of a sequencer's writer.)  Unlike BGZF a member does not say how long
-// it is, so a rank that starts in the middle of the file can only LOOK for a member start: the three magic bytes with no reserved flag
-// bit set, a header that parses, and deflate data that inflates cleanly for its first 64 KiB — a block header made of chance bits
-// survives the Huffman-code tests about once in 4000 tries and then dies within a few hundred symbols.  That makes a false start
-// unlikely, not impossible; what PROVES a cut is the rank before it: its members must end — trailer, CRC-32 and ISIZE checked —
-// exactly where the next rank began (gz_shard_fold below), or every rank falls back to rank 0 reading the whole file.
-//
-// gz_member_here: true when a member demonstrably starts at p.  *first_byte: the first byte it (or, when it is empty, a member
-// behind it, inside [p, stop)) inflates to; -1 when there is none in that stretch.
-bool gz_member_here(const uint8_t* img, uint64_t n, uint64_t p, uint64_t stop, int* first_byte) {
-  *first_byte = -1;
-  std::vector<uint8_t> buf;
-  bool first = true;
-  while (p < n && (first || p < stop)) {
-    if (n - p < 18 || img[p] != 0x1f || img[p + 1] != 0x8b || img[p + 2] != 8 || (img[p + 3] & 0xE0)) return !first;
-    const long h = scfq_gzfast::member_header(img + p, (size_t)(n - p));
-    if (h <= 0) return !first;
-    const uint64_t sample = std::min<uint64_t>(n - (p + (uint64_t)h), 64u << 10);
-    if (buf.empty()) buf.resize(scfq_gzfast::kWindow + (2u << 20));
-    auto dec = std::unique_ptr<scfq_inflate::Decoder>(new scfq_inflate::Decoder());
-    dec->begin(img + p + h, img + p + h + sample);
-    uint8_t* o = buf.data() + scfq_gzfast::kWindow;
-    const int r = dec->run(o, buf.data() + buf.size());
-    const uint64_t got = (uint64_t)(o - (buf.data() + scfq_gzfast::kWindow));
-    if (r == scfq_inflate::kErrData) return !first;
-    if (r == scfq_inflate::kErrTruncated && sample == n - (p + (uint64_t)h)) return !first;      // (the FILE ends inside the member: damaged)
-    if (got) { *first_byte = buf[scfq_gzfast::kWindow]; return true; }
-    if (r != scfq_inflate::kStreamEnd) return true;            // (no byte yet and no end either: a long run of empty stored blocks; rare, harmless)
-    // an empty member: the first byte is a later member's
-    const uint8_t* t = dec->end_of_stream();
-    first = false;
-    p = (uint64_t)(t - img) + 8;
-  }
-  return true;
-}
-// the first demonstrable member start at or after `from`; n when there is none.  *first_byte as above (stop: the end of the rank's stretch)
-// (limit: only starts in front of this offset are looked for — a rank that only wants to know what its own share of the file holds does
-// not walk a 25 GB member to its end)
-uint64_t gz_member_boundary(const uint8_t* img, uint64_t n, uint64_t from, uint64_t stop, int* first_byte, uint64_t limit = ~0ull) {
-  *first_byte = -1;
-  const uint64_t last = std::min<uint64_t>(limit, n >= 17 ? n - 17 : 0);       // first offset that is no candidate any more
-  for (uint64_t p = from; p < last;) {
-    const void* hit = std::memchr(img + p, 0x1f, (size_t)(last - p));
-    if (!hit) break;
-    p = (uint64_t)(static_cast<const uint8_t*>(hit) - img);
-    if (img[p + 1] == 0x8b && img[p + 2] == 8 && !(img[p + 3] & 0xE0) && gz_member_here(img, n, p, std::max(stop, p + 1), first_byte)) return p;
-    ++p;
-  }
-  return n;
-}
-
-// A shard that was scanned as if it began the input (no byte before it is known when its scan starts: that byte is the LAST one the
-// member before inflates to), put right once that byte is known.  Two things depend on it: a '\n' at the shard's first position ends
-// a line whose '\r' — if the byte before is one — is not part of that line (len, and the quality histogram's '\r' bin, are taken back
-// exactly as a range of the device path takes back a '\r' that lies in the range before it: u64 modular); and the shard's first byte
-// starts a line only when the byte before is a '\n' (K4's line starts, and what they begin with).
-void gz_shard_fix(scfq_partial* p, uint64_t* hist, int true_prev, int first_byte, uint32_t flags) {
-  if (p->bytes == 0 || true_prev < 0 || first_byte < 0) return;
-  if (first_byte == '\n' && true_prev == '\r') {
-    p->len[0] -= 1;
-    if (hist && (p->hist_class == 0 || p->hist_class == 1)) hist[0 * 256 + 13] -= 1;
-  }
-  if ((flags & SCFQ_STRUCT_CHECK) && true_prev != '\n') {
-    p->starts[0] -= 1;
-    if (first_byte == '@') p->first_at[0] -= 1;
-    if (first_byte == '+') p->first_plus[0] -= 1;
-  }
-}
-// ---- ONE member over several ranks: the deflate stream is cut where BLOCKS start -----------------------------------------------------
-// gz_block_boundary: the first bit at or after byte `from` where a dynamic-Huffman block demonstrably starts (scfq_pgz.hpp's test: a
-// header that parses — complete code-length, literal/length and distance codes — and 4096 symbols that decode cleanly); 0 when there is
-// none within `span` bytes.  Both neighbours of a cut compute it from the same bytes.  What proves it is the rank before: its chain must
-// arrive at exactly this bit (GzStretch: stop_bit), or every rank falls back to rank 0 reading the whole file.
-uint64_t gz_block_boundary(const uint8_t* img, uint64_t n, uint64_t from, uint64_t span) {
-  const uint64_t to = std::min<uint64_t>(from + span, n > 16 ? n - 16 : 0);
-  if (from >= to) return 0;
-  auto d = std::unique_ptr<scfq_inflate::Decoder>(new scfq_inflate::Decoder());
-  std::vector<uint16_t> scratch(scfq_pgz::kWindow + scfq_pgz::kTrialSymbols + 2 * scfq_inflate::kOutSlack);
-  for (uint32_t i = 0; i < scfq_pgz::kWindow; ++i) scratch[i] = (uint16_t)(0x8000u | i);
-  for (uint64_t b = from * 8; b < to * 8; ++b)
-    if (scfq_pgz::plausible_block(*d, img, img + n, b, scratch)) return b;
-  return 0;
-}
-}  // namespace
+#include "scfq_sharded.hpp"      // scfq_count_file_sharded: one file counted by all ranks of a communicator, in named stages
 extern "C" {
-
-// fq_count of one file by all ranks of a communicator (include/sc_fqcount.h): byte-range shard -> K1/K2 -> exchange -> fold
-int scfq_count_file_sharded(const char* path, const scfq_opts* opts, scfq_comm* comm, scfq_counts* out) {
-  if (!path || !comm || !out || out->struct_size != sizeof(scfq_counts)) return SCFQ_EARG;
-  int rc = check_opts(opts);
-  if (rc) return rc;
-  scfq_opts o = opts_copy(opts);
-  o.flags &= ~SCFQ_PREV_IN_MEMORY;
-  const bool want_hist = o.flags & SCFQ_QUAL_HIST;
-  const bool timing = o.flags & SCFQ_TIMING;
-  const int world = scfq_comm_world(comm), rank = scfq_comm_rank(comm);
-  std::vector<uint64_t> hist(want_hist ? SCFQ_HIST_WORDS : 0), hist_all(want_hist ? SCFQ_HIST_WORDS : 0);
-  scfq_partial mine, all;
-  scfq_partial_identity(&mine, want_hist ? hist.data() : nullptr);
-  const size_t plen = std::strlen(path);
-  const bool is_gz = plen >= 3 && std::memcmp(path + plen - 3, ".gz", 3) == 0;      // src/fq_count.nim:31
-  int local = SCFQ_OK;          // a rank that fails still takes part in the exchange (with the identity) so nobody hangs
-  if (is_gz) {
-    // BGZF (bgzip) input shards where its members are: rank r takes the members that start in its byte range, inflates them on its
-    // device and scans them; the partials fold as for a plain file.  The ranks first AGREE (one all-gather of a word) that every one
-    // of them found its cuts and saw nothing but BGZF members of at most 64 KiB in its range — otherwise, and for every other gzip
-    // layout (one deflate stream has no shards), rank 0 inflates and scans all of it and the others contribute the identity.
-    static const bool shard_bgzf = env_int("SCFQ_SHARD_BGZF", 1) != 0;
-    const int fd = shard_bgzf && world > 1 ? open(path, O_RDONLY) : -1;
-    struct stat sb;
-    const uint8_t* img = nullptr;
-    uint64_t size = 0, b_lo = 0, b_hi = 0;
-    int prev = -1;
-    uint64_t mine_ok = 0;
-    if (fd >= 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size > 0 && bgzf_device_enabled() && !std::getenv("SCFQ_NO_BGZF") && scfq_bgzf::probe(fd)) {
-      void* m = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-      if (m != MAP_FAILED) {
-        img = static_cast<const uint8_t*>(m);
-        size = (uint64_t)sb.st_size;
-        bool ok = true;
-        int prev_hi = -1;
-        if (rank > 0) ok = bgzf_cut(img, size, size / (uint64_t)world * (uint64_t)rank, &b_lo, &prev);
-        if (rank + 1 < world) ok = bgzf_cut(img, size, size / (uint64_t)world * (uint64_t)(rank + 1), &b_hi, &prev_hi) && ok;
-        else b_hi = size;
-        if (b_hi < b_lo) b_hi = b_lo;
-        ok = ok && (b_lo == b_hi || bgzf_is_pure(img + b_lo, b_hi - b_lo));
-        mine_ok = ok ? 1 : 0;
-      }
-    }
-    // An ordinary gzip file (bit 1 of the word the ranks exchange): rank r's members are those that start in [g_lo, g_hi), where a cut is
-    // the first demonstrable member start at or after size * r / world (gz_member_boundary; both neighbours find the same one from the
-    // bytes alone).  A file of ONE member gives every cut but rank 0's as "none": rank 0 has all of it, as before.
-    static const bool shard_gz = env_int("SCFQ_SHARD_GZ", 1) != 0;
-    uint64_t g_lo = 0, g_hi = 0;
-    int g_first = -1;
-    if (!mine_ok && !img && fd >= 0 && shard_gz && gz_device_enabled() && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size >= 64) {
-      void* m = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-      if (m != MAP_FAILED) {
-        img = static_cast<const uint8_t*>(m);
-        size = (uint64_t)sb.st_size;
-        const uint64_t nom_lo = size / (uint64_t)world * (uint64_t)rank, nom_hi = rank + 1 < world ? size / (uint64_t)world * (uint64_t)(rank + 1) : size;
-        // (bit 1: an ordinary gzip file as far as this rank can tell without walking it — the cuts themselves are looked for once the ranks
-        // have agreed on a scheme; a rank that then finds none says so in the gathered rows)
-        int fb = -1;
-        if (rank != 0 || gz_member_here(img, size, 0, 1, &fb)) mine_ok = 2;
-        // (bit 2: at most ONE member starts inside this rank's share of the file — rank 0: none behind the file's first.  When every rank
-        // says so the members are big ones — one, or a few: `cat lane1.gz lane2.gz` — and the ranks cut the deflate streams where BLOCKS
-        // start, a member start being a cut of its own: no rank is left without work, as the member scheme leaves the ranks in whose share
-        // no member starts.  The search stays inside the rank's share.)
-        static const bool shard_blocks = env_int("SCFQ_SHARD_GZ_BLOCKS", 1) != 0;
-        if (mine_ok == 2 && shard_blocks && size >= (uint64_t)world * (8ull << 20)) {
-          const uint64_t m1 = gz_member_boundary(img, size, rank == 0 ? 1 : nom_lo, size, &fb, nom_hi);
-          const uint64_t m2 = m1 < nom_hi ? gz_member_boundary(img, size, m1 + 1, size, &fb, nom_hi) : size;
-          if (rank == 0 ? m1 >= nom_hi : m2 >= nom_hi) mine_ok = 6;
-        }
-      }
-    }
-    std::vector<uint64_t> oks((size_t)world, 0);
-    bool sharded = false, sharded_gz = false, sharded_blk = false;
-    if (world > 1 && shard_bgzf) {
-      // (every rank takes part in this all-gather whatever it found: a rank that cannot even open the file says 0)
-      rc = scfq_comm_allgather_u64(comm, &mine_ok, 1, oks.data(), 0);
-      if (rc) { if (img) munmap(const_cast<uint8_t*>(img), (size_t)size); if (fd >= 0) close(fd); std::snprintf(g_err, sizeof g_err, "%s", scfq_comm_error_detail()); return rc; }
-      sharded = sharded_gz = sharded_blk = true;
-      for (int r = 0; r < world; ++r) {
-        sharded = sharded && oks[(size_t)r] == 1;
-        sharded_gz = sharded_gz && (oks[(size_t)r] & 2) != 0;
-        sharded_blk = sharded_blk && oks[(size_t)r] == 6;
-      }
-    }
-    if (sharded_gz && !sharded_blk) {
-      // (the member scheme's cuts: the first demonstrable member start at or after size * r / world and the one after the next rank's)
-      int f_hi = -1;
-      const uint64_t nom_lo = size / (uint64_t)world * (uint64_t)rank, nom_hi = size / (uint64_t)world * (uint64_t)(rank + 1);
-      g_hi = rank + 1 < world ? gz_member_boundary(img, size, nom_hi, nom_hi, &f_hi) : size;
-      if (rank == 0) g_lo = 0, (void)gz_member_here(img, size, 0, std::max<uint64_t>(g_hi, 1), &g_first);
-      else g_lo = gz_member_boundary(img, size, nom_lo, g_hi, &g_first);
-      if (g_hi < g_lo) g_hi = g_lo;
-    }
-    if (sharded_gz) {
-      // every rank inflates and scans the members of its stretch as if they were a file of their own (device path; the host's decoder
-      // when that declines), scanned as if they began the input; the partials — with each stretch's first byte and whether its members
-      // ended exactly where the next rank's begin — are gathered and folded here, in rank order, with the byte before each stretch
-      // (the last byte of the stretch before it) put right first: gz_shard_fix.
-      if (o.n_devices >= 1 && hipSetDevice(o.device_ids[0]) != hipSuccess) local = SCFQ_EHIP;
-      uint64_t end_off = 0;
-      uint64_t blk_crc_raw = 0, blk_len = 0;      // block scheme: this stretch's raw CRC-32 and length
-      struct BlkGroup { uint64_t first, last, end_byte; };
-      std::vector<BlkGroup> blk_groups;          // ... and the members: the ranks that hold one, the offset just behind its trailer
-      if (sharded_blk) {
-        // ---- big members: rank r's stretch is [cut_r, cut_{r+1}) — a cut is the member start inside the rank's share of the file when there
-        // is one, else the first block start at or behind the share's first byte; a stretch never crosses a member's end ----
-        struct Cut { bool found = false, member = false; uint64_t byte = 0, bit = 0; };
-        auto cut_of = [&](int r) -> Cut {
-          Cut ct;
-          if (r <= 0) { ct.found = true; ct.member = true; return ct; }
-          if (r >= world) { ct.found = true; ct.member = true; ct.byte = size; ct.bit = size * 8; return ct; }
-          const uint64_t lo = size / (uint64_t)world * (uint64_t)r, hi = r + 1 < world ? size / (uint64_t)world * (uint64_t)(r + 1) : size;
-          int fb = -1;
-          const uint64_t m = gz_member_boundary(img, size, lo, size, &fb, hi);
-          if (m < hi) { ct.found = true; ct.member = true; ct.byte = m; ct.bit = m * 8; return ct; }
-          const uint64_t bb = gz_block_boundary(img, size, lo, std::min<uint64_t>(16ull << 20, hi - lo));
-          if (bb && (bb >> 3) < hi) { ct.found = true; ct.bit = bb; ct.byte = bb >> 3; }
-          return ct;
-        };
-        const Cut c_lo = cut_of(rank), c_hi = cut_of(rank + 1);
-        const long h0 = scfq_gzfast::member_header(img, (size_t)size);
-        // the stretch as the pipeline sees it: an image that begins at the member's start (a member cut) or at the file's (a block cut:
-        // bit positions are the file's), and ends where the next member starts (a member cut) or with the file
-        const uint64_t base = c_lo.member ? c_lo.byte : 0;
-        const uint64_t image_end = c_hi.member ? c_hi.byte : size;
-        GzStretch sx;
-        sx.start_bit = c_lo.member ? 0 : c_lo.bit;
-        sx.stop_bit = c_hi.member ? 0 : c_hi.bit - 8 * base;
-        const bool cuts_ok = h0 > 0 && c_lo.found && c_hi.found && image_end > base + 64 && (c_hi.member || c_hi.bit > (c_lo.member ? c_lo.byte * 8 : c_lo.bit));
-        // What every rank learns of every stretch — [proven, cut kinds and positions, bytes, where its member ended, the map] — and what it
-        // makes of it: the window in front of its own stretch = the maps of the stretches before it IN THE SAME MEMBER, applied in order to
-        // the member's (empty) start.
-        const uint32_t kMapWords = (uint32_t)(scfq_gzfast::kWindow / 4), kHead = 8, w1 = kHead + kMapWords;
-        std::vector<uint8_t> window(scfq_gzfast::kWindow, 0);
-        bool exchanged = false, agree = false;
-        int comm_rc = SCFQ_OK;
-        auto exchange_fn = [&](GzStretch& x, bool proven) -> int {
-          exchanged = true;
-          std::vector<uint64_t> row1(w1, 0), rows1((size_t)world * w1, 0);
-          // (a stretch that ends at a member cut must have ended WITH its member, exactly at the cut: nothing but members in between)
-          proven = proven && cuts_ok && !local && x.map.size() == scfq_gzfast::kWindow && x.member_ended == c_hi.member &&
-                   (!c_hi.member || c_hi.byte == size || base + x.end_byte == c_hi.byte);
-          row1[0] = proven ? 1 : 0;
-          row1[1] = c_lo.member; row1[2] = c_lo.bit; row1[3] = c_hi.member; row1[4] = c_hi.bit;
-          row1[5] = x.out_bytes; row1[6] = base + x.end_byte;
-          if (proven) std::memcpy(row1.data() + kHead, x.map.data(), 2 * scfq_gzfast::kWindow);
-          comm_rc = scfq_comm_allgather_u64(comm, row1.data(), w1, rows1.data(), 0);
-          if (comm_rc) return 1;
-          agree = true;
-          for (int r = 0; r < world; ++r) {
-            const uint64_t* rr = rows1.data() + (size_t)r * w1;
-            const uint64_t* nx = r + 1 < world ? rows1.data() + (size_t)(r + 1) * w1 : nullptr;
-            agree = agree && rr[0] == 1 && (nx ? (rr[3] == nx[1] && rr[4] == nx[2]) : (rr[3] == 1 && rr[4] == size * 8));      // a stretch ends where the next begins
-          }
-          if (!agree) return 1;
-          // the members' ends, for the CRC check at the fold: [first rank, last rank, offset just behind the trailer]
-          blk_groups.clear();
-          for (int r = 0, a0 = 0; r < world; ++r) {
-            const uint64_t* rr = rows1.data() + (size_t)r * w1;
-            if (rr[3] == 1) { blk_groups.push_back({(uint64_t)a0, (uint64_t)r, rr[6]}); a0 = r + 1; }
-          }
-          int first_of_member = rank;
-          while (first_of_member > 0 && rows1[(size_t)first_of_member * w1 + 1] == 0) --first_of_member;
-          std::vector<uint8_t> next(scfq_gzfast::kWindow, 0);
-          uint64_t before_bytes = 0;
-          for (int r = first_of_member; r < rank; ++r) {
-            const uint16_t* m = reinterpret_cast<const uint16_t*>(rows1.data() + (size_t)r * w1 + kHead);
-            for (uint32_t i = 0; i < scfq_gzfast::kWindow; ++i) next[i] = (m[i] & 0x8000u) ? window[m[i] & 0x7FFFu] : (uint8_t)m[i];
-            window.swap(next);
-            before_bytes += rows1[(size_t)r * w1 + 5];
-          }
-          x.window = window.data();
-          x.valid = (uint32_t)std::min<uint64_t>(scfq_gzfast::kWindow, before_bytes);
-          return 0;
-        };
-        Ctx* c = nullptr;
-        SessionLock sl;
-        if (!local) local = get_ctx(&c, sl);
-        // ONE pass (the default): the stretch's proven symbols are kept — two bytes per inflated byte — while its map goes out and the window
-        // comes back (GzStretch::exchange), then they become bytes.  SCFQ_SHARD_GZ_KEEP=0: two passes, the second decoding again (what a
-        // device short of memory would want: nothing is kept between them).
-        static const bool keep_env = env_int("SCFQ_SHARD_GZ_KEEP", 1) != 0;
-        bool keep_on = keep_env;
-        if (keep_on && !local) {
-          // (the store of kept symbols: two bytes per inflated byte — taken as 12 per compressed byte of the stretch, FASTQ compresses 3 - 5
-          // times — must leave the pipeline its own 12 GB or so: a rank whose device is short of that goes over its stretch twice instead;
-          // the ranks need not agree on this, the exchange in the middle is the same)
-          size_t free_b = 0, total_b = 0;
-          const uint64_t lo_b = c_lo.byte, hi_b = c_hi.byte;
-          if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
-          // (SCFQ_TEST_DEVICE_FREE_GB: the tests' way of putting a rank on a device that is short of memory)
-          static const int test_free_gb = env_int("SCFQ_TEST_DEVICE_FREE_GB", -1);
-          if (test_free_gb >= 0) free_b = std::min<size_t>(free_b, (size_t)test_free_gb << 30);
-          if ((hi_b > lo_b ? hi_b - lo_b : 0) * 12 + (16ull << 30) > (uint64_t)free_b) keep_on = false;
-        }
-        uint64_t out1 = 0;
-        if (keep_on) {
-          if (!local && cuts_ok) local = begin_session(c, rank == 0);
-          if (!local && cuts_ok) {
-            sx.exchange = exchange_fn;
-            const int r1 = ingest_gz_device(c, img + base, image_end - base, o.flags, timing, nullptr, fd, base, &sx);
-            if (r1 == kFallbackToHost) { if (agree) local = SCFQ_EGZ; } else if (r1) local = r1;
-          }
-          if (!exchanged) (void)exchange_fn(sx, false);
-          out1 = sx.out_bytes;
-        } else {
-          GzStretch sx1 = sx;
-          sx1.map_only = true;
-          bool proven = false;
-          if (!local && cuts_ok) {
-            const int r1 = ingest_gz_device(c, img + base, image_end - base, o.flags, false, nullptr, fd, base, &sx1);
-            if (r1 == SCFQ_OK) proven = true; else if (r1 != kFallbackToHost) local = r1;
-          }
-          (void)exchange_fn(sx1, proven);
-          out1 = sx1.out_bytes;
-          if (agree) {
-            sx.window = sx1.window;
-            sx.valid = sx1.valid;
-            if (!local) local = begin_session(c, rank == 0);
-            if (!local) {
-              const int r2 = ingest_gz_device(c, img + base, image_end - base, o.flags, timing, nullptr, fd, base, &sx);
-              local = r2 == kFallbackToHost ? SCFQ_EGZ : r2;
-            }
-          }
-        }
-        if (comm_rc) { if (img) munmap(const_cast<uint8_t*>(img), (size_t)size); if (fd >= 0) close(fd); std::snprintf(g_err, sizeof g_err, "%s", scfq_comm_error_detail()); return local ? local : comm_rc; }
-        if (agree) {
-          if (!local && sx.out_bytes != out1) local = SCFQ_EGZ;
-          if (!local) local = end_session(c, want_hist, &mine, want_hist ? hist.data() : nullptr);
-          g_first = sx.first_byte;
-          blk_crc_raw = sx.crc_raw;
-          blk_len = sx.out_bytes;
-        } else {
-          local = SCFQ_EGZ;      // (not an error of this rank: the rows below send every rank to the fall-back)
-          std::snprintf(g_err, sizeof g_err, "the block cuts of a one-member file did not join up");
-        }
-      } else if (!local && g_hi > g_lo) {
-        Ctx* c = nullptr;
-        SessionLock sl;
-        local = get_ctx(&c, sl);
-        if (!local) local = begin_session(c, rank == 0);
-        if (!local) {
-          const uint64_t len = g_hi - g_lo;
-          static const uint64_t min_bytes = (uint64_t)std::max(0, env_int("SCFQ_GZ_DEVICE_MIN_MB", 4)) << 20;
-          local = len >= std::max<uint64_t>(min_bytes, 64) ? ingest_gz_device(c, img + g_lo, len, o.flags, timing, &end_off, fd, g_lo) : kFallbackToHost;
-          if (local == kFallbackToHost) {
-            // (small stretches, and whatever the device path declines: the host's decoder over the same bytes — Resume from the first
-            // block of the stretch's first member, an empty window, no prefix)
-            (void)hipStreamSynchronize(c->compute);
-            (void)hipStreamSynchronize(c->copy);
-            local = begin_session(c, rank == 0);
-            const long h = scfq_gzfast::member_header(img + g_lo, (size_t)len);
-            if (!local && h <= 0) local = SCFQ_EGZ;
-            if (!local) {
-              struct RangeSource : Source {
-                scfq_gzfast::Resume rs;
-                int64_t fill(uint8_t* dst, uint64_t cap) override { const int64_t r = rs.next_chunk(dst, cap); return r < 0 ? (int64_t)SCFQ_EGZ : r; }
-              } src;
-              const std::vector<uint8_t> no_window(scfq_gzfast::kWindow, 0);
-              src.rs.open(img + g_lo, (size_t)len, (uint64_t)h * 8, no_window.data(), 0, 0, 0);
-              local = ingest(c, src, -1, o.flags, opt_chunk(&o), timing);
-              end_off = src.rs.end_offset();
-            }
-          }
-          // the stretch must be members and nothing else, up to the very byte the next stretch starts at (only the file's last stretch may
-          // have the trailing bytes gzread ignores behind it)
-          if (!local && end_off != len && g_hi < size) { local = SCFQ_EGZ; std::snprintf(g_err, sizeof g_err, "shard %d: its members end at byte %llu, the next shard begins at %llu", rank, (unsigned long long)(g_lo + end_off), (unsigned long long)g_hi); }
-        }
-        if (!local) local = end_session(c, want_hist, &mine, want_hist ? hist.data() : nullptr);
-      }
-      if (img) munmap(const_cast<uint8_t*>(img), (size_t)size);
-      if (fd >= 0) close(fd);
-      if (local) scfq_partial_identity(&mine, want_hist ? hist.data() : nullptr);
-      mine.reserved[0] = (uint64_t)(int64_t)local;
-      mine.reserved[1] = (uint64_t)(g_first + 1);          // 0: this stretch holds no byte
-      mine.reserved[2] = blk_crc_raw;                      // (block scheme) raw CRC-32 and length of this stretch of the one member
-      mine.reserved[3] = blk_len;
-      const uint32_t words = SCFQ_PARTIAL_WORDS + (want_hist ? SCFQ_HIST_WORDS : 0);
-      std::vector<uint64_t> row(words), rows((size_t)world * words);
-      std::memcpy(row.data(), &mine, sizeof mine);
-      if (want_hist) std::memcpy(row.data() + SCFQ_PARTIAL_WORDS, hist.data(), SCFQ_HIST_WORDS * sizeof(uint64_t));
-      rc = scfq_comm_allgather_u64(comm, row.data(), words, rows.data(), 0);
-      if (rc) { std::snprintf(g_err, sizeof g_err, "%s", scfq_comm_error_detail()); return local ? local : rc; }
-      bool all_ok = true;
-      for (int r = 0; r < world; ++r) all_ok = all_ok && rows[(size_t)r * words + offsetof(scfq_partial, reserved) / 8] == 0;
-      if (all_ok && sharded_blk) {
-        // every member's CRC-32 and ISIZE against the join of its stretches' (x^(8 |part|), as between the batches of one stretch)
-        const int tfd = open(path, O_RDONLY);
-        for (const BlkGroup& gpm : blk_groups) {
-          uint32_t raw = 0;
-          uint64_t len = 0;
-          for (uint64_t r = gpm.first; r <= gpm.last; ++r) {
-            const uint64_t* rr = rows.data() + (size_t)r * words + offsetof(scfq_partial, reserved) / 8;
-            raw = gz_mulmod(gz_xpow8n(rr[3]), raw) ^ (uint32_t)rr[2];
-            len += rr[3];
-          }
-          const uint32_t crc = raw ^ gz_mulmod(gz_xpow8n(len), 0xFFFFFFFFu) ^ 0xFFFFFFFFu;
-          uint8_t t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-          const bool have_trailer = tfd >= 0 && gpm.end_byte >= 8 && pread(tfd, t, 8, (off_t)(gpm.end_byte - 8)) == 8;
-          const uint32_t t_crc = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
-          const uint32_t t_len = (uint32_t)t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
-          if (!have_trailer || t_crc != crc || t_len != (uint32_t)(len & 0xFFFFFFFFull)) all_ok = false;      // damaged: gzread's verdict, from rank 0's readers
-        }
-        if (tfd >= 0) close(tfd);
-        if (blk_groups.empty()) all_ok = false;
-      }
-      if (all_ok) {
-        scfq_partial_identity(&all, want_hist ? hist_all.data() : nullptr);
-        int before = -1;      // the last byte in front of the stretch being added (-1: nothing yet)
-        for (int r = 0; r < world; ++r) {
-          scfq_partial pr;
-          std::memcpy(&pr, rows.data() + (size_t)r * words, sizeof pr);
-          uint64_t* hr = want_hist ? rows.data() + (size_t)r * words + SCFQ_PARTIAL_WORDS : nullptr;
-          gz_shard_fix(&pr, hr, before, (int)pr.reserved[1] - 1, o.flags);
-          pr.reserved[1] = pr.reserved[2] = pr.reserved[3] = 0;
-          if ((rc = scfq_partial_combine(&all, &pr, want_hist ? hist_all.data() : nullptr, hr))) return rc;
-          if (pr.bytes) before = (int)(pr.last_byte & 0xFF);
-        }
-        return scfq_partial_finalize(&all, want_hist ? hist_all.data() : nullptr, out);
-      }
-      // a cut that was no member start after all (or a damaged file): every rank knows, rank 0 reads the whole file the ordinary way —
-      // its readers are gzread byte for byte, error text included — and the others contribute the identity to the exchange below.  What
-      // the block stage said of itself ("did not join up") is no part of that text: a damaged file must end with gzread's message alone
-      // (tests/test_gpu_inflate_crafted.py::test_sharded_stretch_reference_before_the_member_start)
-      local = SCFQ_OK;
-      g_err[0] = '\0';
-      scfq_partial_identity(&mine, want_hist ? hist.data() : nullptr);
-      if (rank == 0) {
-        scfq_opts o1 = o;
-        o1.n_devices = std::min(o.n_devices, 1);
-        local = count_file_partial(path, &o1, &mine, want_hist ? hist.data() : nullptr);
-      }
-    } else if (sharded) {
-      if (o.n_devices >= 1 && hipSetDevice(o.device_ids[0]) != hipSuccess) local = SCFQ_EHIP;
-      if (!local && b_hi > b_lo) {
-        Ctx* c = nullptr;
-        SessionLock sl;
-        local = get_ctx(&c, sl);
-        if (!local) local = begin_session(c, rank == 0);
-        if (!local) {
-          local = ingest_bgzf_device(c, img + b_lo, b_hi - b_lo, o.flags, opt_chunk(&o), timing, prev, fd, b_lo);
-          if (local == kFallbackToHost || local == kNotPureBgzf) {
-            // no room for the device path's buffers (kNotPureBgzf cannot happen: the range was walked): the host's block-parallel
-            // inflate over the same members
-            local = begin_session(c, rank == 0);
-            if (!local) { BgzfSource src(fd, b_hi); src.pos = b_lo; local = ingest(c, src, prev, o.flags, opt_chunk(&o), timing); }
-          }
-        }
-        if (!local) local = end_session(c, want_hist, &mine, want_hist ? hist.data() : nullptr);
-      }
-    } else if (rank == 0) {
-      scfq_opts o1 = o;
-      o1.n_devices = std::min(o.n_devices, 1);
-      local = count_file_partial(path, &o1, &mine, want_hist ? hist.data() : nullptr);
-    }
-    if (!sharded_gz) {
-      if (img) munmap(const_cast<uint8_t*>(img), (size_t)size);
-      if (fd >= 0) close(fd);
-    }
-  } else {
-    const int fd = open(path, O_RDONLY);
-    struct stat sb;
-    if (fd < 0 || fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) {
-      if (fd >= 0) close(fd);
-      local = SCFQ_EOPEN;
-    } else {
-      const uint64_t size = (uint64_t)sb.st_size;
-      const uint64_t lo = size / (uint64_t)world * (uint64_t)rank + std::min<uint64_t>(size % (uint64_t)world, (uint64_t)rank);
-      const uint64_t hi = size / (uint64_t)world * (uint64_t)(rank + 1) + std::min<uint64_t>(size % (uint64_t)world, (uint64_t)rank + 1);
-      int prev = -1;
-      if (lo) { uint8_t pb; if (pread(fd, &pb, 1, (off_t)(lo - 1)) != 1) local = SCFQ_EIO; else prev = pb; }
-      if (!local && o.n_devices >= 1 && hipSetDevice(o.device_ids[0]) != hipSuccess) local = SCFQ_EHIP;
-      if (!local) {
-        Ctx* c = nullptr;
-        SessionLock sl;
-        local = get_ctx(&c, sl);
-        if (!local) local = begin_session(c, lo == 0);
-        if (!local && hi > lo) {
-          FdSource src(fd, lo, hi);
-          local = ingest(c, src, prev, o.flags, std::min<uint64_t>(opt_chunk(&o), std::max<uint64_t>((hi - lo + 4095) & ~4095ull, 4096)), timing);
-        }
-        if (!local) local = end_session(c, want_hist, &mine, want_hist ? hist.data() : nullptr);
-      }
-      close(fd);
-    }
-  }
-  if (local) scfq_partial_identity(&mine, want_hist ? hist.data() : nullptr);
-  mine.reserved[0] = (uint64_t)(int64_t)local;       // every rank learns whether any rank failed
-  rc = scfq_comm_exchange(comm, &mine, want_hist ? hist.data() : nullptr, &all, want_hist ? hist_all.data() : nullptr, 0);
-  if (rc) { std::snprintf(g_err, sizeof g_err, "%s", scfq_comm_error_detail()); return local ? local : rc; }
-  if (local) return local;
-  if (all.reserved[0]) { std::snprintf(g_err, sizeof g_err, "another rank failed to count its shard"); return SCFQ_EIO; }
-  return scfq_partial_finalize(&all, want_hist ? hist_all.data() : nullptr, out);
-}
 
 // host only (include/sc_fqcount_debug.h): the two rules of the gzip-member shards, for the CPU tests
 int64_t scfq_debug_gz_member_boundary(const char* path, uint64_t from, int* first_byte) {
   if (!path || !first_byte) return SCFQ_EARG;
-  const int fd = open(path, O_RDONLY);
-  struct stat sb;
-  if (fd < 0 || fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode) || sb.st_size == 0) { if (fd >= 0) close(fd); return SCFQ_EOPEN; }
-  void* m = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-  close(fd);
-  if (m == MAP_FAILED) return SCFQ_EIO;
-  const uint64_t n = (uint64_t)sb.st_size;
-  const uint64_t at = gz_member_boundary(static_cast<const uint8_t*>(m), n, std::min(from, n), n, first_byte);
-  munmap(m, (size_t)n);
-  return (int64_t)at;
+  InputFile in(path);
+  if (!in.regular() || in.size() == 0) return SCFQ_EOPEN;
+  if (!in.map()) return SCFQ_EIO;
+  const uint64_t n = in.size();
+  return (int64_t)scfq_shard::gz_member_boundary(in.img(), n, std::min(from, n), n, first_byte);
 }
 int scfq_debug_gz_shard_fix(scfq_partial* p, uint64_t* hist, int true_prev, int first_byte, uint32_t flags) {
   if (!p) return SCFQ_EARG;
-  gz_shard_fix(p, hist, true_prev, first_byte, flags);
+  scfq_shard::gz_shard_fix(p, hist, true_prev, first_byte, flags);
   return SCFQ_OK;
 }
 
@@ -2083,11 +1515,10 @@ int scfq_prepare(const scfq_opts* opts) {
   HIPCHK(hipGetDevice(&prev));
   for (int d = 0; d < nd && !rc; ++d) {
     if (o.n_devices >= 1 && hipSetDevice(o.device_ids[d]) != hipSuccess) { rc = SCFQ_EHIP; break; }
-    Ctx* c = nullptr;
-    SessionLock sl;
-    rc = get_ctx(&c, sl);
-    if (!rc) rc = ensure_staging(c, kDefaultChunk, true);
-    if (!rc) rc = want_copy_stream(c);
+    Session s;
+    rc = s.take();
+    if (!rc) rc = ensure_staging(s.c, kDefaultChunk, true);
+    if (!rc) rc = want_copy_stream(s.c);
   }
   (void)hipSetDevice(prev);
   if (!rc && o.n_devices > 1 && !exchange_on_host(o.device_ids, o.n_devices)) {
@@ -2160,109 +1591,96 @@ int scfq_stage_file(const char* path, const scfq_opts* opts, void** dptr_out, ui
   if (rc) return rc;
   *dptr_out = nullptr;
   *n_out = 0;
-  const size_t plen = std::strlen(path);
-  const bool is_gz = plen >= 3 && std::memcmp(path + plen - 3, ".gz", 3) == 0;     // src/fq_dedup.nim:32, src/fq_count.nim:31
+  const bool is_gz = is_gz_name(path);
+  InputFile in;
   std::unique_ptr<Source> src;
-  int fd = -1;
   gzFile gz = nullptr;
   uint64_t hint = 64ull << 20;
-  struct Closer { int* fd; gzFile* gz; std::unique_ptr<Source>* s; ~Closer() { s->reset(); if (*gz) gzclose(*gz); if (*fd >= 0) close(*fd); } } closer{&fd, &gz, &src};
-  struct stat sb;
+  GzCloser closer{&gz, &src};
   if (is_gz && bgzf_device_enabled()) {
     // pure BGZF: the inflated size is the sum of the ISIZE fields, and the members are inflated on the device straight
     // into the result buffer
-    const int bfd = open(path, O_RDONLY);
-    struct stat bsb;
-    if (bfd >= 0 && fstat(bfd, &bsb) == 0 && S_ISREG(bsb.st_mode) && bsb.st_size > 0 && !std::getenv("SCFQ_NO_BGZF") && scfq_bgzf::probe(bfd)) {
-      void* m = mmap(nullptr, (size_t)bsb.st_size, PROT_READ, MAP_PRIVATE, bfd, 0);
-      if (m != MAP_FAILED) {
-        struct Unmap { void* m; size_t n; int fd; ~Unmap() { munmap(m, n); close(fd); } } um{m, (size_t)bsb.st_size, bfd};
-        const uint8_t* img = static_cast<const uint8_t*>(m);
-        const uint64_t fsize = (uint64_t)bsb.st_size;
-        if (bgzf_is_pure(img, fsize)) {
-          uint64_t total = 0;
-          for (uint64_t q = 0; q < fsize;) { uint32_t hl; const uint32_t bs = scfq_bgzf::block_size(img + q, fsize - q, &hl); total += scfq_bgzf::rd32(img + q + bs - 4); q += bs; }
-          if (opts && opts->n_devices >= 1) HIPCHK(hipSetDevice(opts->device_ids[0]));
-          Ctx* c = nullptr;
-          SessionLock sl;
-          rc = get_ctx(&c, sl);
-          if (rc) return rc;
-          if ((rc = want_copy_stream(c))) return rc;      // (staging a whole file: chunk k + 1 crosses PCIe under chunk k's work)
-          rc = ensure_bgzf_device_buffers(c, fsize);
-          if (rc == SCFQ_OK) {
-            uint8_t* d_buf = nullptr;
-            HIPCHK(hipMalloc(&d_buf, std::max<uint64_t>(total, 16)));
-            struct BufGuard { uint8_t** p; ~BufGuard() { if (*p) (void)hipFree(*p); } } bg{&d_buf};
-            HIPCHK(hipMemsetAsync(c->d_dstatus, 0, sizeof(uint32_t), c->compute));
-            uint64_t pos = 0, off = 0;
-            for (unsigned it = 0; pos < fsize; ++it) {
-              const int b = it & 1;
-              if (it >= 2) HIPCHK(hipEventSynchronize(c->ev_copied[b]));
-              uint32_t nb = 0;
-              uint64_t ob = 0;
-              const int64_t used = bgzf_plan(img, fsize, pos, c->inf_cap, c->comp_cap, bgzf_members_per_launch(c->inf_cap), c->h_blk[b], &nb, &ob);
-              if (used < 0) return SCFQ_EGZ;
-              if (used == 0) break;
-              if (it >= 2) HIPCHK(hipStreamWaitEvent(c->copy, c->ev_scanned[b], 0));
-              { FileBytes fb; fb.img = img; fb.fd = bfd; if ((rc = copy_through_ring(c, c->d_comp[b], fb, pos, (uint64_t)used))) return rc; }
-              HIPCHK(hipMemcpyAsync(c->d_blk[b], c->h_blk[b], nb * sizeof(scfq_dinflate::Block), hipMemcpyHostToDevice, c->copy));
-              HIPCHK(hipEventRecord(c->ev_copied[b], c->copy));
-              HIPCHK(hipStreamWaitEvent(c->compute, c->ev_copied[b], 0));
-              if (nb) {
-                hipLaunchKernelGGL(scfq_dinflate::bgzf_inflate, dim3((nb + scfq_dinflate::kWavesPerWg - 1) / scfq_dinflate::kWavesPerWg),
-                                   dim3(64 * scfq_dinflate::kWavesPerWg), scfq_dinflate::kWavesPerWg * scfq_dinflate::kWaveLdsBytes,
-                                   c->compute, c->d_comp[b], c->d_blk[b], nb, d_buf + off, c->d_dstatus, inflate_serial_loop());
-                HIPCHK(hipGetLastError());
-                if ((rc = bgzf_crc_ready(c))) return rc;
-                hipLaunchKernelGGL(scfq_dinflate::bgzf_crc32_members, dim3(nb), dim3(256), 0, c->compute, d_buf + off, c->d_blk[b], nb, c->d_dstatus);
-                HIPCHK(hipGetLastError());
-              }
-              HIPCHK(hipEventRecord(c->ev_scanned[b], c->compute));
-              pos += (uint64_t)used;
-              off += ob;
+    InputFile bin(path);
+    if (bin.size() > 0 && is_bgzf_input(bin) && bin.map()) {
+      const uint8_t* img = bin.img();
+      const uint64_t fsize = bin.size();
+      if (bgzf_is_pure(img, fsize)) {
+        uint64_t total = 0;
+        for (uint64_t q = 0; q < fsize;) { uint32_t hl; const uint32_t bs = scfq_bgzf::block_size(img + q, fsize - q, &hl); total += scfq_bgzf::rd32(img + q + bs - 4); q += bs; }
+        if (opts && opts->n_devices >= 1) HIPCHK(hipSetDevice(opts->device_ids[0]));
+        Session s;
+        rc = s.take();
+        if (rc) return rc;
+        Ctx* c = s.c;
+        if ((rc = want_copy_stream(c))) return rc;      // (staging a whole file: chunk k + 1 crosses PCIe under chunk k's work)
+        rc = ensure_bgzf_device_buffers(c, fsize);
+        if (rc == SCFQ_OK) {
+          uint8_t* d_buf = nullptr;
+          HIPCHK(hipMalloc(&d_buf, std::max<uint64_t>(total, 16)));
+          struct BufGuard { uint8_t** p; ~BufGuard() { if (*p) (void)hipFree(*p); } } bg{&d_buf};
+          HIPCHK(hipMemsetAsync(c->d_dstatus, 0, sizeof(uint32_t), c->compute));
+          uint64_t pos = 0, off = 0;
+          for (unsigned it = 0; pos < fsize; ++it) {
+            const int b = it & 1;
+            if (it >= 2) HIPCHK(hipEventSynchronize(c->ev_copied[b]));
+            uint32_t nb = 0;
+            uint64_t ob = 0;
+            const int64_t used = bgzf_plan(img, fsize, pos, c->inf_cap, c->comp_cap, bgzf_members_per_launch(c->inf_cap), c->h_blk[b], &nb, &ob);
+            if (used < 0) return SCFQ_EGZ;
+            if (used == 0) break;
+            if (it >= 2) HIPCHK(hipStreamWaitEvent(c->copy, c->ev_scanned[b], 0));
+            if ((rc = copy_through_ring(c, c->d_comp[b], bin.bytes(), pos, (uint64_t)used))) return rc;
+            HIPCHK(hipMemcpyAsync(c->d_blk[b], c->h_blk[b], nb * sizeof(scfq_dinflate::Block), hipMemcpyHostToDevice, c->copy));
+            HIPCHK(hipEventRecord(c->ev_copied[b], c->copy));
+            HIPCHK(hipStreamWaitEvent(c->compute, c->ev_copied[b], 0));
+            if (nb) {
+              hipLaunchKernelGGL(scfq_dinflate::bgzf_inflate, dim3((nb + scfq_dinflate::kWavesPerWg - 1) / scfq_dinflate::kWavesPerWg),
+                                 dim3(64 * scfq_dinflate::kWavesPerWg), scfq_dinflate::kWavesPerWg * scfq_dinflate::kWaveLdsBytes,
+                                 c->compute, c->d_comp[b], c->d_blk[b], nb, d_buf + off, c->d_dstatus, inflate_serial_loop());
+              HIPCHK(hipGetLastError());
+              if ((rc = bgzf_crc_ready(c))) return rc;
+              hipLaunchKernelGGL(scfq_dinflate::bgzf_crc32_members, dim3(nb), dim3(256), 0, c->compute, d_buf + off, c->d_blk[b], nb, c->d_dstatus);
+              HIPCHK(hipGetLastError());
             }
-            uint32_t st = 0;
-            HIPCHK(hipMemcpyAsync(c->h_state + kStateWords - 1, c->d_dstatus, sizeof(uint32_t), hipMemcpyDeviceToHost, c->compute));
-            HIPCHK(hipStreamSynchronize(c->compute));
-            std::memcpy(&st, c->h_state + kStateWords - 1, sizeof st);
-            if (st || off != total) { std::snprintf(g_err, sizeof g_err, "device inflate: error mask 0x%x", st); return SCFQ_EGZ; }
-            *dptr_out = d_buf;
-            *n_out = total;
-            d_buf = nullptr;
-            return SCFQ_OK;
+            HIPCHK(hipEventRecord(c->ev_scanned[b], c->compute));
+            pos += (uint64_t)used;
+            off += ob;
           }
-          if (rc != kFallbackToHost) return rc;
-          rc = SCFQ_OK;
+          uint32_t st = 0;
+          HIPCHK(hipMemcpyAsync(c->h_state + kStateWords - 1, c->d_dstatus, sizeof(uint32_t), hipMemcpyDeviceToHost, c->compute));
+          HIPCHK(hipStreamSynchronize(c->compute));
+          std::memcpy(&st, c->h_state + kStateWords - 1, sizeof st);
+          if (st || off != total) { std::snprintf(g_err, sizeof g_err, "device inflate: error mask 0x%x", st); return SCFQ_EGZ; }
+          *dptr_out = d_buf;
+          *n_out = total;
+          d_buf = nullptr;
+          return SCFQ_OK;
         }
-      } else {
-        close(bfd);
+        if (rc != kFallbackToHost) return rc;
+        rc = SCFQ_OK;
       }
-    } else if (bfd >= 0) {
-      close(bfd);
     }
   }
+  in.open(path);      // (opened again: the device path above has let go of its own descriptor and mapping)
   if (is_gz) {
-    fd = open(path, O_RDONLY);
-    if (fd >= 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode)) hint = std::max<uint64_t>(hint, 4 * (uint64_t)sb.st_size);
-    if (fd >= 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && !std::getenv("SCFQ_NO_BGZF") && scfq_bgzf::probe(fd)) {
-      src.reset(new BgzfSource(fd, (uint64_t)sb.st_size));
+    if (in.regular()) hint = std::max<uint64_t>(hint, 4 * in.size());
+    if (is_bgzf_input(in)) {
+      src.reset(new BgzfSource(in.fd, in.size()));
     } else {
-      if (fd >= 0) close(fd);
-      fd = -1;
+      in.reset();
       src = open_gz_source(path, opt_chunk(opts), &gz);
       if (!src) return SCFQ_EOPEN;
     }
   } else {
-    fd = open(path, O_RDONLY);
-    if (fd < 0 || fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) return SCFQ_EOPEN;
-    hint = std::max<uint64_t>((uint64_t)sb.st_size, 4096);
-    src.reset(new FdSource(fd, 0, (uint64_t)sb.st_size));
+    if (!in.regular()) return SCFQ_EOPEN;
+    hint = std::max<uint64_t>(in.size(), 4096);
+    src.reset(new FdSource(in.fd, 0, in.size()));
   }
   if (opts && opts->n_devices >= 1) HIPCHK(hipSetDevice(opts->device_ids[0]));
-  Ctx* c = nullptr;
-  SessionLock sl;
-  rc = get_ctx(&c, sl);
+  Session s;
+  rc = s.take();
   if (rc) return rc;
+  Ctx* c = s.c;
   if ((rc = want_copy_stream(c))) return rc;      // (staging a whole file: chunk k + 1 crosses PCIe under chunk k's work)
   const uint64_t chunk = opt_chunk(opts);
   rc = ensure_staging(c, chunk, true);
@@ -2344,10 +1762,10 @@ extern "C" {
 // Returns the inflated size, SCFQ_EARG when the image is not pure BGZF or does not fit, SCFQ_EGZ for a corrupt member.
 int64_t scfq_debug_bgzf_inflate(const void* image, uint64_t n, void* out, uint64_t cap) {
   if ((!image && n) || (!out && cap)) return SCFQ_EARG;
-  Ctx* c = nullptr;
-  SessionLock sl;
-  int rc = get_ctx(&c, sl);
+  Session s;
+  int rc = s.take();
   if (rc) return rc;
+  Ctx* c = s.c;
   const uint8_t* img = static_cast<const uint8_t*>(image);
   std::vector<scfq_dinflate::Block> blocks(1u << 20);
   uint64_t total = 0, pos = 0;
@@ -2426,11 +1844,9 @@ int scfq_index_lines_ex2(const void* dptr, uint64_t n, uint64_t* d_line_off, uin
   if (aux) { aux->filled = 0; aux->unk_complete = 0; aux->n_tiles = 0; }
   if (aux && (!aux->keys || !aux->idx || !aux->hdr || (aux->key_bytes != 4 && aux->key_bytes != 8) || aux->hash_bits > 56 || !d_line_off)) return SCFQ_EARG;
   if (flags_out) *flags_out = 1u;            // unknown until the one-pass kernel says otherwise
-  Ctx* c = nullptr;
-  SessionLock sl;
-  int rc = get_ctx(&c, sl);
-  if (rc) return rc;
-  rc = begin_session(c, true);
+  Session s;
+  int rc = s.open(true);
+  Ctx* c = s.c;
   if (rc) return rc;
   if ((rc = wait_for_caller(c, nullptr))) return rc;      // input and line_off are the caller's device buffers
   const uint8_t* base = static_cast<const uint8_t*>(dptr);
@@ -2627,15 +2043,11 @@ static int index_lines_two_pass(Ctx* c, const uint8_t* base, uint64_t n, uint64_
 int64_t scfq_debug_gz_resume(const char* path, uint64_t after_bytes, void* dst, uint64_t cap, uint64_t chunk) {
   if (!path || (!dst && cap)) return SCFQ_EARG;
   if (chunk < (1u << 16)) chunk = 1u << 20;
-  const int fd = open(path, O_RDONLY);
-  struct stat sb;
-  if (fd < 0 || fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode) || sb.st_size < 18) { if (fd >= 0) close(fd); return SCFQ_EOPEN; }
-  const size_t n = (size_t)sb.st_size;
-  void* m = mmap(nullptr, n, PROT_READ, MAP_PRIVATE, fd, 0);
-  close(fd);
-  if (m == MAP_FAILED) return SCFQ_EIO;
-  struct Unmap { void* m; size_t n; ~Unmap() { munmap(m, n); } } um{m, n};
-  const uint8_t* img = static_cast<const uint8_t*>(m);
+  InputFile in(path);
+  if (!in.regular() || in.size() < 18) return SCFQ_EOPEN;
+  if (!in.map()) return SCFQ_EIO;
+  const size_t n = (size_t)in.size();
+  const uint8_t* img = in.img();
   const long h0 = scfq_gzfast::member_header(img, n);
   if (h0 <= 0) return SCFQ_EGZ;
   // first half: the serial decoder over the first member, logging every block header (bit, bytes before it)
@@ -2677,27 +2089,21 @@ int64_t scfq_debug_gz_resume(const char* path, uint64_t after_bytes, void* dst, 
 int64_t scfq_debug_read_file(const char* path, void* dst, uint64_t cap, uint64_t chunk) {
   if (!path || (!dst && cap)) return SCFQ_EARG;
   if (chunk == 0) chunk = kDefaultChunk;
-  const size_t plen = std::strlen(path);
-  const bool is_gz = plen >= 3 && std::memcmp(path + plen - 3, ".gz", 3) == 0;
+  InputFile in(path);
   std::unique_ptr<Source> src;
-  int fd = -1;
   gzFile gz = nullptr;
-  if (is_gz) {
-    fd = open(path, O_RDONLY);
-    struct stat sb;
-    if (fd >= 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && !std::getenv("SCFQ_NO_BGZF") && scfq_bgzf::probe(fd)) {
-      src.reset(new BgzfSource(fd, (uint64_t)sb.st_size));
+  GzCloser closer{&gz, &src};
+  if (is_gz_name(path)) {
+    if (is_bgzf_input(in)) {
+      src.reset(new BgzfSource(in.fd, in.size()));
     } else {
-      if (fd >= 0) close(fd);
-      fd = -1;
+      in.reset();
       src = open_gz_source(path, chunk, &gz);
       if (!src) return SCFQ_EOPEN;
     }
   } else {
-    fd = open(path, O_RDONLY);
-    struct stat sb;
-    if (fd < 0 || fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) { if (fd >= 0) close(fd); return SCFQ_EOPEN; }
-    src.reset(new FdSource(fd, 0, (uint64_t)sb.st_size));
+    if (!in.regular()) return SCFQ_EOPEN;
+    src.reset(new FdSource(in.fd, 0, in.size()));
   }
   std::vector<uint8_t> buf(chunk);
   uint64_t total = 0;
@@ -2710,18 +2116,15 @@ int64_t scfq_debug_read_file(const char* path, void* dst, uint64_t cap, uint64_t
     std::memcpy(static_cast<uint8_t*>(dst) + total, buf.data(), (size_t)got);
     total += (uint64_t)got;
   }
-  src.reset();
-  if (gz) gzclose(gz);
-  if (fd >= 0) close(fd);
   return rc < 0 ? rc : (int64_t)total;
 }
 
 // ---- diagnostic: time of the scan kernel's load structure alone over a device-resident buffer (milliseconds, best of
 // `reps`; < 0 on error). The buffer must be 4 KiB aligned; only whole tiles are streamed.
 double scfq_debug_stream_ms(const void* dptr, uint64_t n, int reps) {
-  Ctx* c = nullptr;
-  SessionLock sl;
-  if (get_ctx(&c, sl) || !dptr || ((uintptr_t)dptr & 4095) || n < (uint64_t)scfq::kTile) return -1.0;
+  Session s;
+  if (s.take() || !dptr || ((uintptr_t)dptr & 4095) || n < (uint64_t)scfq::kTile) return -1.0;
+  Ctx* c = s.c;
   const uint32_t n_tiles = (uint32_t)std::min<uint64_t>(n / scfq::kTile, 0xFFFFFFFFull);
   const uint32_t tpr = pick_tiles_per_range(c, n_tiles);
   const unsigned ranges = (n_tiles + tpr - 1) / tpr, blocks = (ranges + scfq::kWavesPerBlock - 1) / scfq::kWavesPerBlock;
@@ -2747,12 +2150,10 @@ double scfq_debug_stream_ms(const void* dptr, uint64_t n, int reps) {
 // ---- diagnostic: independent byte-serial device kernel (tests only; not used by any counting path) ----
 int scfq_debug_partial_simple(const void* dptr, uint64_t n, int prev_byte, scfq_partial* out) {
   if (!out || (!dptr && n)) return SCFQ_EARG;
-  Ctx* c = nullptr;
-  SessionLock sl;
-  int rc = get_ctx(&c, sl);
+  Session s;
+  int rc = s.open(false);
   if (rc) return rc;
-  rc = begin_session(c, false);
-  if (rc) return rc;
+  Ctx* c = s.c;
   if (n) {
     const uint64_t chunks = (n + 255) / 256;
     rc = ensure_partials(c, chunks, false);
@@ -2767,7 +2168,7 @@ int scfq_debug_partial_simple(const void* dptr, uint64_t n, int prev_byte, scfq_
     HIPCHK(hipGetLastError());
     c->fresh = false;
   }
-  return end_session(c, false, out, nullptr);
+  return s.finish(false, out, nullptr);
 }
 
 }  // extern "C"

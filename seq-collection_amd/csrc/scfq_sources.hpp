@@ -48,6 +48,64 @@ struct FileBytes {
   int fd = -1;                       // ... and, when there is one, the file they are mapped from,
   uint64_t fd_off = 0;               // img[0] being the byte at this offset of it
 };
+
+// An opened input: the descriptor, what fstat said of it and — once map() was asked for — the whole file mapped read-only.  Closed and
+// unmapped when it goes out of scope, whichever return that is.  Mapping is a step of its own (the paths differ in whether and when they
+// map), and unmap() lets the mapping go early (ingest_bgzf_device: once the last compressed byte has crossed).
+struct InputFile {
+  int fd = -1;
+  InputFile() {}
+  explicit InputFile(const char* path) { open(path); }
+  InputFile(InputFile&& o) noexcept { *this = std::move(o); }
+  InputFile& operator=(InputFile&& o) noexcept {
+    if (this != &o) { reset(); fd = o.fd; sb_ = o.sb_; stat_ok_ = o.stat_ok_; m_ = o.m_; o.fd = -1; o.stat_ok_ = false; o.m_ = MAP_FAILED; }
+    return *this;
+  }
+  InputFile(const InputFile&) = delete;
+  InputFile& operator=(const InputFile&) = delete;
+  ~InputFile() { reset(); }
+
+  bool open(const char* path) {
+    reset();
+    fd = ::open(path, O_RDONLY);
+    stat_ok_ = fd >= 0 && fstat(fd, &sb_) == 0;
+    return fd >= 0;
+  }
+  bool is_open() const { return fd >= 0; }
+  bool statted() const { return stat_ok_; }
+  bool directory() const { return stat_ok_ && S_ISDIR(sb_.st_mode); }
+  bool regular() const { return stat_ok_ && S_ISREG(sb_.st_mode); }
+  uint64_t size() const { return regular() ? (uint64_t)sb_.st_size : 0; }      // (0 for what is no regular file: a FIFO, a device)
+  bool map() {      // MAP_PRIVATE, PROT_READ, MADV_SEQUENTIAL; false when there is nothing to map or the kernel says no
+    if (mapped()) return true;
+    if (!regular() || size() == 0) return false;
+    m_ = mmap(nullptr, (size_t)size(), PROT_READ, MAP_PRIVATE, fd, 0);
+    if (m_ != MAP_FAILED) (void)madvise(m_, (size_t)size(), MADV_SEQUENTIAL);
+    return mapped();
+  }
+  bool mapped() const { return m_ != MAP_FAILED; }
+  const uint8_t* img() const { return mapped() ? static_cast<const uint8_t*>(m_) : nullptr; }
+  void unmap() { if (mapped()) { munmap(m_, (size_t)size()); m_ = MAP_FAILED; } }
+  void reset() { unmap(); if (fd >= 0) ::close(fd); fd = -1; stat_ok_ = false; }
+  FileBytes bytes(uint64_t off = 0) const { FileBytes fb; fb.img = img() + off; fb.fd = fd; fb.fd_off = off; return fb; }
+
+ private:
+  struct stat sb_;
+  bool stat_ok_ = false;
+  void* m_ = MAP_FAILED;
+};
+
+// fastq[^3 .. ^1] == ".gz"      src/fq_count.nim:31, src/fq_dedup.nim:32 (case-sensitive, last three bytes)
+inline bool is_gz_name(const char* path) {
+  const size_t n = std::strlen(path);
+  return n >= 3 && std::memcmp(path + n - 3, ".gz", 3) == 0;
+}
+// a BGZF (bgzip) file the block-parallel paths may take: a regular file that starts with a BGZF member, unless SCFQ_NO_BGZF says no.  (How
+// big it has to be is the caller's condition: it differs between them.)
+inline bool is_bgzf_input(const InputFile& in) { return in.regular() && !std::getenv("SCFQ_NO_BGZF") && scfq_bgzf::probe(in.fd); }
+// what stands behind the Source of a ".gz" path that zlib reads: the source goes first, then the gzFile (which owns its descriptor)
+struct GzCloser { gzFile* f; std::unique_ptr<Source>* s; ~GzCloser() { s->reset(); if (*f) gzclose(*f); } };
+
 inline int copy_file_bytes(const FileBytes& fb, uint64_t off, uint8_t* dst, uint64_t len, bool always_pread = false) {
   // (pread for the big pieces of big files only — 128 MiB pieces: 49 ms per 2.43 GB against 80 with memcpy; with the 16 MiB pieces of
   // files up to 1 GiB memcpy out of the mapping is the faster by 3 - 8 %: profiles/r04/copy_variants.jsonl.  SCFQ_COPY_PREAD = 0 / 2:
