@@ -54,8 +54,11 @@ __device__ __forceinline__ uint64_t load_head_word(const uint8_t* base, uint64_t
   uint32_t shift = 0;
   if (a + 8 > n) { const uint64_t a2 = (n >= 8) ? n - 8 : 0; shift = (uint32_t)(a - a2) * 8; a = a2; }   // last bytes of the input
   uint64_t v = 0;
-  if (8u * k < len && n >= 8) { __builtin_memcpy(&v, base + a, 8); v = (shift < 64) ? (v >> shift) : 0; }
-  else if (8u * k < len) { for (uint64_t b = 0; b < 8 && a + b < n; ++b) v |= (uint64_t)base[a + b] << (8 * b); }
+  if (8u * k < len) {
+    if (n >= 8) __builtin_memcpy(&v, base + a, 8);
+    else for (uint64_t b = 0; b < 8 && a + b < n; ++b) v |= (uint64_t)base[a + b] << (8 * b);      // (an input shorter than a word: a is 0)
+    v = (shift < 64) ? (v >> shift) : 0;
+  }
   const uint64_t valid = (len > 8u * k) ? len - 8u * k : 0;          // bytes of this word that belong to the header
   return (valid >= 8) ? v : (valid ? (v & ((1ull << (8 * valid)) - 1)) : 0);
 }
@@ -422,7 +425,9 @@ __device__ __forceinline__ void wave_copy(uint8_t* dst, const uint8_t* src, uint
 }
 
 __global__ __launch_bounds__(256) void dd_gather(const uint8_t* base, uint64_t n, const uint64_t* line_off, uint64_t lines,
-                                                uint64_t n_hdr, const uint64_t* group_off, const uint64_t* out_len, uint8_t* out) {
+                                                uint64_t n_hdr, const uint64_t* group_off, uint64_t n_groups, const uint64_t* out_len, uint8_t* out,
+                                                uint64_t out_cap) {
+  if (group_off[n_groups] > out_cap) return;                  // (the scan's last entry is the total: more than out holds, nothing is written)
   const uint64_t g = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const uint32_t lane = threadIdx.x & 63;
   const uint64_t i0 = g * kGatherGroup;
@@ -571,12 +576,14 @@ int dedup_device(const uint8_t* d_in, uint64_t n, uint8_t* user_out, uint64_t us
                                                    rocprim::plus<uint64_t>(), stream));
   mark2("lengths + scan enqueued");
   uint64_t h[3] = {0, 0, 0};
-  // a caller's buffer that holds the whole input holds any result: the gather goes out behind the scan at once, and the one
-  // wait of the call is the one at the end (otherwise the size has to come back first — the result is allocated to fit)
+  // a caller's buffer that holds the whole input holds any result but one: the gather goes out behind the scan at once, and the one
+  // wait of the call is the one at the end (otherwise the size has to come back first — the result is allocated to fit).  The one:
+  // nothing dropped and a final line without '\n', which gains one — n + 1 bytes.  The gather itself leaves a result alone that
+  // does not fit (out_cap), and the size that comes back says so.
   const bool gather_first = !sized_only && user_out && user_cap >= n;
   if (gather_first) {
     hipLaunchKernelGGL(dd_gather, dim3((unsigned)((n_groups + 3) / 4)), dim3(256), 0, stream, d_in, n, line_off.as<uint64_t>(), lines, n_hdr,
-                       group_off.as<uint64_t>(), out_len.as<uint64_t>(), user_out);
+                       group_off.as<uint64_t>(), n_groups, out_len.as<uint64_t>(), user_out, user_cap);
     SCFQ_SCRATCH_CHK(g_derr, hipGetLastError());
   }
   mark2("gather enqueued");
@@ -591,6 +598,7 @@ int dedup_device(const uint8_t* d_in, uint64_t n, uint8_t* user_out, uint64_t us
   st->bytes_out = h[0];
   st->false_positive = 0;
   *out_bytes = h[0];
+  if (gather_first && h[0] > user_cap) return SCFQ_EARG;
   if (sized_only || h[0] == 0 || gather_first) return SCFQ_OK;
   DevBuf own;
   uint8_t* o = user_out;
@@ -601,7 +609,7 @@ int dedup_device(const uint8_t* d_in, uint64_t n, uint8_t* user_out, uint64_t us
     return SCFQ_EARG;
   }
   hipLaunchKernelGGL(dd_gather, dim3((unsigned)((n_groups + 3) / 4)), dim3(256), 0, stream, d_in, n, line_off.as<uint64_t>(), lines, n_hdr,
-                     group_off.as<uint64_t>(), out_len.as<uint64_t>(), o);
+                     group_off.as<uint64_t>(), n_groups, out_len.as<uint64_t>(), o, h[0]);
   SCFQ_SCRATCH_CHK(g_derr, hipGetLastError());
   SCFQ_SCRATCH_CHK(g_derr, hipStreamSynchronize(stream));
   mark("gather");
