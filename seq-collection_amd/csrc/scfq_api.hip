@@ -11,6 +11,7 @@
 #include "../../include/sc_fqcount.h"
 #include "../../include/sc_fqcount_debug.h"
 #include "fq_scan_kernels.hpp"
+#include "fq_index_kernels.hpp"
 #include "scfq_bgzf.hpp"
 #include "scfq_gzfast.hpp"
 #include "scfq_pgz.hpp"
@@ -166,9 +167,7 @@ struct Ctx {
   uint8_t* d_wg_ok = nullptr;
   uint32_t* d_hist_wg = nullptr;
   bool from_start = false;             // the session begins at the start of the input: header lines are class 0
-  uint32_t last_tpr = 0;               // geometry of the last scan launch (K5 re-walks the same ranges)
-  uint64_t last_ranges = 0;
-  uint64_t* d_first_ord = nullptr;     // K5: per range, ordinal of the first line start it emits
+  uint64_t* d_first_ord = nullptr;     // K5: the scratch of the line index (scfq_index.hpp), grow-only
   uint64_t cap_first_ord = 0;
   uint64_t* d_block_partials = nullptr;   // level-1 fold output
   uint64_t cap_blocks = 0;
@@ -460,8 +459,6 @@ int scan_async(Ctx* c, const uint8_t* dptr, uint64_t n, int prev_byte, uint32_t 
   const uint64_t n_ranges = (NT + tpr - 1) / tpr;
   int rc = ensure_partials(c, n_ranges, hist);
   if (rc) return rc;
-  c->last_tpr = tpr;
-  c->last_ranges = n_ranges;
   scfq::ScanArgs a;
   a.base = dptr;
   a.n = n;
@@ -1823,215 +1820,9 @@ int64_t scfq_debug_bgzf_inflate(const void* image, uint64_t n, void* out, uint64
   return (int64_t)total;
 }
 
-// ---- K5: line index of a device-resident input ------------------------------------------------------------------
-// One pass over the input (fq_index_pos keeps the newline positions of every tile, fq_index_expand_pos turns them into offsets; the
-// mask form — fq_index_masks keeps one bit per byte, fq_index_expand walks the bits — for inputs with 128+ newlines in a 4 KiB tile);
-// SCFQ_INDEX_TWO_PASS=1 keeps the first form (K1 + K2 count, prefix kernel, second pass over the input) for comparison.
-static int index_lines_two_pass(Ctx* c, const uint8_t* base, uint64_t n, uint64_t* d_line_off, uint64_t cap, uint64_t* lines_out);
-
-// internal (fq-dedup): csrc/scfq_index_aux.hpp
-
-int scfq_index_lines(const void* dptr, uint64_t n, uint64_t* d_line_off, uint64_t cap, uint64_t* lines_out) {
-  return scfq_index_lines_ex(dptr, n, d_line_off, cap, lines_out, nullptr);
-}
-
-int scfq_index_lines_ex(const void* dptr, uint64_t n, uint64_t* d_line_off, uint64_t cap, uint64_t* lines_out, uint32_t* flags_out) {
-  return scfq_index_lines_ex2(dptr, n, d_line_off, cap, lines_out, flags_out, nullptr);
-}
-
-int scfq_index_lines_ex2(const void* dptr, uint64_t n, uint64_t* d_line_off, uint64_t cap, uint64_t* lines_out, uint32_t* flags_out, scfq_index_aux* aux) {
-  if ((!dptr && n) || !lines_out) return SCFQ_EARG;
-  if (aux) { aux->filled = 0; aux->unk_complete = 0; aux->n_tiles = 0; }
-  if (aux && (!aux->keys || !aux->idx || !aux->hdr || (aux->key_bytes != 4 && aux->key_bytes != 8) || aux->hash_bits > 56 || !d_line_off)) return SCFQ_EARG;
-  if (flags_out) *flags_out = 1u;            // unknown until the one-pass kernel says otherwise
-  Session s;
-  int rc = s.open(true);
-  Ctx* c = s.c;
-  if (rc) return rc;
-  if ((rc = wait_for_caller(c, nullptr))) return rc;      // input and line_off are the caller's device buffers
-  const uint8_t* base = static_cast<const uint8_t*>(dptr);
-  static const bool two_pass = env_int("SCFQ_INDEX_TWO_PASS", 0) != 0;
-  if (two_pass) return index_lines_two_pass(c, base, n, d_line_off, cap, lines_out);
-  *lines_out = 0;
-  if (n == 0) {
-    if (flags_out) *flags_out = 0;
-    if (d_line_off && cap >= 1) { HIPCHK(hipMemsetAsync(d_line_off, 0, sizeof(uint64_t), c->compute)); HIPCHK(hipStreamSynchronize(c->compute)); }
-    return SCFQ_OK;
-  }
-  const uint64_t B = (uint64_t)(uintptr_t)base, A0 = B & ~(uint64_t)(scfq::kTile - 1);
-  const uint64_t n_tiles = (B + n - A0 + scfq::kTile - 1) / scfq::kTile;
-  if (n_tiles >= (1ull << 32)) { std::snprintf(g_err, sizeof g_err, "a single index launch covers at most 16 TiB"); return SCFQ_EARG; }
-  const uint32_t tpr = pick_tiles_per_range(c, n_tiles);
-  const uint64_t n_ranges = (n_tiles + tpr - 1) / tpr;
-  const bool write = d_line_off && cap >= 1;
-  // The compact form first (fq_index_pos: 16-bit newline positions per tile, 256 B of scratch per tile), the mask form (a bit per
-  // byte, 512 B per tile) when a tile holds more newlines than its slot — lines shorter than 33 bytes on average — or
-  // SCFQ_INDEX_COMPACT=0 says so.  scratch: [n_tiles * (32 | 64)] positions or masks | [n_ranges] counts | [n_ranges + 1] first ordinals | flags
-  static const bool compact_on = env_int("SCFQ_INDEX_COMPACT", 1) != 0;
-  uint64_t* d_ord = nullptr;
-  uint32_t* d_flags = nullptr;
-  bool have_state = false;      // the compact form has brought the line count, the last byte and the flags back already
-  for (int form = compact_on ? 0 : 1; form < 2; ++form) {
-    const bool with_hash = form == 0 && aux && write;
-    const uint64_t per_tile = form == 0 ? scfq::kPosCap / 4 + (with_hash ? scfq::kPosHashCap : 0) : 64;
-    const uint64_t words = n_tiles * per_tile + 2 * n_ranges + 8;
-    if (words > c->cap_first_ord) {
-      HIPCHK(hipStreamSynchronize(c->compute));
-      if (c->d_first_ord) HIPCHK(hipFree(c->d_first_ord));
-      c->d_first_ord = nullptr;
-      c->cap_first_ord = 0;
-      const uint64_t want = words + words / 8;
-      HIPCHK(hipMalloc(&c->d_first_ord, want * sizeof(uint64_t)));
-      c->cap_first_ord = want;
-    }
-    uint64_t* d_tiles = c->d_first_ord;
-    uint64_t* d_counts = d_tiles + n_tiles * per_tile;
-    d_ord = d_counts + n_ranges;
-    d_flags = reinterpret_cast<uint32_t*>(d_ord + n_ranges + 1);
-    HIPCHK(hipMemsetAsync(d_flags, 0, 8, c->compute));
-    if (write) HIPCHK(hipMemsetAsync(d_line_off, 0, sizeof(uint64_t), c->compute));          // line 0 starts at offset 0
-    const unsigned grid = (unsigned)((n_ranges + scfq::kWavesPerBlock - 1) / scfq::kWavesPerBlock);
-    if (form == 0) {
-      scfq::IndexPosArgs pa{};
-      pa.hash_at = with_hash ? d_tiles + n_tiles * (scfq::kPosCap / 4) : nullptr;      // (behind the position slots)
-      pa.hash_seed = aux ? aux->seed : 0;
-      pa.base = base;
-      pa.n = n;
-      pa.tiles_per_range = tpr;
-      pa.n_ranges = n_ranges;
-      pa.pos = reinterpret_cast<uint16_t*>(d_tiles);
-      pa.counts = d_counts;
-      pa.flags = d_flags;
-      pa.want_cr = flags_out ? 1u : 0u;
-      hipLaunchKernelGGL(scfq::fq_index_pos, dim3(grid), dim3(64 * scfq::kWavesPerBlock), scfq::kIndexPosLds, c->compute, pa);
-    } else {
-      scfq::IndexMaskArgs ma;
-      ma.base = base;
-      ma.n = n;
-      ma.tiles_per_range = tpr;
-      ma.n_ranges = n_ranges;
-      ma.masks = d_tiles;
-      ma.counts = d_counts;
-      ma.flags_out = flags_out ? d_flags : nullptr;
-      hipLaunchKernelGGL(scfq::fq_index_masks, dim3(grid), dim3(64 * scfq::kWavesPerBlock), scfq::kWavesPerBlock * 2 * scfq::kTile, c->compute, ma);
-    }
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(scfq::fq_nl_prefix, dim3(1), dim3(1024), 0, c->compute, d_counts, n_ranges, (uint64_t)0, d_ord, 1u);
-    HIPCHK(hipGetLastError());
-    if (write && form == 0) {
-      scfq::IndexExpandPosArgs ea{};
-      if (with_hash) {
-        ea.hash_at = d_tiles + n_tiles * (scfq::kPosCap / 4);
-        ea.keys = aux->keys; ea.idx = aux->idx; ea.hdr = aux->hdr;
-        ea.cap_records = aux->cap_records; ea.key_bytes = aux->key_bytes; ea.hash_bits = aux->hash_bits; ea.hash_seed = aux->seed;
-        ea.unk = (aux->unk && aux->unk_tiles >= n_tiles) ? aux->unk : nullptr;
-        ea.flags_rw = d_flags;
-      }
-      ea.pos = reinterpret_cast<const uint16_t*>(d_tiles);
-      ea.flags = d_flags;
-      ea.lead = B - A0;
-      ea.n_tiles = (uint32_t)n_tiles;
-      ea.tiles_per_range = tpr;
-      ea.n_ranges = n_ranges;
-      ea.first_ord = d_ord;
-      ea.line_off = d_line_off;
-      ea.cap = cap;
-      ea.off_base = 0;
-      hipLaunchKernelGGL(scfq::fq_index_expand_pos, dim3((unsigned)((n_ranges + 3) / 4)), dim3(256), 0, c->compute, ea);
-      HIPCHK(hipGetLastError());
-    } else if (write) {
-      scfq::IndexExpandArgs ea;
-      ea.masks = d_tiles;
-      ea.lead = B - A0;
-      ea.n_tiles = (uint32_t)n_tiles;
-      ea.tiles_per_range = tpr;
-      ea.n_ranges = n_ranges;
-      ea.first_ord = d_ord;
-      ea.line_off = d_line_off;
-      ea.cap = cap;
-      ea.off_base = 0;
-      hipLaunchKernelGGL(scfq::fq_index_expand, dim3((unsigned)((n_ranges + 3) / 4)), dim3(256), 0, c->compute, ea);
-      HIPCHK(hipGetLastError());
-    }
-    if (form == 1) break;
-    // (the compact form's one question to the device: did every tile fit its slot?  Answered together with the line count below when
-    // it did; a file of very short lines pays this wait and a second pass)
-    HIPCHK(hipMemcpyAsync(c->h_state + 2, d_flags, 4, hipMemcpyDeviceToHost, c->compute));
-    HIPCHK(hipMemcpyAsync(c->h_state, d_ord + n_ranges, sizeof(uint64_t), hipMemcpyDeviceToHost, c->compute));
-    HIPCHK(hipMemcpyAsync(c->h_state + 1, base + n - 1, 1, hipMemcpyDeviceToHost, c->compute));
-    HIPCHK(hipStreamSynchronize(c->compute));
-    if (!(c->h_state[2] & 2u)) {
-      have_state = true;
-      if (with_hash) { aux->filled = 1; aux->n_tiles = n_tiles; aux->unk_complete = (aux->unk && aux->unk_tiles >= n_tiles && !(c->h_state[2] & 4u)) ? 1 : 0; }
-      break;
-    }
-    trace("line index: a tile with more newlines than the compact form's slot holds, the mask form runs");
-  }
-  // first_ord[n_ranges] = 1 + number of '\n'
-  if (!have_state) {
-    HIPCHK(hipMemcpyAsync(c->h_state, d_ord + n_ranges, sizeof(uint64_t), hipMemcpyDeviceToHost, c->compute));
-    HIPCHK(hipMemcpyAsync(c->h_state + 1, base + n - 1, 1, hipMemcpyDeviceToHost, c->compute));
-    HIPCHK(hipMemcpyAsync(c->h_state + 2, d_flags, 4, hipMemcpyDeviceToHost, c->compute));
-    HIPCHK(hipStreamSynchronize(c->compute));
-  }
-  if (flags_out) *flags_out = (uint32_t)(c->h_state[2] & 1u);
-  c->h_state[0] -= 1;
-  const uint64_t nl = c->h_state[0];
-  const bool open_end = (uint8_t)(c->h_state[1] & 0xFF) != (uint8_t)'\n';
-  const uint64_t lines = nl + (open_end ? 1u : 0u);
-  *lines_out = lines;
-  if (write && cap >= lines + 1 && open_end) {
-    // the final line has no '\n': the sentinel pretends there is one right after the input
-    c->h_state[0] = n + 1;
-    HIPCHK(hipMemcpyAsync(d_line_off + lines, c->h_state, sizeof(uint64_t), hipMemcpyHostToDevice, c->compute));
-    HIPCHK(hipStreamSynchronize(c->compute));
-  }
-  return SCFQ_OK;
-}
-
-static int index_lines_two_pass(Ctx* c, const uint8_t* base, uint64_t n, uint64_t* d_line_off, uint64_t cap, uint64_t* lines_out) {
-  int rc = scan_async(c, base, n, -1, 0, false);
-  if (rc) return rc;
-  scfq_partial p;
-  rc = end_session(c, false, &p, nullptr);      // synchronises: the newline count sizes the index
-  if (rc) return rc;
-  const uint64_t lines = p.nl + ((n > 0 && p.last_byte != (uint64_t)'\n') ? 1u : 0u);
-  *lines_out = lines;
-  if (!d_line_off || cap < lines + 1) return SCFQ_OK;   // count only / index does not fit: caller sizes and calls again
-  HIPCHK(hipMemsetAsync(d_line_off, 0, sizeof(uint64_t), c->compute));          // line 0 starts at offset 0
-  if (n) {
-    const uint64_t n_ranges = c->last_ranges;
-    if (n_ranges + 1 > c->cap_first_ord) {
-      if (c->d_first_ord) HIPCHK(hipFree(c->d_first_ord));
-      c->d_first_ord = nullptr;
-      c->cap_first_ord = 0;
-      const uint64_t want = std::max<uint64_t>(n_ranges + 1 + n_ranges / 4, 4096);
-      HIPCHK(hipMalloc(&c->d_first_ord, want * sizeof(uint64_t)));
-      c->cap_first_ord = want;
-    }
-    hipLaunchKernelGGL(scfq::fq_nl_prefix, dim3(1), dim3(1024), 0, c->compute, c->d_partials, n_ranges, (uint64_t)0, c->d_first_ord);
-    HIPCHK(hipGetLastError());
-    scfq::IndexArgs ia;
-    ia.base = base;
-    ia.n = n;
-    ia.tiles_per_range = c->last_tpr;
-    ia.n_ranges = n_ranges;
-    ia.first_ord = c->d_first_ord;
-    ia.line_off = d_line_off;
-    ia.off_base = 0;
-    const unsigned grid = (unsigned)((n_ranges + scfq::kWavesPerBlock - 1) / scfq::kWavesPerBlock);
-    hipLaunchKernelGGL(scfq::fq_index_lines, dim3(grid), dim3(64 * scfq::kWavesPerBlock), scfq::kWavesPerBlock * 2 * scfq::kTile,
-                       c->compute, ia);
-    HIPCHK(hipGetLastError());
-    if (p.last_byte != (uint64_t)'\n') {
-      // the final line has no '\n': the sentinel pretends there is one right after the input
-      c->h_state[0] = n + 1;
-      HIPCHK(hipMemcpyAsync(d_line_off + lines, c->h_state, sizeof(uint64_t), hipMemcpyHostToDevice, c->compute));
-    }
-  }
-  HIPCHK(hipStreamSynchronize(c->compute));
-  return SCFQ_OK;
-}
+}  // extern "C"
+#include "scfq_index.hpp"        // scfq_index_lines, scfq_index_lines_ex2: K5, the line index of a device-resident input
+extern "C" {
 
 // ---- diagnostic: run the host-side source selection (plain pread / BGZF parallel inflate / serial gzread) of
 // scfq_count_file without any device, writing the byte stream the scan would see into dst. Returns the byte

@@ -1,4 +1,4 @@
-// scfq_index_aux.hpp — internal: what fq-dedup (scfq_dedup.hip) asks of the line index (scfq_api.hip) beyond the offsets.
+// scfq_index_aux.hpp — internal: what fq-dedup (scfq_dedup.hip) asks of the line index (scfq_index.hpp, fq_index_kernels.hpp) beyond the offsets.
 #pragma once
 #include <cstdint>
 
@@ -21,5 +21,4 @@ struct scfq_index_aux {
 };
 
 // the index plus flags — bit 0: the input may hold "\r\n" line ends
-extern "C" int scfq_index_lines_ex(const void* dptr, uint64_t n, uint64_t* d_line_off, uint64_t cap, uint64_t* lines_out, uint32_t* flags_out);
 extern "C" int scfq_index_lines_ex2(const void* dptr, uint64_t n, uint64_t* d_line_off, uint64_t cap, uint64_t* lines_out, uint32_t* flags_out, scfq_index_aux* aux);

@@ -75,3 +75,55 @@ def test_line_index_slot_boundary(gpu, scfq):
             assert scfq.index_lines_device(ptr, a.size, small.data_ptr(), cap) == lines
             got = small.cpu().numpy().view(np.uint64)
             assert np.array_equal(got[:cap], starts[:cap]) and got[cap] == 0x5555555555555555, (k, offset, "small")
+
+
+def _index_lines_flags(scfq, ptr, n, line_off_ptr, cap):
+    """scfq_index_lines_ex2 without aux (csrc/scfq_index_aux.hpp): (lines, flag word); bit 0 = the input may hold "\\r\\n" """
+    import ctypes
+    f = scfq.lib().scfq_index_lines_ex2
+    f.restype = ctypes.c_int
+    f.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
+                  ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p]
+    lines, flags = ctypes.c_uint64(), ctypes.c_uint32(0xFFFFFFFF)
+    assert f(ctypes.c_void_p(ptr), n, ctypes.c_void_p(line_off_ptr), cap, ctypes.byref(lines), ctypes.byref(flags), None) == 0
+    return lines.value, flags.value
+
+
+def test_line_index_cr_flag(gpu, scfq):
+    """Bit 0 of the index's flag word lets fq-dedup skip its look-behind reads: it must be set whenever a '\\r' stands directly before a
+    '\\n', wherever the pair falls — inside a lane's 64 bytes, across two lanes, across two tiles, at the input's end — and clear for an
+    input without '\\r' and for an empty one, in the compact form (sparse newlines) and in the mask form (one tile with 200 newlines).
+    A '\\r' that no '\\n' follows asserts nothing (the bit may be conservative), so the inputs hold none.  Positions are the kernel's: a
+    tile is 4 KiB of ADDRESS space, byte p of it is input byte p - offset."""
+    torch = gpu
+    rng = np.random.default_rng(11)
+    n = 3 * 4096 + 100
+    cases = {                                   # kernel position of the '\r' (the '\n' follows it), None: no '\r'
+        "none": None,
+        "mid_lane": 4096 + 5 * 64 + 20,
+        "lane_end": 4096 + 7 * 64 + 63,
+        "tile_end": 2 * 4096 - 1,
+        "input_end": "end",
+    }
+    for offset in (0, 17):
+        for dense in (False, True):
+            for name, at in cases.items():
+                a = rng.integers(65, 91, n, dtype=np.uint8)
+                a[100] = 10
+                if dense:                       # 200 newlines in the kernel's tile 2: more than a compact slot holds
+                    a[2 * 4096 - offset + 1 + rng.choice(4095, size=200, replace=False)] = 10
+                if at is not None:
+                    i = n - 2 if at == "end" else at - offset
+                    a[i], a[i + 1] = 13, 10
+                t, ptr = to_dev(torch, a, offset)
+                lines, starts = expected_index(a)
+                buf = torch.full((lines + 2,), 0x5555555555555555, dtype=torch.int64, device="cuda")
+                got_lines, flags = _index_lines_flags(scfq, ptr, n, buf.data_ptr(), lines + 1)
+                got = buf.cpu().numpy().view(np.uint64)
+                assert got_lines == lines and np.array_equal(got[:lines + 1], starts), (name, offset, dense)
+                assert got[lines + 1] == 0x5555555555555555
+                assert (flags & 1) == (0 if at is None else 1), (name, offset, dense, flags)
+        t, ptr = to_dev(torch, np.zeros(0, np.uint8), offset)
+        buf = torch.full((2,), 0x5555555555555555, dtype=torch.int64, device="cuda")
+        assert _index_lines_flags(scfq, ptr, 0, buf.data_ptr(), 1) == (0, 0), offset
+        assert buf.cpu().numpy().view(np.uint64).tolist() == [0, 0x5555555555555555]
