@@ -407,6 +407,79 @@ int scfq_kmers_file(const char* path, const scfq_opts* opts, uint32_t k, uint32_
 int scfq_format_kmer_tsv(uint32_t k, uint64_t index, uint64_t count, char* buf, uint64_t cap);
 const char* scfq_kmers_error_detail(void);    /* static, thread-local */
 
+/* ---- `sc fa-gc` (FASTA group): src/fa_gc.nim, docs/fa-gc.md, sc.nim:84-96 --------------------------------------------
+ * GC content of the windows [pos - w, pos + w] around 1-based positions of a FASTA. The contract:
+ *   Lines.   A header line is a line whose first byte is '>' (a line that starts at byte 0 of the input included); every
+ *            other line is a sequence line.
+ *   Bases.   A base is a byte 0x21 .. 0x7E on a sequence line: htslib's faidx rule (isgraph), so '\r', blanks and tabs are
+ *            not bases and a CRLF file has the coordinates of its LF form.
+ *   Contigs. A contig starts at a header line; its name is the header text after '>' up to the first byte <= 0x20; its
+ *            bases are those of the sequence lines up to the next header line, numbered from 0. A name has at most 255
+ *            bytes (a longer one: SCFQ_EARG, text in scfq_fa_error_detail()). Of two contigs with one name the first is
+ *            found by name, both stay in the table. Bases before the first header line belong to no contig
+ *            (orphan_bases). Line lengths need not be uniform: for every file faidx accepts the coordinates are faidx's.
+ *            No .fai file is read or written.
+ *   Classes. gc = base in {G, C, g, c}; acgt = base in {A, C, G, T, a, c, g, t} (calc_gc, fa_gc.nim:26-27); everything
+ *            else ('N', IUPAC codes, a '>' that does not start a line) is a base in neither class.
+ * Where the reference reloads a chromosome and re-counts 2w + 1 bases per (position, window) pair, the index holds prefix
+ * tables per 4 KiB tile of the input, built in one pass, and an interval costs two tile reads whatever its length. All
+ * values are integers and exact. Limits: one device, the whole (inflated) input resident in its memory, names of at most
+ * 255 bytes; there is no CPU fallback (SCFQ_EHIP without a device), as scfq_kmers_buffer. */
+typedef struct scfq_fa_index scfq_fa_index;   /* opaque: tile tables on the device, contig table on the host */
+typedef struct scfq_fa_summary {
+  uint64_t struct_size;   /* caller sets to sizeof(scfq_fa_summary) before the call */
+  uint64_t abi_version;   /* library writes SCFQ_ABI_VERSION */
+  uint64_t input_bytes;   /* bytes scanned (inflated bytes for .gz) */
+  uint64_t tiles;
+  uint64_t contigs;
+  uint64_t bases;         /* of all sequence lines, orphan_bases included */
+  uint64_t gc_bases;
+  uint64_t acgt_bases;
+  uint64_t orphan_bases;  /* bases before the first header line */
+} scfq_fa_summary;
+typedef struct scfq_fa_contig {
+  const char* name;       /* NUL-terminated, owned by the index */
+  uint64_t name_len;
+  uint64_t header_offset; /* byte offset of the '>' */
+  uint64_t length;        /* bases */
+} scfq_fa_contig;
+typedef struct scfq_fa_interval { uint64_t contig, begin, end; } scfq_fa_interval;   /* 0-based, half-open, end <= length */
+typedef struct scfq_fa_counts { uint64_t gc, acgt, bases; } scfq_fa_counts;
+
+/* Builds the index of a FASTA in host (is_device = 0) or device memory. A host buffer is staged and the staged copy is
+ * owned by the index; a DEVICE buffer stays the caller's, is read again by every scfq_fa_count_intervals and must outlive
+ * the index (device pointers follow the scfq_set_wait_stream contract of scfq_index_lines; any alignment). sum may be
+ * NULL. SCFQ_EARG for a NULL out, a wrong sum->struct_size or a NULL ptr with n > 0; *out is NULL after every failure. */
+int scfq_fa_index_buffer(const void* ptr, uint64_t n, int is_device, scfq_fa_index** out, scfq_fa_summary* sum);
+/* Stages the whole (inflated) input with scfq_stage_file, ".gz" and BGZF by suffix as everywhere else; the index owns it. */
+int scfq_fa_index_file(const char* path, const scfq_opts* opts, scfq_fa_index** out, scfq_fa_summary* sum);
+/* Contig i in file order; SCFQ_EARG for i >= contigs. */
+int scfq_fa_contig_at(const scfq_fa_index* index, uint64_t i, scfq_fa_contig* out);
+/* The first contig named `name` (NUL-terminated); SCFQ_EARG when absent. */
+int scfq_fa_contig_find(const scfq_fa_index* index, const char* name, uint64_t* i_out);
+/* out[i] = (gc, acgt, bases) of the bases [begin, end) of contig q[i].contig; q and out are HOST arrays of nq entries, and
+ * all of them go to the device in one call. An interval with begin > end, end > length or contig >= contigs: SCFQ_EARG,
+ * the index of the first such interval in scfq_fa_error_detail(), and nothing is written. nq = 0 is valid. One call at a
+ * time per index (the index works on one stream of its own); two indexes are independent. */
+int scfq_fa_count_intervals(scfq_fa_index* index, const scfq_fa_interval* q, uint64_t nq, scfq_fa_counts* out);
+void scfq_fa_index_free(scfq_fa_index* index);   /* NULL is fine */
+const char* scfq_fa_error_detail(void);          /* static, thread-local */
+
+/* Host-only helpers of the command (no device is touched).
+ * scfq_fa_parse_window restates sci_parse_int (helpers.nim:230-237) literally: without an 'e' the commas are removed and
+ * the rest is a decimal integer ("3,200" is 3200); with an 'e' the value is pow(coeff * 10.0, exponent) truncated, so
+ * "1e3" is 1000 and "5e5" is 312500000 (50^5, not 500000), as in the reference. SCFQ_EARG for text that is neither and
+ * for a window < 1 ("Window lengths must be >= 1", fa_gc.nim:70-71), the text in scfq_fa_error_detail(). */
+int scfq_fa_parse_window(const char* text, uint64_t* window_out);
+/* The bases a window covers (sub_seq, fa_gc.nim:29-37) for a 1-based pos: pos0 = pos - 1; *out_of_range iff pos < 1 or
+ * pos0 >= length (then begin = end = 0); begin = max(0, pos0 - w), end = min(length, pos0 + w + 1). */
+int scfq_fa_gc_interval(int64_t pos, uint64_t window, uint64_t length, uint64_t* begin, uint64_t* end, int* out_of_range);
+/* The cell text: x = gc / acgt as an IEEE double, round(x * 10^d) / 10^d with C round() and d = the number of decimal
+ * digits of `window` + 2 (fa_gc.nim:54), printed as the shortest text that reads back as the same double, laid out the way
+ * Python's repr(float) does: "0.5", "1.0", "0.0", "5e-05"; "nan" for acgt = 0. Returns the number of bytes needed
+ * (excluding NUL); writes at most cap bytes incl. NUL. */
+int scfq_format_fa_gc_value(uint64_t gc, uint64_t acgt, uint64_t window, char* buf, uint64_t cap);
+
 /* Whole (inflated) input of `path` into a device buffer the caller frees with scfq_device_free(). */
 int scfq_stage_file(const char* path, const scfq_opts* opts, void** device_ptr_out, uint64_t* n_out);
 int scfq_device_free(void* device_ptr);

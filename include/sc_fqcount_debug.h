@@ -69,6 +69,10 @@ int scfq_debug_cycles_stages(double* ms, uint32_t cap);
  * copies to the host (table and summary) — [1..3] are HIP-event times, taken only while SCFQ_KMERS_TIMING=1 is in the
  * environment (zeros otherwise). Writes min(cap, 4) values, returns 4. */
 int scfq_debug_kmers_stages(double* ms, uint32_t cap);
+/* Stage times of the calling thread's last scfq_fa_index_buffer / scfq_fa_index_file, in milliseconds: ms[0] F1, the tile scan,
+ * ms[1] F2, the scan over the tile records, ms[2] F3, the contig table's kernel, ms[3] unused (0) — HIP-event times, taken only
+ * while SCFQ_FA_TIMING=1 is in the environment (zeros otherwise). Writes min(cap, 4) values, returns 4. */
+int scfq_debug_fa_stages(double* ms, uint32_t cap);
 
 #ifdef __cplusplus
 }

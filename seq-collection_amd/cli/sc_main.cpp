@@ -19,6 +19,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cctype>
 #include <condition_variable>
 #include <cstdio>
 #include <mutex>
@@ -134,6 +135,7 @@ static void help_top(FILE* f) {
                "  fq-readstats     Per-read length, N50, GC and quality of a FASTQ\n"
                "  fq-cycles        Per-position base composition and quality of a FASTQ\n"
                "  fq-kmers         K-mer spectrum of the sequence lines of a FASTQ\n\n"
+               "FASTA\n  fa-gc            Calculate GC content surrouding a location\n\n"
                "Options:\n  -h, --help                 Show this help\n  -v, --version              Show version\n"
                "      --debug                Debug mode\n",
                kVersion);
@@ -565,6 +567,226 @@ static int cmd_fq_kmers(const std::vector<std::string>& params) {
   return 0;
 }
 
+// command "fa-gc" (sc.nim:84-96, src/fa_gc.nim): --pos <chr:pos | file> <fasta> <window> [<window> ...]
+static void warning_msg(const std::string& msg) {                    // helpers.nim:36-37 (colorize fgYellow)
+  std::fprintf(stderr, "\x1b[33mWarning: %s\x1b[0m\n", msg.c_str());
+}
+
+struct FaPosition {
+  std::string chrom;
+  long long pos = 0;
+};
+
+static bool fa_parse_int(const std::string& s, long long* out) {     // Nim parseInt without the '_' separators
+  const size_t d = (!s.empty() && (s[0] == '-' || s[0] == '+')) ? 1 : 0;
+  if (s.size() == d || s.size() - d > 18 || s.find_first_not_of("0123456789", d) != std::string::npos) return false;
+  *out = std::atoll(s.c_str());
+  return true;
+}
+
+// The whole positions file; a name that ends in ".gz" goes through the library's host gzip reader.
+static bool fa_read_text(const std::string& path, std::string* out) {
+  if (path.size() >= 3 && path.compare(path.size() - 3, 3, ".gz") == 0) {
+    for (uint64_t cap = 1u << 20;; cap *= 4) {
+      out->resize(cap);
+      const int64_t got = scfq_debug_read_file(path.c_str(), &(*out)[0], cap, 0);
+      if (got >= 0) { out->resize((size_t)got); return true; }
+      if (got != SCFQ_EARG || cap > (1ull << 34)) return false;     // (SCFQ_EARG: the text does not fit into cap)
+    }
+  }
+  FILE* f = std::fopen(path.c_str(), "rb");
+  if (!f) return false;
+  out->clear();
+  char buf[1 << 16];
+  size_t got;
+  while ((got = std::fread(buf, 1, sizeof buf, f)) > 0) out->append(buf, got);
+  std::fclose(f);
+  return true;
+}
+
+// iter_pos, helpers.nim:88-151: one "chr:pos" string, or a text file with chrom and position as its first two fields
+static std::vector<FaPosition> fa_positions(const std::string& pos_in) {
+  std::vector<FaPosition> out;
+  if (pos_in.find(':') != std::string::npos && pos_in.find('/') == std::string::npos) {
+    const size_t c = pos_in.find(':');
+    FaPosition p;
+    p.chrom = pos_in.substr(0, c);
+    if (!fa_parse_int(pos_in.substr(c + 1), &p.pos)) quit_error("Invalid position: " + pos_in, 1);
+    out.push_back(p);
+    return out;
+  }
+  std::string lower = pos_in;
+  for (char& ch : lower) ch = (char)std::tolower((unsigned char)ch);
+  if (lower.size() >= 4 && lower.compare(lower.size() - 4, 4, ".bcf") == 0)
+    quit_error("BCF position files are not supported: " + pos_in + " (give chr:pos, or a text file: BED, VCF, TSV)", 1);
+  std::string text;
+  if (!fa_read_text(pos_in, &text)) quit_error("Unable to open file: " + pos_in, 2);
+  const char* seps = "\t: ";
+  size_t at = 0;
+  for (long long n = 1; at < text.size(); ++n) {
+    size_t nl = text.find('\n', at);
+    if (nl == std::string::npos) nl = text.size();
+    std::string line = text.substr(at, nl - at);
+    at = nl + 1;
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    const size_t first = line.find_first_not_of(seps), last = line.find_last_not_of(seps);
+    const std::string cur = first == std::string::npos ? "" : line.substr(first, last - first + 1);
+    const size_t e1 = cur.find_first_of(seps);
+    FaPosition p;
+    bool ok = e1 != std::string::npos;
+    if (ok) {
+      const size_t s2 = cur.find_first_not_of(seps, e1);
+      size_t e2 = cur.find_first_of(seps, s2);
+      if (e2 == std::string::npos) e2 = cur.size();
+      p.chrom = cur.substr(0, e1);
+      ok = fa_parse_int(cur.substr(s2, e2 - s2), &p.pos);
+    }
+    if (ok) out.push_back(p);
+    else if (n != 1 && (line.empty() || line[0] != '#'))
+      warning_msg("Invalid line: " + std::to_string(n) + " in \"" + pos_in + "\" > " + line);
+  }
+  return out;
+}
+
+// The order of the rows: names lower-cased and without a leading "chr"; all-digit names first, by value and then position;
+// then x, y, m, by that rank and then position; then every other name in byte order, input order kept within a name.  This
+// is genome_cmp (helpers.nim:164-193) wherever genome_cmp is a consistent order: it is not for ties among x / y / m (its
+// second branch repeats the first, so equal ranks compare as "greater" both ways) nor between one of x / y / m and another
+// non-numeric name (x < "i" by name but every x, y, m pair ignores names), where the result of its sort depends on the
+// input order.
+struct FaSortKey {
+  int group = 2;              // 0 digits, 1 x / y / m, 2 other
+  std::string name;           // digits without leading zeros / the folded name
+  int rank = 0;
+  long long pos = 0;
+};
+static FaSortKey fa_sort_key(const FaPosition& p) {
+  FaSortKey k;
+  std::string s = p.chrom;
+  for (char& ch : s) ch = (char)std::tolower((unsigned char)ch);
+  if (s.size() > 3 && s.compare(0, 3, "chr") == 0) s = s.substr(3);
+  k.name = s;
+  k.pos = p.pos;
+  if (s.find_first_not_of("0123456789") == std::string::npos) {   // (an empty name is all digits to the reference's all())
+    k.group = 0;
+    const size_t nz = s.find_first_not_of('0');
+    k.name = nz == std::string::npos ? "" : s.substr(nz);
+  } else if (s == "x" || s == "y" || s == "m") {
+    k.group = 1;
+    k.rank = s == "x" ? 1 : s == "y" ? 2 : 3;
+  }
+  return k;
+}
+static bool fa_key_less(const FaSortKey& a, const FaSortKey& b) {
+  if (a.group != b.group) return a.group < b.group;
+  if (a.group == 0) {
+    if (a.name.size() != b.name.size()) return a.name.size() < b.name.size();
+    if (a.name != b.name) return a.name < b.name;
+    return a.pos < b.pos;
+  }
+  if (a.group == 1) return a.rank != b.rank ? a.rank < b.rank : a.pos < b.pos;
+  return a.name < b.name;
+}
+
+static int cmd_fa_gc(const std::vector<std::string>& params) {
+  auto help = [](FILE* f) {
+    std::fputs("Calculate GC content surrouding a location\n\nUsage:\n  fa-gc [options] fasta [windows ...]\n\nArguments:\n"
+               "  fasta            Input FASTA (plain, .gz or BGZF)\n"
+               "  [windows ...]    sequence length up and downstream (50 --> ~100bp window [see docs])\n\nOptions:\n"
+               "  -p, --pos=POS              VCF, BED, or string position (e.g. chr1:8675309)\n"
+               "  -h, --help                 Show this help\n", f);
+  };
+  if (params.size() == 1) { help(stdout); return 0; }
+  std::string pos_in;
+  std::vector<std::string> args;
+  bool only_positional = false;
+  for (size_t i = 1; i < params.size(); ++i) {
+    const std::string& a = params[i];
+    if (only_positional || a.empty() || a[0] != '-' || a == "-") { args.push_back(a); continue; }
+    if (a == "--") { only_positional = true; continue; }
+    if (a == "-h" || a == "--help") { help(stdout); return 0; }
+    if (a == "-p" || a == "--pos") {
+      if (i + 1 >= params.size()) { help(stdout); quit_error("Error: Missing value for " + a, 1); }
+      pos_in = params[++i];
+    } else if (a.compare(0, 6, "--pos=") == 0) pos_in = a.substr(6);
+    else if (a.compare(0, 3, "-p=") == 0) pos_in = a.substr(3);
+    else { help(stdout); quit_error("Error: Unknown option: " + a, 1); }
+  }
+  if (args.empty()) { help(stdout); quit_error("Error: Missing FASTA", 1); }
+  if (pos_in.empty()) quit_error("Must provide --pos: (chr:100 / bed / vcf )", 1);
+  if (args.size() < 2) quit_error("Must provide a list of windows: (e.g. 100 200 500)", 1);
+  const std::string fasta = args[0];
+  std::vector<uint64_t> windows;
+  for (size_t i = 1; i < args.size(); ++i) {
+    uint64_t w = 0;
+    if (scfq_fa_parse_window(args[i].c_str(), &w) != SCFQ_OK) quit_error(scfq_fa_error_detail(), 1);
+    windows.push_back(w);
+  }
+  std::vector<FaPosition> positions = fa_positions(pos_in);
+  {
+    std::vector<std::pair<FaSortKey, FaPosition>> keyed;
+    for (const auto& p : positions) keyed.emplace_back(fa_sort_key(p), p);
+    std::stable_sort(keyed.begin(), keyed.end(), [](const auto& a, const auto& b) { return fa_key_less(a.first, b.first); });
+    for (size_t i = 0; i < keyed.size(); ++i) positions[i] = keyed[i].second;
+  }
+
+  scfq_fa_index* index = nullptr;
+  const int rc = scfq_fa_index_file(fasta.c_str(), nullptr, &index, nullptr);
+  if (rc == SCFQ_EOPEN) quit_error("Unable to open file: " + fasta, 2);
+  if (rc != SCFQ_OK) {
+    std::string msg = scfq_strerror(rc);
+    const char* d = *scfq_fa_error_detail() ? scfq_fa_error_detail() : scfq_last_error_detail();
+    if (d && *d) { msg += ": "; msg += d; }
+    quit_error(msg, 1);
+  }
+  std::string header = "chrom\tpos";
+  for (const uint64_t w : windows) header += "\tgc_" + std::to_string(2 * w);
+  std::printf("%s\n", header.c_str());
+
+  // every cell of the run in one call
+  std::vector<const FaPosition*> rows;
+  std::vector<scfq_fa_interval> cells;
+  for (const auto& p : positions) {
+    uint64_t c = 0;
+    scfq_fa_contig contig;
+    int out_of_range = 1;
+    uint64_t begin = 0, end = 0;
+    if (scfq_fa_contig_find(index, p.chrom.c_str(), &c) == SCFQ_OK && scfq_fa_contig_at(index, c, &contig) == SCFQ_OK)
+      scfq_fa_gc_interval(p.pos, windows[0], contig.length, &begin, &end, &out_of_range);
+    if (out_of_range) {     // (the reference dereferences nil here)
+      warning_msg("<" + p.chrom + ":" + std::to_string(p.pos) + "> is out of range");
+      continue;
+    }
+    rows.push_back(&p);
+    for (const uint64_t w : windows) {
+      scfq_fa_gc_interval(p.pos, w, contig.length, &begin, &end, &out_of_range);
+      cells.push_back(scfq_fa_interval{c, begin, end});
+    }
+  }
+  std::vector<scfq_fa_counts> counts(cells.size());
+  const int qrc = scfq_fa_count_intervals(index, cells.data(), cells.size(), counts.data());
+  if (qrc != SCFQ_OK) {
+    std::string msg = scfq_strerror(qrc);
+    const char* d = *scfq_fa_error_detail() ? scfq_fa_error_detail() : scfq_last_error_detail();
+    if (d && *d) { msg += ": "; msg += d; }
+    quit_error(msg, 1);
+  }
+  for (size_t r = 0; r < rows.size(); ++r) {
+    std::string line = rows[r]->chrom + "\t" + std::to_string(rows[r]->pos);
+    for (size_t k = 0; k < windows.size(); ++k) {
+      char cell[48];
+      const scfq_fa_counts& v = counts[r * windows.size() + k];
+      scfq_format_fa_gc_value(v.gc, v.acgt, windows[k], cell, sizeof cell);
+      line += "\t";
+      line += cell;
+    }
+    std::printf("%s\n", line.c_str());
+  }
+  std::fflush(stdout);
+  scfq_fa_index_free(index);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   scfq_debug_stage_mark("sc: main entered");
   signal(SIGPIPE, SIG_IGN);   // sc.nim:45-46
@@ -579,6 +801,7 @@ int main(int argc, char** argv) {
   if (params[0] == "fq-readstats") return cmd_fq_readstats(params);
   if (params[0] == "fq-cycles") return cmd_fq_cycles(params);
   if (params[0] == "fq-kmers") return cmd_fq_kmers(params);
+  if (params[0] == "fa-gc") return cmd_fa_gc(params);
   if (params[0] != "fq-count") {
     help_top(stdout);
     quit_error("Unknown command: " + params[0] + " (this build provides the FASTQ commands only)", 1);

@@ -49,6 +49,9 @@ EXPORTS = [
     "scfq_debug_read_stats_stages",
     "scfq_cycles_buffer", "scfq_cycles_file", "scfq_format_cycle_row_tsv", "scfq_cycles_error_detail", "scfq_debug_cycles_stages",
     "scfq_kmers_buffer", "scfq_kmers_file", "scfq_format_kmer_tsv", "scfq_kmers_error_detail", "scfq_debug_kmers_stages",
+    "scfq_fa_index_buffer", "scfq_fa_index_file", "scfq_fa_contig_at", "scfq_fa_contig_find", "scfq_fa_count_intervals",
+    "scfq_fa_index_free", "scfq_fa_error_detail", "scfq_fa_parse_window", "scfq_fa_gc_interval", "scfq_format_fa_gc_value",
+    "scfq_debug_fa_stages",
 ]
 
 
@@ -131,6 +134,27 @@ KMER_SUMMARY_FIELDS = ("struct_size", "abi_version", "reads", "lines", "input_by
 class KmerSummary(ctypes.Structure):
     """scfq_kmer_summary (fourteen uint64)"""
     _fields_ = [(n, ctypes.c_uint64) for n in KMER_SUMMARY_FIELDS]
+
+
+FA_SUMMARY_FIELDS = ("struct_size", "abi_version", "input_bytes", "tiles", "contigs", "bases", "gc_bases", "acgt_bases", "orphan_bases")
+
+
+class FaSummary(ctypes.Structure):
+    """scfq_fa_summary (nine uint64)"""
+    _fields_ = [(n, ctypes.c_uint64) for n in FA_SUMMARY_FIELDS]
+
+
+class FaContig(ctypes.Structure):
+    """scfq_fa_contig: the name is owned by the index"""
+    _fields_ = [("name", ctypes.c_char_p), ("name_len", ctypes.c_uint64), ("header_offset", ctypes.c_uint64), ("length", ctypes.c_uint64)]
+
+
+class FaInterval(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in ("contig", "begin", "end")]
+
+
+class FaCounts(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in ("gc", "acgt", "bases")]
 
 
 class SynthInfo(ctypes.Structure):
@@ -241,6 +265,19 @@ def lib():
         L.scfq_format_kmer_tsv.argtypes = [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_uint64]
         L.scfq_kmers_error_detail.restype = ctypes.c_char_p
         L.scfq_debug_kmers_stages.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]
+        L.scfq_fa_index_buffer.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, pvp, ctypes.POINTER(FaSummary)]
+        L.scfq_fa_index_file.argtypes = [ctypes.c_char_p, ctypes.c_void_p, pvp, ctypes.POINTER(FaSummary)]
+        L.scfq_fa_contig_at.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(FaContig)]
+        L.scfq_fa_contig_find.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64)]
+        L.scfq_fa_count_intervals.argtypes = [vp, vp, ctypes.c_uint64, vp]
+        L.scfq_fa_index_free.argtypes = [vp]
+        L.scfq_fa_index_free.restype = None
+        L.scfq_fa_error_detail.restype = ctypes.c_char_p
+        L.scfq_fa_parse_window.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64)]
+        L.scfq_fa_gc_interval.argtypes = [ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
+                                          ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int)]
+        L.scfq_format_fa_gc_value.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_uint64]
+        L.scfq_debug_fa_stages.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]
         _lib = L
     return _lib
 
@@ -615,6 +652,108 @@ def kmers_stages():
     return list(ms)
 
 
+def _fa_check(rc, what):
+    if rc != 0:
+        raise ScfqError(rc, what, lib().scfq_fa_error_detail().decode() or lib().scfq_last_error_detail().decode())
+
+
+class FaIndex:
+    """scfq_fa_index: the tile tables of one FASTA on the device and its contig table.  `summary` is the FaSummary of the
+    indexing call, `contigs` a list of (name, header_offset, length) in file order.  A device buffer that was indexed in
+    place stays the caller's and has to outlive the index.  close() (or the end of a `with`) frees it."""
+
+    def __init__(self, handle, summary, keep=None):
+        self._h, self.summary, self._keep = handle, summary, keep
+        self.contigs = []
+        c = FaContig()
+        for i in range(summary.contigs):
+            _fa_check(lib().scfq_fa_contig_at(self._h, i, ctypes.byref(c)), "scfq_fa_contig_at")
+            self.contigs.append((ctypes.string_at(c.name, c.name_len).decode("latin-1"), c.header_offset, c.length))
+
+    def find(self, name):
+        """index of the first contig of that name, or None"""
+        i = ctypes.c_uint64()
+        raw = name.encode("latin-1") if isinstance(name, str) else name
+        if b"\0" in raw:
+            return None
+        return i.value if lib().scfq_fa_contig_find(self._h, raw, ctypes.byref(i)) == 0 else None
+
+    def close(self):
+        if self._h:
+            lib().scfq_fa_index_free(self._h)
+        self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _fa_index_call(fn, what, keep, *head):
+    h = ctypes.c_void_p()
+    s = FaSummary()
+    s.struct_size = ctypes.sizeof(FaSummary)
+    _fa_check(fn(*head, ctypes.byref(h), ctypes.byref(s)), what)
+    return FaIndex(h, s, keep)
+
+
+def fa_index_device(dev_ptr, n):
+    """fa-gc index of a device-resident FASTA (any alignment); the buffer stays the caller's and must outlive the index"""
+    return _fa_index_call(lib().scfq_fa_index_buffer, "scfq_fa_index_buffer", None, ctypes.c_void_p(dev_ptr), n, 1)
+
+
+def fa_index_host(data):
+    """fa-gc index of a host buffer (bytes / numpy uint8): staged, the copy is owned by the index"""
+    addr, n, keep = _host_ptr(data)
+    return _fa_index_call(lib().scfq_fa_index_buffer, "scfq_fa_index_buffer", None, addr, n, 0)
+
+
+def fa_index_file(path):
+    return _fa_index_call(lib().scfq_fa_index_file, "scfq_fa_index_file", None, os.fsencode(path), None)
+
+
+def fa_count_intervals(index, intervals):
+    """intervals: (contig, begin, end) rows, 0-based and half-open (a list, or a numpy uint64 array of shape (nq, 3)).
+    Returns a numpy uint64 array of shape (nq, 3): gc, acgt, bases."""
+    import numpy as np
+    q = np.ascontiguousarray(np.asarray(intervals, dtype=np.uint64).reshape(-1, 3))
+    out = np.zeros((q.shape[0], 3), dtype=np.uint64)
+    _fa_check(lib().scfq_fa_count_intervals(index._h, q.ctypes.data if q.size else None, q.shape[0], out.ctypes.data if q.size else None),
+              "scfq_fa_count_intervals")
+    return out
+
+
+def fa_parse_window(text):
+    """sci_parse_int (helpers.nim:230-237) and the ">= 1" rule: "3,200" -> 3200, "1e3" -> 1000, "5e5" -> 312500000"""
+    w = ctypes.c_uint64()
+    _fa_check(lib().scfq_fa_parse_window(text.encode(), ctypes.byref(w)), "scfq_fa_parse_window")
+    return w.value
+
+
+def fa_gc_interval(pos, window, length):
+    """(begin, end) of the bases a window around the 1-based pos covers, or None when pos is out of range"""
+    b, e, bad = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int()
+    _fa_check(lib().scfq_fa_gc_interval(pos, window, length, ctypes.byref(b), ctypes.byref(e), ctypes.byref(bad)), "scfq_fa_gc_interval")
+    return None if bad.value else (b.value, e.value)
+
+
+def format_fa_gc_value(gc, acgt, window):
+    buf = ctypes.create_string_buffer(64)
+    _check(min(0, lib().scfq_format_fa_gc_value(gc, acgt, window, buf, 64)), "scfq_format_fa_gc_value")
+    return buf.value.decode()
+
+
+def fa_stages():
+    """(F1 tile scan, F2 record scan, F3 contig table, 0) milliseconds of this thread's last fa index call: HIP-event times,
+    zeros unless SCFQ_FA_TIMING=1 is in the environment"""
+    ms = (ctypes.c_double * 4)()
+    lib().scfq_debug_fa_stages(ms, 4)
+    return list(ms)
+
+
 SCFQ_META_WHOLE_FILE = 0x1
 
 
@@ -816,3 +955,101 @@ def fq_count(fastq, basename=False, absolute=False, out=None, flags=0, devices=N
         raise
     (out or sys.stdout).write(output_w_fnames(format_tsv(c), fastq, basename, absolute) + "\n")
     return c
+
+
+def warning_msg(msg, stream=None):
+    """src/utils/helpers.nim:36-37 (colorize fgYellow)"""
+    (stream or sys.stderr).write("\x1b[33mWarning: %s\x1b[0m\n" % msg)
+
+
+def _fa_int(text):
+    import re
+    return int(text) if re.fullmatch(r"[+-]?[0-9]{1,18}", text) else None
+
+
+def fa_positions(pos_in, err=None):
+    """iter_pos (helpers.nim:88-151): [(chrom, pos)] of one "chr:pos" string or of a text file whose first two fields are
+    chrom and position; warnings for the lines that are neither go to `err`"""
+    import re
+    if ":" in pos_in and "/" not in pos_in:
+        chrom, _, pos = pos_in.partition(":")
+        if _fa_int(pos) is None:
+            quit_error("Invalid position: " + pos_in, 1)
+        return [(chrom, _fa_int(pos))]
+    if pos_in.lower().endswith(".bcf"):
+        quit_error("BCF position files are not supported: " + pos_in + " (give chr:pos, or a text file: BED, VCF, TSV)", 1)
+    try:
+        if pos_in.endswith(".gz"):
+            import gzip
+            with gzip.open(pos_in, "rb") as f:
+                text = f.read()
+        else:
+            with open(pos_in, "rb") as f:
+                text = f.read()
+    except OSError:
+        quit_error("Unable to open file: " + pos_in, 2)
+    out = []
+    lines = text.decode("latin-1").split("\n")
+    if lines and lines[-1] == "":
+        lines.pop()
+    for n, line in enumerate(lines, 1):
+        if line.endswith("\r"):
+            line = line[:-1]
+        fields = re.split(r"[\t: ]+", line.strip("\t: "))
+        pos = _fa_int(fields[1]) if len(fields) >= 2 else None
+        if pos is not None:
+            out.append((fields[0], pos))
+        elif n != 1 and not line.startswith("#"):
+            warning_msg('Invalid line: %d in "%s" > %s' % (n, pos_in, line), err)
+    return out
+
+
+def fa_sort_key(chrom, pos):
+    """The order of fa-gc's rows (see cli/sc_main.cpp): all-digit names by value and position, then x, y, m by that rank and
+    position, then the other names; names lower-cased and without a leading "chr".  For sorted(), which is stable."""
+    s = chrom.lower()
+    if len(s) > 3 and s.startswith("chr"):
+        s = s[3:]
+    if all(c in "0123456789" for c in s):
+        return (0, int(s or "0"), "", pos)
+    if s in ("x", "y", "m"):
+        return (1, "xym".index(s), "", pos)
+    return (2, 0, s.encode("latin-1"), 0)
+
+
+def fa_gc(fasta, positions_in, windows_in, out=None, err=None):
+    """proc fa_gc*(fasta: string, positions_in: string, windows_in: seq[string])   (src/fa_gc.nim:59-100), as `sc fa-gc`
+    prints it; returns the text (and writes it to `out` when given).  Every cell goes to the device in one call."""
+    windows = []
+    for w in windows_in:
+        try:
+            windows.append(fa_parse_window(w))
+        except ScfqError as e:
+            quit_error(lib().scfq_fa_error_detail().decode() or str(e), 1)
+    positions = sorted(fa_positions(positions_in, err), key=lambda p: fa_sort_key(*p))
+    try:
+        index = fa_index_file(fasta)
+    except ScfqError as e:
+        if e.rc == SCFQ_EOPEN:
+            quit_error("Unable to open file: " + fasta, 2)
+        raise
+    with index:
+        text = ["\t".join(["chrom", "pos"] + ["gc_%d" % (2 * w) for w in windows])]
+        rows, cells = [], []
+        for chrom, pos in positions:
+            c = index.find(chrom)
+            spans = None if c is None else [fa_gc_interval(pos, w, index.contigs[c][2]) for w in windows]
+            if spans is None or spans[0] is None:
+                warning_msg("<%s:%d> is out of range" % (chrom, pos), err)
+                continue
+            rows.append((chrom, pos))
+            cells += [(c, b, e) for b, e in spans]
+        counts = fa_count_intervals(index, cells)
+    for r, (chrom, pos) in enumerate(rows):
+        vals = [format_fa_gc_value(int(counts[r * len(windows) + k][0]), int(counts[r * len(windows) + k][1]), w)
+                for k, w in enumerate(windows)]
+        text.append("\t".join([chrom, str(pos)] + vals))
+    text = "\n".join(text) + "\n"
+    if out is not None:
+        out.write(text)
+    return text
