@@ -407,6 +407,66 @@ int scfq_kmers_file(const char* path, const scfq_opts* opts, uint32_t k, uint32_
 int scfq_format_kmer_tsv(uint32_t k, uint64_t index, uint64_t count, char* buf, uint64_t cap);
 const char* scfq_kmers_error_detail(void);    /* static, thread-local */
 
+/* ---- `sc fq-adapters` (addition; not in the reference): adapter content by read position --------------------------------
+ * Lines and records are those of fq-readstats above. A probe is 1 .. SCFQ_ADAPTERS_MAX_LEN letters, each exactly 'A',
+ * 'C', 'G' or 'T'; a call takes 1 .. SCFQ_ADAPTERS_MAX_PROBES of them. Probe j of length m occurs at 0-based position p of
+ * sequence line 4i+1 when the m text bytes from p are all inside that line's text and equal the probe byte for byte
+ * (case-sensitive, as everywhere else; occurrences may overlap). A probe never occurs in a header, separator or quality
+ * line, whatever those hold. hits[j] counts all occurrences of probe j; first(i, j) is the smallest position at which probe
+ * j occurs in read i, or none; any(i) is the minimum of first(i, j) over the probes, or none. All values are integers and
+ * exact. Device pipeline over the HBM-resident input: line index (K5), A1 — the matching kernel, partitioned by BYTES as
+ * M1 of fq-kmers, with a 32-bit atomic minimum per (read, probe) —, A2, a pass over the reads that counts the first
+ * positions into rows, and A3, their sum. Positions are kept in 32 bits: a sequence line of 2^32 - 1 bytes or more returns
+ * SCFQ_EARG (text in scfq_adapters_error_detail()), nothing wraps. */
+#define SCFQ_ADAPTERS_MAX_PROBES 8
+#define SCFQ_ADAPTERS_MAX_LEN    32
+#define SCFQ_ADAPTERS_MAX_CAP    (1ull << 24)
+typedef struct scfq_adapter_row {                 /* 72 bytes */
+  uint64_t first[SCFQ_ADAPTERS_MAX_PROBES];       /* reads whose first occurrence of probe j starts here */
+  uint64_t any;                                   /* reads whose earliest occurrence of any probe starts here */
+} scfq_adapter_row;
+
+typedef struct scfq_adapter_summary {             /* 42 x 8 bytes */
+  uint64_t struct_size;   /* caller sets to sizeof(scfq_adapter_summary) before the call */
+  uint64_t abi_version;   /* library writes SCFQ_ABI_VERSION */
+  uint64_t reads;         /* ceil(lines / 4) */
+  uint64_t lines;
+  uint64_t input_bytes;   /* bytes scanned (inflated bytes for .gz) */
+  uint64_t n_probes;
+  uint64_t max_seq_len;   /* longest text of a line 4i+1; 0 without one */
+  uint64_t positions;     /* rows written: min(cap, max_seq_len) */
+  uint64_t probe_len[SCFQ_ADAPTERS_MAX_PROBES];
+  uint64_t hits[SCFQ_ADAPTERS_MAX_PROBES];
+  scfq_adapter_row tail;  /* first occurrences at positions >= cap, added up */
+  scfq_adapter_row total; /* every position added up: total.first[j] = reads that hold probe j, total.any = reads that hold one */
+} scfq_adapter_summary;
+
+/* Input in host (is_device = 0) or device memory. probes: n_probes NUL-terminated strings. rows_host: HOST memory for
+ * `cap` rows (may be NULL when cap is 0); rows [0, positions) are written, every field, rows [positions, cap) are not
+ * touched. cap = 0 is the sizing call: everything lands in tail, read max_seq_len and call again. total, hits, reads,
+ * lines, input_bytes, max_seq_len and probe_len do not depend on cap, and rows[p] is the same for every cap > p. Slots
+ * j >= n_probes are 0 everywhere. The same probe given twice is allowed: both columns are equal. SCFQ_EARG with text in
+ * scfq_adapters_error_detail(): n_probes of 0 or above SCFQ_ADAPTERS_MAX_PROBES, a NULL or empty probe, a probe longer
+ * than SCFQ_ADAPTERS_MAX_LEN, a probe byte that is not A C G T, cap above SCFQ_ADAPTERS_MAX_CAP, a sequence line too long
+ * for 32-bit positions; SCFQ_EARG also for a NULL out or a wrong struct_size, NULL ptr with n > 0, NULL rows_host with
+ * cap > 0, NULL probes. Device pointers follow the scfq_set_wait_stream contract of scfq_index_lines. One device, the
+ * whole input resident, fewer than 2^31 records, as scfq_kmers_buffer; there is no CPU fallback (SCFQ_EHIP without a
+ * device). */
+int scfq_adapters_buffer(const void* ptr, uint64_t n, int is_device, const char* const* probes, uint32_t n_probes,
+                         scfq_adapter_row* rows_host, uint64_t cap, scfq_adapter_summary* out);
+/* Stages the whole (inflated) input with scfq_stage_file, ".gz" and BGZF by suffix as everywhere else. */
+int scfq_adapters_file(const char* path, const scfq_opts* opts, const char* const* probes, uint32_t n_probes,
+                       scfq_adapter_row* rows_host, uint64_t cap, scfq_adapter_summary* out);
+/* Entry i of the built-in set (the 12-mers the common QC tools look for): *name and *seq point to static strings (either
+ * may be NULL). Returns the size of the set; SCFQ_EARG for i beyond it. */
+int scfq_adapters_default(uint32_t i, const char** name, const char** seq);
+/* n_probes + 1 tab-separated fields (first[0 .. n_probes), any) without trailing newline: with counts != 0 the integers of
+ * r, otherwise 100 * r->x / reads as IEEE doubles printed by the rule of scfq_format_tsv ("nan" for 0/0). Returns the
+ * number of bytes needed (excluding NUL); writes at most cap bytes incl. NUL, as scfq_format_cycle_row_tsv. SCFQ_EARG for
+ * a NULL r, n_probes of 0 or above SCFQ_ADAPTERS_MAX_PROBES. */
+int scfq_format_adapter_row_tsv(const scfq_adapter_row* r, uint32_t n_probes, uint64_t reads, int counts, char* buf, uint64_t cap);
+const char* scfq_adapters_error_detail(void); /* static, thread-local */
+
 /* ---- `sc fa-gc` (FASTA group): src/fa_gc.nim, docs/fa-gc.md, sc.nim:84-96 --------------------------------------------
  * GC content of the windows [pos - w, pos + w] around 1-based positions of a FASTA. The contract:
  *   Lines.   A header line is a line whose first byte is '>' (a line that starts at byte 0 of the input included); every

@@ -69,6 +69,11 @@ int scfq_debug_cycles_stages(double* ms, uint32_t cap);
  * copies to the host (table and summary) — [1..3] are HIP-event times, taken only while SCFQ_KMERS_TIMING=1 is in the
  * environment (zeros otherwise). Writes min(cap, 4) values, returns 4. */
 int scfq_debug_kmers_stages(double* ms, uint32_t cap);
+/* Stage times of the calling thread's last scfq_adapters_buffer / scfq_adapters_file, in milliseconds: ms[0] line index (host
+ * clock around the synchronous index call), ms[1] A1, the matching kernel, ms[2] A2, first positions into rows, ms[3] A3, the
+ * sum of the rows (without the copies to the host) — [1..3] are HIP-event times, taken only while SCFQ_ADAPTERS_TIMING=1 is in
+ * the environment (zeros otherwise). Writes min(cap, 4) values, returns 4. */
+int scfq_debug_adapters_stages(double* ms, uint32_t cap);
 /* Stage times of the calling thread's last scfq_fa_index_buffer / scfq_fa_index_file, in milliseconds: ms[0] F1, the tile scan,
  * ms[1] F2, the scan over the tile records, ms[2] F3, the contig table's kernel, ms[3] unused (0) — HIP-event times, taken only
  * while SCFQ_FA_TIMING=1 is in the environment (zeros otherwise). Writes min(cap, 4) values, returns 4. */

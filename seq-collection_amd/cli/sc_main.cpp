@@ -134,7 +134,8 @@ static void help_top(FILE* f) {
                "  fq-dedup         Removes exact duplicates from FASTQ Files\n  fq-meta          Output metadata for FASTQ\n"
                "  fq-readstats     Per-read length, N50, GC and quality of a FASTQ\n"
                "  fq-cycles        Per-position base composition and quality of a FASTQ\n"
-               "  fq-kmers         K-mer spectrum of the sequence lines of a FASTQ\n\n"
+               "  fq-kmers         K-mer spectrum of the sequence lines of a FASTQ\n"
+               "  fq-adapters      Adapter content by read position of a FASTQ\n\n"
                "FASTA\n  fa-gc            Calculate GC content surrouding a location\n\n"
                "Options:\n  -h, --help                 Show this help\n  -v, --version              Show version\n"
                "      --debug                Debug mode\n",
@@ -567,6 +568,135 @@ static int cmd_fq_kmers(const std::vector<std::string>& params) {
   return 0;
 }
 
+// command "fq-adapters" (addition, not in the reference): -t/--header, -b/--basename, -a/--absolute as fq-count, --adapter=NAME:SEQ,
+// --max-positions=N, --counts, --totals, [fastq ...]
+static const char* kAdaptersTotalsHeader = "adapter\tsequence\treads\treads_with\tpercent\thits";
+static int cmd_fq_adapters(const std::vector<std::string>& params) {
+  auto help = [](FILE* f) {
+    std::fputs("Adapter content by read position of a FASTQ\n\nUsage:\n  fq-adapters [options] [fastq ...]\n\nArguments:\n"
+               "  [fastq ...]      Input FASTQ\n\nOptions:\n  -t, --header               Output the header\n"
+               "  -b, --basename             Add basename column\n  -a, --absolute             Add column for absolute path\n"
+               "      --adapter=NAME:SEQ     Look for SEQ (1 .. 32 letters of A C G T) and call it NAME; up to eight, and giving any\n"
+               "                             replaces the built-in set (Illumina universal and small RNA, Nextera, SOLiD, poly-A, poly-G)\n"
+               "      --max-positions=N      One row per position up to N (default: 1000, at most 16777216); what lies beyond\n"
+               "                             comes as one last row \">N\"\n"
+               "      --counts               The reads whose first occurrence starts at the position, as integers (default: the\n"
+               "                             percentage of the reads in which it starts at or before the position); the \">N\" row\n"
+               "                             then holds the reads whose first occurrence starts beyond N\n"
+               "      --totals               One row per adapter and file instead: adapter sequence reads reads_with percent hits,\n"
+               "                             and a row \"any\"\n"
+               "  -h, --help                 Show this help\n", f);
+  };
+  if (params.size() == 1) { help(stdout); return 0; }
+  bool header = false, basename = false, absolute = false, only_positional = false, counts = false, totals = false;
+  uint64_t max_positions = 1000;
+  std::vector<std::string> files, names, seqs;
+  for (size_t i = 1; i < params.size(); ++i) {
+    const std::string& a = params[i];
+    if (only_positional || a.empty() || a[0] != '-' || a == "-") { files.push_back(a); continue; }
+    if (a == "--") { only_positional = true; continue; }
+    if (a == "-h" || a == "--help") { help(stdout); return 0; }
+    if (a == "--header") header = true;
+    else if (a == "--basename") basename = true;
+    else if (a == "--absolute") absolute = true;
+    else if (a == "--counts") counts = true;
+    else if (a == "--totals") totals = true;
+    else if (a.compare(0, 16, "--max-positions=") == 0) {
+      const std::string v = a.substr(16);
+      const bool digits = !v.empty() && v.size() <= 8 && v.find_first_not_of("0123456789") == std::string::npos;
+      if (!digits || std::stoull(v) > SCFQ_ADAPTERS_MAX_CAP) { help(stdout); quit_error("Error: Bad value for --max-positions: " + v, 1); }
+      max_positions = std::stoull(v);
+    } else if (a.compare(0, 10, "--adapter=") == 0) {
+      const std::string v = a.substr(10);
+      const size_t colon = v.find(':');
+      const std::string name = colon == std::string::npos ? "" : v.substr(0, colon), seq = colon == std::string::npos ? "" : v.substr(colon + 1);
+      if (name.empty() || name.find('\t') != std::string::npos || seq.empty() || seq.size() > SCFQ_ADAPTERS_MAX_LEN ||
+          seq.find_first_not_of("ACGT") != std::string::npos || names.size() >= SCFQ_ADAPTERS_MAX_PROBES) {
+        help(stdout);
+        quit_error("Error: Bad value for --adapter: " + v, 1);
+      }
+      names.push_back(name);
+      seqs.push_back(seq);
+    } else if (a.size() >= 2 && a[1] != '-') {
+      for (size_t k = 1; k < a.size(); ++k) {
+        if (a[k] == 't') header = true;
+        else if (a[k] == 'b') basename = true;
+        else if (a[k] == 'a') absolute = true;
+        else if (a[k] == 'h') { help(stdout); return 0; }
+        else { help(stdout); quit_error(std::string("Error: Unknown option: -") + a[k], 1); }
+      }
+    } else {
+      help(stdout);
+      quit_error("Error: Unknown option: " + a, 1);
+    }
+  }
+  if (names.empty()) {
+    const char *name = nullptr, *seq = nullptr;
+    for (uint32_t i = 0; scfq_adapters_default(i, &name, &seq) > 0; ++i) { names.push_back(name); seqs.push_back(seq); }
+  }
+  const uint32_t np = (uint32_t)names.size();
+  std::vector<const char*> probes;
+  for (const auto& s : seqs) probes.push_back(s.c_str());
+  if (header) {
+    std::string h = "position";
+    for (const auto& nm : names) h += "\t" + nm;
+    std::printf("%s\n", output_header(totals ? std::string(kAdaptersTotalsHeader) : h + "\tany", basename, absolute).c_str());
+  } else if (files.empty()) quit_error("No FASTQ specified", 3);
+  std::vector<scfq_adapter_row> rows;
+  for (const auto& fastq : files) {
+    if (fastq.size() < 3) quit_error("index out of bounds", 1);
+    scfq_adapter_summary s;
+    int rc = SCFQ_OK;
+    // the sizing call first: the table is as long as the file's longest sequence line, not as --max-positions
+    for (int pass = 0; pass < 2 && rc == SCFQ_OK; ++pass) {
+      std::memset(&s, 0, sizeof s);
+      s.struct_size = sizeof s;
+      rc = scfq_adapters_file(fastq.c_str(), nullptr, probes.data(), np, rows.empty() ? nullptr : rows.data(), rows.size(), &s);
+      if (pass == 1 || rc != SCFQ_OK || totals) break;
+      rows.assign((size_t)std::min<uint64_t>(max_positions, s.max_seq_len), scfq_adapter_row());
+      if (rows.empty()) break;
+    }
+    if (rc == SCFQ_EOPEN) quit_error("Unable to open file: " + fastq, fastq.compare(fastq.size() - 3, 3, ".gz") == 0 ? 1 : 2);   // as fq-count
+    if (rc != SCFQ_OK) {
+      std::string msg = scfq_strerror(rc);
+      const char* d = *scfq_adapters_error_detail() ? scfq_adapters_error_detail() : scfq_last_error_detail();
+      if (d && *d) { msg += ": "; msg += d; }
+      quit_error(msg, 1);
+    }
+    char row[1024];
+    if (totals) {
+      uint64_t hits = 0;
+      for (uint32_t j = 0; j <= np; ++j) {
+        const uint64_t with = j < np ? s.total.first[j] : s.total.any;
+        const std::string line = (j < np ? names[j] + "\t" + seqs[j] : std::string("any\t*")) + "\t" + std::to_string(s.reads) + "\t" +
+                                 std::to_string(with) + "\t" + nim_float(100.0 * (double)with / (double)s.reads) + "\t" +
+                                 std::to_string(j < np ? s.hits[j] : hits);
+        if (j < np) hits += s.hits[j];
+        std::printf("%s\n", output_w_fnames(line, fastq, basename, absolute).c_str());
+      }
+      continue;
+    }
+    // the rows as they are with --counts; added up from position 1 otherwise
+    scfq_adapter_row acc;
+    std::memset(&acc, 0, sizeof acc);
+    for (uint64_t p = 0; p < s.positions; ++p) {
+      for (uint32_t j = 0; j < np; ++j) acc.first[j] += rows[p].first[j];
+      acc.any += rows[p].any;
+      scfq_format_adapter_row_tsv(counts ? &rows[p] : &acc, np, s.reads, counts, row, sizeof row);
+      std::printf("%s\n", output_w_fnames(std::to_string(p + 1) + "\t" + row, fastq, basename, absolute).c_str());
+    }
+    bool tail = s.tail.any != 0;
+    for (uint32_t j = 0; j < np; ++j) tail = tail || s.tail.first[j] != 0;
+    if (tail) {
+      scfq_format_adapter_row_tsv(counts ? &s.tail : &s.total, np, s.reads, counts, row, sizeof row);
+      std::printf("%s\n", output_w_fnames(">" + std::to_string(max_positions) + "\t" + row, fastq, basename, absolute).c_str());
+    }
+    rows.clear();
+  }
+  std::fflush(stdout);
+  return 0;
+}
+
 // command "fa-gc" (sc.nim:84-96, src/fa_gc.nim): --pos <chr:pos | file> <fasta> <window> [<window> ...]
 static void warning_msg(const std::string& msg) {                    // helpers.nim:36-37 (colorize fgYellow)
   std::fprintf(stderr, "\x1b[33mWarning: %s\x1b[0m\n", msg.c_str());
@@ -801,6 +931,7 @@ int main(int argc, char** argv) {
   if (params[0] == "fq-readstats") return cmd_fq_readstats(params);
   if (params[0] == "fq-cycles") return cmd_fq_cycles(params);
   if (params[0] == "fq-kmers") return cmd_fq_kmers(params);
+  if (params[0] == "fq-adapters") return cmd_fq_adapters(params);
   if (params[0] == "fa-gc") return cmd_fa_gc(params);
   if (params[0] != "fq-count") {
     help_top(stdout);

@@ -160,6 +160,39 @@ int scfq_format_kmer_tsv(uint32_t k, uint64_t index, uint64_t count, char* buf, 
   return m;
 }
 
+// the built-in probes of fq-adapters: the names and 12-mers the common QC tools use
+int scfq_adapters_default(uint32_t i, const char** name, const char** seq) {
+  static const char* const kSet[][2] = {
+      {"illumina_universal", "AGATCGGAAGAG"}, {"illumina_small_rna_3p", "TGGAATTCTCGG"}, {"illumina_small_rna_5p", "GATCGTCGGACT"},
+      {"nextera", "CTGTCTCTTATA"},            {"polya", "AAAAAAAAAAAA"},                 {"polyg", "GGGGGGGGGGGG"},
+      {"solid_small_rna", "CGCCTTGGCCGT"}};
+  const uint32_t size = sizeof kSet / sizeof kSet[0];
+  if (i >= size) return SCFQ_EARG;
+  if (name) *name = kSet[i][0];
+  if (seq) *seq = kSet[i][1];
+  return (int)size;
+}
+
+// the fq-adapters row: the integers, or their share of `reads` in percent by the same `$float` rule
+int scfq_format_adapter_row_tsv(const scfq_adapter_row* r, uint32_t n_probes, uint64_t reads, int counts, char* buf, uint64_t cap) {
+  if (!r || n_probes < 1 || n_probes > SCFQ_ADAPTERS_MAX_PROBES) return SCFQ_EARG;
+  char tmp[(SCFQ_ADAPTERS_MAX_PROBES + 1) * 100];
+  int m = 0;
+  for (uint32_t j = 0; j <= n_probes; ++j) {
+    const uint64_t v = j < n_probes ? r->first[j] : r->any;
+    if (j) tmp[m++] = '\t';
+    if (counts) m += std::snprintf(tmp + m, sizeof tmp - m, "%llu", (unsigned long long)v);
+    else m += nim_float_to_str(100.0 * (double)v / (double)reads, tmp + m, 96);
+  }
+  tmp[m] = 0;
+  if (buf && cap) {
+    const uint64_t ncopy = ((uint64_t)m < cap - 1) ? (uint64_t)m : cap - 1;
+    std::memcpy(buf, tmp, ncopy);
+    buf[ncopy] = 0;
+  }
+  return m;
+}
+
 const char* scfq_strerror(int rc) {
   switch (rc) {
     case SCFQ_OK: return "ok";

@@ -49,6 +49,8 @@ EXPORTS = [
     "scfq_debug_read_stats_stages",
     "scfq_cycles_buffer", "scfq_cycles_file", "scfq_format_cycle_row_tsv", "scfq_cycles_error_detail", "scfq_debug_cycles_stages",
     "scfq_kmers_buffer", "scfq_kmers_file", "scfq_format_kmer_tsv", "scfq_kmers_error_detail", "scfq_debug_kmers_stages",
+    "scfq_adapters_buffer", "scfq_adapters_file", "scfq_adapters_default", "scfq_format_adapter_row_tsv", "scfq_adapters_error_detail",
+    "scfq_debug_adapters_stages",
     "scfq_fa_index_buffer", "scfq_fa_index_file", "scfq_fa_contig_at", "scfq_fa_contig_find", "scfq_fa_count_intervals",
     "scfq_fa_index_free", "scfq_fa_error_detail", "scfq_fa_parse_window", "scfq_fa_gc_interval", "scfq_format_fa_gc_value",
     "scfq_debug_fa_stages",
@@ -134,6 +136,24 @@ KMER_SUMMARY_FIELDS = ("struct_size", "abi_version", "reads", "lines", "input_by
 class KmerSummary(ctypes.Structure):
     """scfq_kmer_summary (fourteen uint64)"""
     _fields_ = [(n, ctypes.c_uint64) for n in KMER_SUMMARY_FIELDS]
+
+
+ADAPTERS_MAX_PROBES = 8
+ADAPTERS_MAX_LEN = 32
+ADAPTERS_MAX_CAP = 1 << 24
+ADAPTER_SUMMARY_HEAD = ("struct_size", "abi_version", "reads", "lines", "input_bytes", "n_probes", "max_seq_len", "positions")
+
+
+class AdapterRow(ctypes.Structure):
+    """scfq_adapter_row: one position of the fq-adapters table (nine uint64: first[8], any)"""
+    _fields_ = [("first", ctypes.c_uint64 * ADAPTERS_MAX_PROBES), ("any", ctypes.c_uint64)]
+
+
+class AdapterSummary(ctypes.Structure):
+    """scfq_adapter_summary (42 uint64)"""
+    _fields_ = [(n, ctypes.c_uint64) for n in ADAPTER_SUMMARY_HEAD] + \
+               [("probe_len", ctypes.c_uint64 * ADAPTERS_MAX_PROBES), ("hits", ctypes.c_uint64 * ADAPTERS_MAX_PROBES),
+                ("tail", AdapterRow), ("total", AdapterRow)]
 
 
 FA_SUMMARY_FIELDS = ("struct_size", "abi_version", "input_bytes", "tiles", "contigs", "bases", "gc_bases", "acgt_bases", "orphan_bases")
@@ -265,6 +285,15 @@ def lib():
         L.scfq_format_kmer_tsv.argtypes = [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_uint64]
         L.scfq_kmers_error_detail.restype = ctypes.c_char_p
         L.scfq_debug_kmers_stages.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]
+        L.scfq_adapters_buffer.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.c_uint32,
+                                           ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(AdapterSummary)]
+        L.scfq_adapters_file.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_char_p), ctypes.c_uint32, ctypes.c_void_p,
+                                         ctypes.c_uint64, ctypes.POINTER(AdapterSummary)]
+        L.scfq_adapters_default.argtypes = [ctypes.c_uint32, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_char_p)]
+        L.scfq_format_adapter_row_tsv.argtypes = [ctypes.POINTER(AdapterRow), ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int, ctypes.c_char_p,
+                                                  ctypes.c_uint64]
+        L.scfq_adapters_error_detail.restype = ctypes.c_char_p
+        L.scfq_debug_adapters_stages.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]
         L.scfq_fa_index_buffer.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, pvp, ctypes.POINTER(FaSummary)]
         L.scfq_fa_index_file.argtypes = [ctypes.c_char_p, ctypes.c_void_p, pvp, ctypes.POINTER(FaSummary)]
         L.scfq_fa_contig_at.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(FaContig)]
@@ -649,6 +678,80 @@ def kmers_stages():
     HIP-event times and zeros unless SCFQ_KMERS_TIMING=1 is in the environment"""
     ms = (ctypes.c_double * 4)()
     lib().scfq_debug_kmers_stages(ms, 4)
+    return list(ms)
+
+
+def _new_adapter_summary():
+    s = AdapterSummary()
+    s.struct_size = ctypes.sizeof(AdapterSummary)
+    return s
+
+
+def adapters_default():
+    """the built-in probes as a list of (name, sequence)"""
+    out, i = [], 0
+    name, seq = ctypes.c_char_p(), ctypes.c_char_p()
+    while lib().scfq_adapters_default(i, ctypes.byref(name), ctypes.byref(seq)) > 0:
+        out.append((name.value.decode(), seq.value.decode()))
+        i += 1
+    return out
+
+
+def _probe_array(probes):
+    """probes: None (the built-in set) or a sequence of str / bytes"""
+    if probes is None:
+        probes = [seq for _, seq in adapters_default()]
+    enc = [p.encode() if isinstance(p, str) else p for p in probes]
+    return (ctypes.c_char_p * max(len(enc), 1))(*enc), len(enc)
+
+
+def _adapters_call(fn, what, probes, cap, *head):
+    """cap: the number of rows, or a caller's uint64 array of shape (cap, 9), filled in place ([positions, cap) untouched)"""
+    import numpy as np
+    if isinstance(cap, np.ndarray):
+        buf = cap
+        assert buf.dtype == np.uint64 and buf.ndim == 2 and buf.shape[1] == 9 and buf.flags.c_contiguous
+    else:
+        buf = np.zeros((cap, 9), dtype=np.uint64)
+    arr, n_probes = _probe_array(probes)
+    s = _new_adapter_summary()
+    rc = fn(*head, arr, n_probes, ctypes.c_void_p(buf.ctypes.data) if buf.shape[0] else None, buf.shape[0], ctypes.byref(s))
+    if rc != 0:
+        raise ScfqError(rc, what, lib().scfq_adapters_error_detail().decode() or lib().scfq_last_error_detail().decode())
+    return s, (buf[:s.positions] if buf.shape[0] else None)
+
+
+def adapters_device(dev_ptr, n, probes=None, cap=0):
+    """fq-adapters of a device-resident FASTQ, at most `cap` positions (0: the sizing call; read max_seq_len).  probes: None for the
+    built-in set.  Returns (AdapterSummary, rows as a uint64 array of shape (positions, 9): first[0 .. 8) and any; None for cap 0)."""
+    return _adapters_call(lib().scfq_adapters_buffer, "scfq_adapters_buffer", probes, cap, ctypes.c_void_p(dev_ptr), n, 1)
+
+
+def adapters_host(data, probes=None, cap=0):
+    """fq-adapters of a host buffer (bytes / numpy uint8)"""
+    addr, n, keep = _host_ptr(data)
+    return _adapters_call(lib().scfq_adapters_buffer, "scfq_adapters_buffer", probes, cap, addr, n, 0)
+
+
+def adapters_file(path, probes=None, cap=0):
+    return _adapters_call(lib().scfq_adapters_file, "scfq_adapters_file", probes, cap, os.fsencode(path), None)
+
+
+def format_adapter_row_tsv(row, n_probes, reads, counts=False):
+    """row: an AdapterRow or nine integers (first[0 .. 8), any)"""
+    if not isinstance(row, AdapterRow):
+        v = [int(x) for x in row]
+        row = AdapterRow((ctypes.c_uint64 * ADAPTERS_MAX_PROBES)(*v[:8]), v[8])
+    buf = ctypes.create_string_buffer(1024)
+    _check(min(0, lib().scfq_format_adapter_row_tsv(ctypes.byref(row), n_probes, reads, 1 if counts else 0, buf, 1024)), "scfq_format_adapter_row_tsv")
+    return buf.value.decode()
+
+
+def adapters_stages():
+    """(index, matching kernel, rows, finish) milliseconds of this thread's last adapters call; the last three are HIP-event times
+    and zeros unless SCFQ_ADAPTERS_TIMING=1 is in the environment"""
+    ms = (ctypes.c_double * 4)()
+    lib().scfq_debug_adapters_stages(ms, 4)
     return list(ms)
 
 
