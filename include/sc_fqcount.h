@@ -467,6 +467,84 @@ int scfq_adapters_default(uint32_t i, const char** name, const char** seq);
 int scfq_format_adapter_row_tsv(const scfq_adapter_row* r, uint32_t n_probes, uint64_t reads, int counts, char* buf, uint64_t cap);
 const char* scfq_adapters_error_detail(void); /* static, thread-local */
 
+/* ---- `sc fq-insert-size` (addition; the reference reads insert sizes from an aligned BAM): read-pair overlap -------------
+ * Inputs are two FASTQs, record i of each being pair i (pairs = min(reads1, reads2), unpaired = |reads1 - reads2|), or one
+ * interleaved FASTQ, records 2i and 2i+1 being pair i (pairs = reads / 2, unpaired = reads & 1). Lines, records and line
+ * ends are those of fq-readstats above: reads = ceil(lines / 4), a '\r' before a real '\n' is stripped, a sequence line the
+ * input does not have is a text of length 0.
+ * For pair i let A be the text of mate 1's sequence line (length La), B that of mate 2's (length Lb) and
+ * C[y] = comp(B[Lb-1-y]), comp exchanging 'A' <-> 'T' and 'C' <-> 'G': the reverse complement of mate 2. A byte that is not
+ * exactly one of A C G T never agrees with anything (case-sensitive, as everywhere else). For an offset d in
+ * [-(Lb-1), La-1], C[y] faces A[y+d]: the overlap is the y in [max(0,-d), min(Lb, La-d)), ov(d) its size, mm(d) the number
+ * of overlap positions at which A[y+d] and C[y] do not agree, and insert(d) = d + Lb, in 1 .. La+Lb-1 (d < 0: the mates
+ * read through the insert into the adapters). An offset is accepted iff ov(d) >= min_overlap, mm(d) <= max_mismatches and
+ * 100 * mm(d) <= max_mismatch_pct * ov(d). The pair's offset d* is the accepted offset with the largest ov; ties go to the
+ * smallest mm, then to the largest d. Defaults 30 / 5 / 20; allowed min_overlap 1 .. 512, max_mismatches 0 .. 65535,
+ * max_mismatch_pct 0 .. 100 (anything else: SCFQ_EARG, text in scfq_insert_size_error_detail()). A pair with La or Lb above
+ * SCFQ_INSERT_MAX_LEN counts in too_long and is not analysed; of such a line only the bytes that tell its length are read.
+ * The method sees inserts up to La + Lb - min_overlap only: a longer fragment's mates do not overlap (not_overlapped).
+ * All values are integers and exact. Device pipeline over the HBM-resident inputs: line index (K5) of each, P1 — a wave per
+ * pair: both reads as bit planes (two code bits and a valid bit per base, 64 bases per word), a lane per offset, shifts and
+ * population counts, one packed-key minimum per wave; histogram in 32-bit LDS counters per block, flushed to 64-bit global
+ * ones — and P2, a pass over the bins for min, max, mode and median. */
+#define SCFQ_INSERT_MAX_LEN     512
+#define SCFQ_INSERT_HIST_BINS   1024
+#define SCFQ_INSERT_INTERLEAVED 0x1u
+typedef struct scfq_overlap_rec {   /* 8 bytes; {0, 0, 0}: no accepted offset; {0, 0, 0xFFFF}: a too-long pair */
+  int32_t  offset;                  /* d* */
+  uint16_t overlap;                 /* ov(d*) */
+  uint16_t mismatches;              /* mm(d*) */
+} scfq_overlap_rec;
+
+typedef struct scfq_insert_opts {
+  uint64_t struct_size;             /* sizeof(scfq_insert_opts) */
+  uint32_t flags;                   /* SCFQ_INSERT_INTERLEAVED */
+  uint32_t min_overlap;
+  uint32_t max_mismatches;
+  uint32_t max_mismatch_pct;
+} scfq_insert_opts;
+
+typedef struct scfq_insert_summary {   /* 25 x 8 bytes */
+  uint64_t struct_size;   /* caller sets to sizeof(scfq_insert_summary) before the call */
+  uint64_t abi_version;   /* library writes SCFQ_ABI_VERSION */
+  uint64_t reads1, reads2;             /* ceil(lines / 4) of each input (reads2 = lines2 = input_bytes2 = 0 for interleaved input) */
+  uint64_t lines1, lines2;
+  uint64_t input_bytes1, input_bytes2; /* bytes scanned (inflated bytes for .gz) */
+  uint64_t pairs, unpaired;
+  uint64_t overlapped, not_overlapped, too_long;   /* pairs = overlapped + not_overlapped + too_long */
+  uint64_t read_through;               /* overlapped pairs with insert < max(La, Lb) */
+  uint64_t overlap_bases, mismatches;  /* sums of ov(d*) and mm(d*) */
+  uint64_t insert_sum, insert_sq_sum;  /* sums of insert(d*) and its square */
+  uint64_t min_insert, max_insert;     /* 0 without an overlapped pair, as the next two */
+  uint64_t mode_insert;                /* the smallest s with the largest count */
+  uint64_t median_insert;              /* the smallest s with 2 * cum(s) >= overlapped */
+  uint64_t min_overlap, max_mismatches, max_mismatch_pct;   /* the parameters as used */
+} scfq_insert_summary;
+
+/* r1 / r2 in host (is_device = 0) or device memory, both of one kind. opts = NULL: the defaults; with
+ * SCFQ_INSERT_INTERLEAVED r1 is the interleaved input and r2 must be NULL with n2 = 0. recs_device: DEVICE memory for
+ * rec_cap records that receives the per-pair table, entries [0, pairs), or NULL; rec_cap < pairs returns SCFQ_EARG with
+ * out->pairs (and reads, lines, input_bytes) set, as scfq_read_stats_buffer. hist_host: HOST memory for exactly
+ * SCFQ_INSERT_HIST_BINS entries, or NULL: entry s = pairs with insert s, entry 0 is always 0. SCFQ_EARG for a NULL out or
+ * a wrong struct_size (out's or opts'), a NULL pointer with n > 0, NULL recs_device with rec_cap > 0; with text: unknown
+ * flag bits, a parameter out of range, a second buffer with interleaved input. Device pointers follow the
+ * scfq_set_wait_stream contract of scfq_index_lines. One device, both inputs whole and resident, fewer than 2^31 records
+ * per input, as scfq_adapters_buffer; there is no CPU fallback (SCFQ_EHIP without a device). */
+int scfq_insert_size_buffers(const void* r1, uint64_t n1, const void* r2, uint64_t n2, int is_device,
+                             const scfq_insert_opts* opts, scfq_overlap_rec* recs_device, uint64_t rec_cap,
+                             uint64_t* hist_host, scfq_insert_summary* out);
+/* path2 = NULL: path1 is interleaved (SCFQ_INSERT_INTERLEAVED in iopts is then implied, and SCFQ_EARG with a path2). Stages
+ * the whole (inflated) inputs with scfq_stage_file, ".gz" and BGZF by suffix as everywhere else. */
+int scfq_insert_size_files(const char* path1, const char* path2, const scfq_opts* opts, const scfq_insert_opts* iopts,
+                           scfq_overlap_rec* recs_device, uint64_t rec_cap, uint64_t* hist_host, scfq_insert_summary* out);
+/* "<pairs>\t<overlapped>\t<percent_overlapped>\t<min>\t<median>\t<mean>\t<std_dev>\t<mode>\t<max>\t<read_through>\t
+ * <mismatch_rate>" without trailing newline. percent_overlapped = 100 * overlapped / pairs, mean = insert_sum / overlapped,
+ * std_dev = sqrt((double)(overlapped * insert_sq_sum - insert_sum^2)) / overlapped with the difference formed as an exact
+ * 128-bit integer and converted once, mismatch_rate = mismatches / overlap_bases; IEEE doubles printed by the rule of
+ * scfq_format_tsv ("nan" for 0/0). Returns the number of bytes needed (excluding NUL); writes at most cap bytes incl. NUL. */
+int scfq_format_insert_size_tsv(const scfq_insert_summary* s, char* buf, uint64_t cap);
+const char* scfq_insert_size_error_detail(void); /* static, thread-local */
+
 /* ---- `sc fa-gc` (FASTA group): src/fa_gc.nim, docs/fa-gc.md, sc.nim:84-96 --------------------------------------------
  * GC content of the windows [pos - w, pos + w] around 1-based positions of a FASTA. The contract:
  *   Lines.   A header line is a line whose first byte is '>' (a line that starts at byte 0 of the input included); every

@@ -74,6 +74,11 @@ int scfq_debug_kmers_stages(double* ms, uint32_t cap);
  * sum of the rows (without the copies to the host) — [1..3] are HIP-event times, taken only while SCFQ_ADAPTERS_TIMING=1 is in
  * the environment (zeros otherwise). Writes min(cap, 4) values, returns 4. */
 int scfq_debug_adapters_stages(double* ms, uint32_t cap);
+/* Stage times of the calling thread's last scfq_insert_size_buffers / scfq_insert_size_files, in milliseconds: ms[0] the line
+ * indexes (host clock around the synchronous index calls), ms[1] P1, the overlap kernel, ms[2] P2, the pass over the bins,
+ * ms[3] the copy of bins and sums to the host — [1..3] are HIP-event times, taken only while SCFQ_INSERT_TIMING=1 is in the
+ * environment (zeros otherwise). Writes min(cap, 4) values, returns 4. */
+int scfq_debug_insert_size_stages(double* ms, uint32_t cap);
 /* Stage times of the calling thread's last scfq_fa_index_buffer / scfq_fa_index_file, in milliseconds: ms[0] F1, the tile scan,
  * ms[1] F2, the scan over the tile records, ms[2] F3, the contig table's kernel, ms[3] unused (0) — HIP-event times, taken only
  * while SCFQ_FA_TIMING=1 is in the environment (zeros otherwise). Writes min(cap, 4) values, returns 4. */

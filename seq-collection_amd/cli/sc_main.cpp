@@ -135,7 +135,8 @@ static void help_top(FILE* f) {
                "  fq-readstats     Per-read length, N50, GC and quality of a FASTQ\n"
                "  fq-cycles        Per-position base composition and quality of a FASTQ\n"
                "  fq-kmers         K-mer spectrum of the sequence lines of a FASTQ\n"
-               "  fq-adapters      Adapter content by read position of a FASTQ\n\n"
+               "  fq-adapters      Adapter content by read position of a FASTQ\n"
+               "  fq-insert-size   Insert sizes from the overlap of the mates of read pairs\n\n"
                "FASTA\n  fa-gc            Calculate GC content surrouding a location\n\n"
                "Options:\n  -h, --help                 Show this help\n  -v, --version              Show version\n"
                "      --debug                Debug mode\n",
@@ -467,6 +468,102 @@ static int cmd_fq_cycles(const std::vector<std::string>& params) {
       std::printf("%s\n", output_w_fnames(">" + std::to_string(max_cycles) + "\t" + row, fastq, basename, absolute).c_str());
     }
     rows.clear();
+  }
+  std::fflush(stdout);
+  return 0;
+}
+
+// command "fq-insert-size" (addition, not in the reference): -t/--header, -b/--basename, -a/--absolute as fq-count, --interleaved,
+// --min-overlap=N, --max-mismatches=N, --max-mismatch-pct=N, --dist, R1.fq R2.fq [R1.fq R2.fq ...]
+static const char* kInsertHeader = "pairs\toverlapped\tpercent_overlapped\tmin\tmedian\tmean\tstd_dev\tmode\tmax\tread_through\tmismatch_rate";
+static const char* kInsertDistHeader = "insert_size\tcount";
+static int cmd_fq_insert_size(const std::vector<std::string>& params) {
+  auto help = [](FILE* f) {
+    std::fputs("Insert sizes from the overlap of the two mates of a read pair\n\nUsage:\n  fq-insert-size [options] R1.fq R2.fq [R1.fq R2.fq ...]\n\n"
+               "Arguments:\n  R1.fq R2.fq      Input FASTQs, two at a time: record i of each is pair i\n\nOptions:\n"
+               "  -t, --header               Output the header\n"
+               "  -b, --basename             Add basename column\n  -a, --absolute             Add column for absolute path\n"
+               "      --interleaved          Every argument is one interleaved FASTQ: records 2i and 2i+1 are pair i\n"
+               "      --min-overlap=N        Shortest overlap that is accepted (default: 30, 1 .. 512)\n"
+               "      --max-mismatches=N     Most mismatches inside the overlap (default: 5, 0 .. 65535)\n"
+               "      --max-mismatch-pct=N   ... and in percent of the overlap (default: 20, 0 .. 100)\n"
+               "      --dist                 One row \"insert_size count\" per insert size that occurs instead of the summary row\n"
+               "  -h, --help                 Show this help\n", f);
+  };
+  if (params.size() == 1) { help(stdout); return 0; }
+  bool header = false, basename = false, absolute = false, only_positional = false, interleaved = false, dist = false;
+  scfq_insert_opts io;
+  std::memset(&io, 0, sizeof io);
+  io.struct_size = sizeof io;
+  io.min_overlap = 30; io.max_mismatches = 5; io.max_mismatch_pct = 20;
+  std::vector<std::string> files;
+  // --name=N with N in lo .. hi
+  auto number = [&](const std::string& a, const char* name, uint32_t lo, uint32_t hi, uint32_t* out) -> bool {
+    const std::string key = std::string("--") + name + "=";
+    if (a.compare(0, key.size(), key) != 0) return false;
+    const std::string v = a.substr(key.size());
+    const bool digits = !v.empty() && v.size() <= 6 && v.find_first_not_of("0123456789") == std::string::npos;
+    if (!digits || std::stoull(v) < lo || std::stoull(v) > hi) { help(stdout); quit_error(std::string("Error: Bad value for --") + name + ": " + v, 1); }
+    *out = (uint32_t)std::stoull(v);
+    return true;
+  };
+  for (size_t i = 1; i < params.size(); ++i) {
+    const std::string& a = params[i];
+    if (only_positional || a.empty() || a[0] != '-' || a == "-") { files.push_back(a); continue; }
+    if (a == "--") { only_positional = true; continue; }
+    if (a == "-h" || a == "--help") { help(stdout); return 0; }
+    if (a == "--header") header = true;
+    else if (a == "--basename") basename = true;
+    else if (a == "--absolute") absolute = true;
+    else if (a == "--interleaved") interleaved = true;
+    else if (a == "--dist") dist = true;
+    else if (number(a, "min-overlap", 1, SCFQ_INSERT_MAX_LEN, &io.min_overlap) || number(a, "max-mismatches", 0, 65535, &io.max_mismatches) ||
+             number(a, "max-mismatch-pct", 0, 100, &io.max_mismatch_pct)) {
+    } else if (a.size() >= 2 && a[1] != '-') {
+      for (size_t k = 1; k < a.size(); ++k) {
+        if (a[k] == 't') header = true;
+        else if (a[k] == 'b') basename = true;
+        else if (a[k] == 'a') absolute = true;
+        else if (a[k] == 'h') { help(stdout); return 0; }
+        else { help(stdout); quit_error(std::string("Error: Unknown option: -") + a[k], 1); }
+      }
+    } else {
+      help(stdout);
+      quit_error("Error: Unknown option: " + a, 1);
+    }
+  }
+  if (!interleaved && files.size() % 2) { help(stdout); quit_error("Error: FASTQs come two at a time (R1 R2), or one at a time with --interleaved", 1); }
+  if (header) std::printf("%s\n", output_header(dist ? kInsertDistHeader : kInsertHeader, basename, absolute).c_str());
+  else if (files.empty()) quit_error("No FASTQ specified", 3);
+  if (interleaved) io.flags |= SCFQ_INSERT_INTERLEAVED;
+  std::vector<uint64_t> hist(SCFQ_INSERT_HIST_BINS);
+  for (size_t i = 0; i < files.size(); i += interleaved ? 1 : 2) {
+    const std::string& r1 = files[i];
+    const std::string* r2 = interleaved ? nullptr : &files[i + 1];
+    if (r1.size() < 3 || (r2 && r2->size() < 3)) quit_error("index out of bounds", 1);
+    scfq_insert_summary s;
+    std::memset(&s, 0, sizeof s);
+    s.struct_size = sizeof s;
+    const int rc = scfq_insert_size_files(r1.c_str(), r2 ? r2->c_str() : nullptr, nullptr, &io, nullptr, 0, hist.data(), &s);
+    if (rc == SCFQ_EOPEN) {
+      // (the first of the two that cannot be opened is the one the library stopped at)
+      const std::string& bad = (r2 && access(r1.c_str(), R_OK) == 0) ? *r2 : r1;
+      quit_error("Unable to open file: " + bad, bad.compare(bad.size() - 3, 3, ".gz") == 0 ? 1 : 2);   // as fq-count
+    }
+    if (rc != SCFQ_OK) {
+      std::string msg = scfq_strerror(rc);
+      const char* d = *scfq_insert_size_error_detail() ? scfq_insert_size_error_detail() : scfq_last_error_detail();
+      if (d && *d) { msg += ": "; msg += d; }
+      quit_error(msg, 1);
+    }
+    if (dist) {
+      for (uint32_t k = 0; k < SCFQ_INSERT_HIST_BINS; ++k)
+        if (hist[k]) std::printf("%s\n", output_w_fnames(std::to_string(k) + "\t" + std::to_string(hist[k]), r1, basename, absolute).c_str());
+    } else {
+      char row[1024];
+      scfq_format_insert_size_tsv(&s, row, sizeof row);
+      std::printf("%s\n", output_w_fnames(row, r1, basename, absolute).c_str());
+    }
   }
   std::fflush(stdout);
   return 0;
@@ -932,6 +1029,7 @@ int main(int argc, char** argv) {
   if (params[0] == "fq-cycles") return cmd_fq_cycles(params);
   if (params[0] == "fq-kmers") return cmd_fq_kmers(params);
   if (params[0] == "fq-adapters") return cmd_fq_adapters(params);
+  if (params[0] == "fq-insert-size") return cmd_fq_insert_size(params);
   if (params[0] == "fa-gc") return cmd_fa_gc(params);
   if (params[0] != "fq-count") {
     help_top(stdout);

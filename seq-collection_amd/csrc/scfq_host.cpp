@@ -7,6 +7,7 @@
 //   src/fq_count.nim:47-51   output fields and `$` formatting (Nim 1.0.6 `$float` = "%.16g" + ".0" rule)
 #include "../../include/sc_fqcount.h"
 
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 
@@ -185,6 +186,29 @@ int scfq_format_adapter_row_tsv(const scfq_adapter_row* r, uint32_t n_probes, ui
     else m += nim_float_to_str(100.0 * (double)v / (double)reads, tmp + m, 96);
   }
   tmp[m] = 0;
+  if (buf && cap) {
+    const uint64_t ncopy = ((uint64_t)m < cap - 1) ? (uint64_t)m : cap - 1;
+    std::memcpy(buf, tmp, ncopy);
+    buf[ncopy] = 0;
+  }
+  return m;
+}
+
+// the fq-insert-size row.  The variance's numerator is exact (128 bits) and becomes a double once, so a checker with big integers
+// gets the same bits
+int scfq_format_insert_size_tsv(const scfq_insert_summary* s, char* buf, uint64_t cap) {
+  if (!s) return SCFQ_EARG;
+  const unsigned __int128 num = (unsigned __int128)s->overlapped * s->insert_sq_sum - (unsigned __int128)s->insert_sum * s->insert_sum;
+  char pct[96], mean[96], sd[96], mr[96];
+  nim_float_to_str(100.0 * (double)s->overlapped / (double)s->pairs, pct, sizeof pct);
+  nim_float_to_str((double)s->insert_sum / (double)s->overlapped, mean, sizeof mean);
+  nim_float_to_str(std::sqrt((double)num) / (double)s->overlapped, sd, sizeof sd);
+  nim_float_to_str((double)s->mismatches / (double)s->overlap_bases, mr, sizeof mr);
+  char tmp[1024];
+  const int m = std::snprintf(tmp, sizeof tmp, "%llu\t%llu\t%s\t%llu\t%llu\t%s\t%s\t%llu\t%llu\t%llu\t%s", (unsigned long long)s->pairs,
+                              (unsigned long long)s->overlapped, pct, (unsigned long long)s->min_insert, (unsigned long long)s->median_insert,
+                              mean, sd, (unsigned long long)s->mode_insert, (unsigned long long)s->max_insert,
+                              (unsigned long long)s->read_through, mr);
   if (buf && cap) {
     const uint64_t ncopy = ((uint64_t)m < cap - 1) ? (uint64_t)m : cap - 1;
     std::memcpy(buf, tmp, ncopy);

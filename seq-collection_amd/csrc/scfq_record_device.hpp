@@ -27,3 +27,8 @@ __device__ __forceinline__ uint64_t wave_max(uint64_t v) {
   for (int o = 32; o > 0; o >>= 1) { const uint64_t x = __shfl_xor((unsigned long long)v, o, 64); v = x > v ? x : v; }
   return v;
 }
+__device__ __forceinline__ uint64_t wave_min(uint64_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { const uint64_t x = __shfl_xor((unsigned long long)v, o, 64); v = x < v ? x : v; }
+  return v;
+}

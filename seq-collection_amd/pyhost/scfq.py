@@ -51,6 +51,8 @@ EXPORTS = [
     "scfq_kmers_buffer", "scfq_kmers_file", "scfq_format_kmer_tsv", "scfq_kmers_error_detail", "scfq_debug_kmers_stages",
     "scfq_adapters_buffer", "scfq_adapters_file", "scfq_adapters_default", "scfq_format_adapter_row_tsv", "scfq_adapters_error_detail",
     "scfq_debug_adapters_stages",
+    "scfq_insert_size_buffers", "scfq_insert_size_files", "scfq_format_insert_size_tsv", "scfq_insert_size_error_detail",
+    "scfq_debug_insert_size_stages",
     "scfq_fa_index_buffer", "scfq_fa_index_file", "scfq_fa_contig_at", "scfq_fa_contig_find", "scfq_fa_count_intervals",
     "scfq_fa_index_free", "scfq_fa_error_detail", "scfq_fa_parse_window", "scfq_fa_gc_interval", "scfq_format_fa_gc_value",
     "scfq_debug_fa_stages",
@@ -154,6 +156,31 @@ class AdapterSummary(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in ADAPTER_SUMMARY_HEAD] + \
                [("probe_len", ctypes.c_uint64 * ADAPTERS_MAX_PROBES), ("hits", ctypes.c_uint64 * ADAPTERS_MAX_PROBES),
                 ("tail", AdapterRow), ("total", AdapterRow)]
+
+
+INSERT_MAX_LEN = 512
+INSERT_HIST_BINS = 1024
+SCFQ_INSERT_INTERLEAVED = 0x1
+INSERT_SUMMARY_FIELDS = ("struct_size", "abi_version", "reads1", "reads2", "lines1", "lines2", "input_bytes1", "input_bytes2", "pairs", "unpaired",
+                         "overlapped", "not_overlapped", "too_long", "read_through", "overlap_bases", "mismatches", "insert_sum",
+                         "insert_sq_sum", "min_insert", "max_insert", "mode_insert", "median_insert", "min_overlap", "max_mismatches",
+                         "max_mismatch_pct")
+
+
+class OverlapRec(ctypes.Structure):
+    """scfq_overlap_rec: one pair of the fq-insert-size table (8 bytes)"""
+    _fields_ = [("offset", ctypes.c_int32), ("overlap", ctypes.c_uint16), ("mismatches", ctypes.c_uint16)]
+
+
+class InsertOpts(ctypes.Structure):
+    """scfq_insert_opts"""
+    _fields_ = [("struct_size", ctypes.c_uint64), ("flags", ctypes.c_uint32), ("min_overlap", ctypes.c_uint32),
+                ("max_mismatches", ctypes.c_uint32), ("max_mismatch_pct", ctypes.c_uint32)]
+
+
+class InsertSummary(ctypes.Structure):
+    """scfq_insert_summary (25 uint64)"""
+    _fields_ = [(n, ctypes.c_uint64) for n in INSERT_SUMMARY_FIELDS]
 
 
 FA_SUMMARY_FIELDS = ("struct_size", "abi_version", "input_bytes", "tiles", "contigs", "bases", "gc_bases", "acgt_bases", "orphan_bases")
@@ -294,6 +321,14 @@ def lib():
                                                   ctypes.c_uint64]
         L.scfq_adapters_error_detail.restype = ctypes.c_char_p
         L.scfq_debug_adapters_stages.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]
+        L.scfq_insert_size_buffers.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
+                                               ctypes.POINTER(InsertOpts), ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                               ctypes.POINTER(InsertSummary)]
+        L.scfq_insert_size_files.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_void_p, ctypes.POINTER(InsertOpts), ctypes.c_void_p,
+                                             ctypes.c_uint64, ctypes.c_void_p, ctypes.POINTER(InsertSummary)]
+        L.scfq_format_insert_size_tsv.argtypes = [ctypes.POINTER(InsertSummary), ctypes.c_char_p, ctypes.c_uint64]
+        L.scfq_insert_size_error_detail.restype = ctypes.c_char_p
+        L.scfq_debug_insert_size_stages.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]
         L.scfq_fa_index_buffer.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, pvp, ctypes.POINTER(FaSummary)]
         L.scfq_fa_index_file.argtypes = [ctypes.c_char_p, ctypes.c_void_p, pvp, ctypes.POINTER(FaSummary)]
         L.scfq_fa_contig_at.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(FaContig)]
@@ -752,6 +787,72 @@ def adapters_stages():
     and zeros unless SCFQ_ADAPTERS_TIMING=1 is in the environment"""
     ms = (ctypes.c_double * 4)()
     lib().scfq_debug_adapters_stages(ms, 4)
+    return list(ms)
+
+
+def _new_insert_summary():
+    s = InsertSummary()
+    s.struct_size = ctypes.sizeof(InsertSummary)
+    return s
+
+
+def insert_opts(interleaved=False, min_overlap=30, max_mismatches=5, max_mismatch_pct=20):
+    o = InsertOpts()
+    o.struct_size = ctypes.sizeof(InsertOpts)
+    o.flags = SCFQ_INSERT_INTERLEAVED if interleaved else 0
+    o.min_overlap, o.max_mismatches, o.max_mismatch_pct = min_overlap, max_mismatches, max_mismatch_pct
+    return o
+
+
+def _insert_call(fn, what, params, interleaved, records_ptr, cap, *head):
+    """params: None (the library's defaults) or (min_overlap, max_mismatches, max_mismatch_pct).  Returns (InsertSummary, the
+    histogram as a uint64 array of INSERT_HIST_BINS entries)."""
+    import numpy as np
+    hist = np.zeros(INSERT_HIST_BINS, dtype=np.uint64)
+    s = _new_insert_summary()
+    o = None
+    if params is not None or interleaved:
+        o = insert_opts(interleaved, *(params if params is not None else ()))
+    rc = fn(*head, ctypes.byref(o) if o is not None else None, ctypes.c_void_p(records_ptr) if records_ptr else None, cap,
+            ctypes.c_void_p(hist.ctypes.data), ctypes.byref(s))
+    if rc != 0:
+        e = ScfqError(rc, what, lib().scfq_insert_size_error_detail().decode() or lib().scfq_last_error_detail().decode())
+        e.summary = s
+        raise e
+    return s, hist
+
+
+def insert_size_device(ptr1, n1, ptr2=None, n2=0, params=None, records_ptr=None, cap=0):
+    """fq-insert-size of device-resident FASTQs; ptr2 = None: ptr1 is interleaved.  records_ptr: device memory for `cap` OverlapRec
+    entries (None: summary and histogram only; size it with the `pairs` of such a call)."""
+    return _insert_call(lib().scfq_insert_size_buffers, "scfq_insert_size_buffers", params, ptr2 is None, records_ptr, cap,
+                        ctypes.c_void_p(ptr1), n1, ctypes.c_void_p(ptr2) if ptr2 is not None else None, n2, 1)
+
+
+def insert_size_host(data1, data2=None, params=None, records_ptr=None, cap=0):
+    """fq-insert-size of host buffers (bytes / numpy uint8); data2 = None: data1 is interleaved"""
+    a1, n1, keep1 = _host_ptr(data1)
+    a2, n2, keep2 = _host_ptr(data2) if data2 is not None else (None, 0, None)
+    return _insert_call(lib().scfq_insert_size_buffers, "scfq_insert_size_buffers", params, data2 is None, records_ptr, cap, a1, n1, a2, n2, 0)
+
+
+def insert_size_file(path1, path2=None, params=None, records_ptr=None, cap=0):
+    """path2 = None: path1 is interleaved"""
+    return _insert_call(lib().scfq_insert_size_files, "scfq_insert_size_files", params, path2 is None, records_ptr, cap, os.fsencode(path1),
+                        os.fsencode(path2) if path2 is not None else None, None)
+
+
+def format_insert_size_tsv(s):
+    buf = ctypes.create_string_buffer(1024)
+    lib().scfq_format_insert_size_tsv(ctypes.byref(s), buf, 1024)
+    return buf.value.decode()
+
+
+def insert_size_stages():
+    """(indexes, overlap kernel, pass over the bins, copy to the host) milliseconds of this thread's last insert_size call; the last
+    three are HIP-event times and zeros unless SCFQ_INSERT_TIMING=1 is in the environment"""
+    ms = (ctypes.c_double * 4)()
+    lib().scfq_debug_insert_size_stages(ms, 4)
     return list(ms)
 
 
