@@ -545,6 +545,91 @@ int scfq_insert_size_files(const char* path1, const char* path2, const scfq_opts
 int scfq_format_insert_size_tsv(const scfq_insert_summary* s, char* buf, uint64_t cap);
 const char* scfq_insert_size_error_detail(void); /* static, thread-local */
 
+/* ---- `sc fq-merge` (addition, not in the reference): overlapping read pairs become single reads -----------------------
+ * Inputs, lines, records, pairs and `unpaired`; A, B, C = revcomp(B), La, Lb, d, ov, mm; the acceptance of an offset by
+ * min_overlap / max_mismatches / max_mismatch_pct (defaults 30 / 5 / 20, the same ranges), the choice of d* and
+ * SCFQ_INSERT_MAX_LEN are those of fq-insert-size above. One more parameter: phred_offset Q0, 33 (the default) or 64.
+ * QA and QB are the texts of the two quality lines (line 4r+3). A quality byte the line does not have counts as the byte
+ * Q0 (a line shorter than the sequence line, a record cut short); bytes of a quality line beyond the sequence length are
+ * ignored. comp() maps A <-> T and C <-> G and leaves every other byte as it is; valid(b) holds when b is exactly one of
+ * A C G T.
+ * A pair with an accepted offset is MERGED. Its merged read has length s = d* + Lb, the insert: mate 1 starts the fragment
+ * and C ends it. For x in [0, s): A covers x iff x < La; C covers x iff x >= d*, at y = x - d*, its source byte being
+ * B[Lb-1-y] with quality QB[Lb-1-y]. At least one covers x; what lies outside [0, s) is read-through into adapter and is
+ * dropped. Base and quality byte at x (qa, qc: the quality bytes of A and C there):
+ *   only A covers                       A[x]                                           QA[x]
+ *   only C covers                       comp(B[..])                                    QB[..]
+ *   both cover, both valid, equal       that base                                      max(qa, qc)
+ *   both cover, both valid, different   the one with the larger quality byte, mate 1   min(Q0 + max(2, |qa - qc|), 126)
+ *                                       on a tie
+ *   both cover, exactly one valid       the valid one                                  its own quality byte
+ *   both cover, neither valid           A[x]                                           min(qa, qc)
+ * (the two "both valid" rows are FLASH's rule). The merged record is the text of mate 1's header line, '\n', the merged
+ * bases, '\n', "+\n", the merged quality bytes, '\n': len(header) + 2 s + 5 bytes; merged records appear in pair order.
+ * A pair without an accepted offset, or a too-long pair, is UNMERGED: mate 1's record is echoed to the first unmerged
+ * output and mate 2's to the second, exactly as fq-dedup echoes a kept record (each line the record has as text + '\n':
+ * "\r\n" comes out as '\n', a last line without a newline gains one). With interleaved input both records go to the first
+ * unmerged output, mate 1 then mate 2, and there is no second one. Records counted in `unpaired` go nowhere.
+ * All values are integers and exact. Device pipeline over the HBM-resident inputs: line index (K5) of each, P1 of
+ * fq-insert-size (the same kernel) into a table in pool memory, M1 — a thread per pair: the three output lengths, summed
+ * per group of 32 pairs, and the sums of the statistics —, three exclusive scans over the groups, and M2 — a wave per
+ * group: unmerged records are copied, merged ones built four positions per lane and stored as words. */
+#define SCFQ_MERGE_INTERLEAVED 0x1u
+typedef struct scfq_merge_opts {
+  uint64_t struct_size;             /* sizeof(scfq_merge_opts) */
+  uint32_t flags;                   /* SCFQ_MERGE_INTERLEAVED */
+  uint32_t min_overlap;
+  uint32_t max_mismatches;
+  uint32_t max_mismatch_pct;
+  uint32_t phred_offset;            /* 33 or 64 */
+  uint32_t reserved;                /* 0 */
+} scfq_merge_opts;
+
+typedef struct scfq_merge_stats {      /* 26 x 8 bytes */
+  uint64_t struct_size;   /* caller sets to sizeof(scfq_merge_stats) before the call */
+  uint64_t abi_version;   /* library writes SCFQ_ABI_VERSION */
+  uint64_t reads1, reads2;             /* as scfq_insert_summary, down to `unpaired` */
+  uint64_t lines1, lines2;
+  uint64_t input_bytes1, input_bytes2;
+  uint64_t pairs, unpaired;
+  uint64_t merged, not_overlapped, too_long;   /* pairs = merged + not_overlapped + too_long */
+  uint64_t merged_bases;               /* sum of s */
+  uint64_t overlap_bases, mismatches;  /* sums of ov(d*) and mm(d*): fq-insert-size's values on the same input */
+  uint64_t took_mate1, took_mate2;     /* positions of the row "both valid, different" won by each mate */
+  uint64_t neither_valid;              /* positions of the last row */
+  uint64_t merged_bytes, unmerged1_bytes, unmerged2_bytes;   /* sizes of the three outputs, written or not */
+  uint64_t min_overlap, max_mismatches, max_mismatch_pct, phred_offset;   /* the parameters as used */
+} scfq_merge_stats;
+
+/* r1 / r2 in host (is_device = 0) or device memory, both of one kind; with SCFQ_MERGE_INTERLEAVED r1 is the interleaved
+ * input and r2 must be NULL with n2 = 0. opts = NULL: the defaults. The three outputs are all host (out_is_device = 0) or
+ * all device memory. An output pointer of NULL with capacity 0 is not written; its size is reported in stats all the same,
+ * so a call with three NULLs is the sizing call. An output that is too small returns SCFQ_EARG with text naming the output
+ * and both sizes: stats is filled, every field, and NO byte is written to ANY output (M2 compares the scanned totals with
+ * the capacities before it stores). un2 with interleaved input is SCFQ_EARG, with text. SCFQ_EARG for a NULL stats or a
+ * wrong struct_size (stats' or opts'), a NULL input with n > 0, a NULL output with a capacity; with text in
+ * scfq_merge_error_detail(): unknown flag bits, a parameter out of range, phred_offset other than 33 or 64, reserved not
+ * 0, a second buffer with interleaved input. Device pointers follow the scfq_set_wait_stream contract of
+ * scfq_index_lines. One device, inputs and outputs whole and resident, fewer than 2^31 records per input, as
+ * scfq_insert_size_buffers; there is no CPU fallback (SCFQ_EHIP without a device). */
+int scfq_merge_buffers(const void* r1, uint64_t n1, const void* r2, uint64_t n2, int is_device,
+                       const scfq_merge_opts* opts, void* merged, uint64_t merged_cap, void* un1, uint64_t un1_cap,
+                       void* un2, uint64_t un2_cap, int out_is_device, scfq_merge_stats* stats);
+/* path2 = NULL: path1 is interleaved (SCFQ_MERGE_INTERLEAVED is then implied, and SCFQ_EARG with a path2; a un2_fd >= 0
+ * is SCFQ_EARG then). Stages the whole (inflated) inputs with scfq_stage_file, ".gz" and BGZF by suffix as everywhere
+ * else. A descriptor below 0: that output is not produced (its size is still in stats). The outputs are written one after
+ * another, each in full: merged, then un1, then un2 — three pipes that one reader drains in lock-step would stall, give
+ * each its own reader or use files. A reader that has gone away is SCFQ_EPIPE and any other failing write SCFQ_EIO, text
+ * in scfq_merge_error_detail(), as scfq_dedup_file; stats is complete then. */
+int scfq_merge_files(const char* path1, const char* path2, const scfq_opts* opts, const scfq_merge_opts* mopts,
+                     int merged_fd, int un1_fd, int un2_fd, scfq_merge_stats* stats);
+/* "<pairs>\t<merged>\t<percent_merged>\t<not_overlapped>\t<too_long>\t<unpaired>\t<merged_bases>\t<overlap_bases>\t
+ * <mismatches>\t<took_mate1>\t<took_mate2>\t<neither_valid>\t<merged_bytes>\t<unmerged1_bytes>\t<unmerged2_bytes>" without
+ * trailing newline; percent_merged = 100 * merged / pairs, an IEEE double printed by the rule of scfq_format_tsv ("nan" for
+ * 0/0). Returns the number of bytes needed (excluding NUL); writes at most cap bytes incl. NUL. SCFQ_EARG for a NULL s. */
+int scfq_format_merge_stats_tsv(const scfq_merge_stats* s, char* buf, uint64_t cap);
+const char* scfq_merge_error_detail(void);       /* static, thread-local */
+
 /* ---- `sc fa-gc` (FASTA group): src/fa_gc.nim, docs/fa-gc.md, sc.nim:84-96 --------------------------------------------
  * GC content of the windows [pos - w, pos + w] around 1-based positions of a FASTA. The contract:
  *   Lines.   A header line is a line whose first byte is '>' (a line that starts at byte 0 of the input included); every

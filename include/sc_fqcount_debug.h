@@ -79,6 +79,11 @@ int scfq_debug_adapters_stages(double* ms, uint32_t cap);
  * ms[3] the copy of bins and sums to the host — [1..3] are HIP-event times, taken only while SCFQ_INSERT_TIMING=1 is in the
  * environment (zeros otherwise). Writes min(cap, 4) values, returns 4. */
 int scfq_debug_insert_size_stages(double* ms, uint32_t cap);
+/* Stage times of the calling thread's last scfq_merge_buffers / scfq_merge_files, in milliseconds: ms[0] the line indexes (host
+ * clock around the synchronous index calls), ms[1] P1, the overlap kernel, ms[2] M1 with the three scans, ms[3] M2, the write
+ * kernel — [1..3] are HIP-event times, taken only while SCFQ_MERGE_TIMING=1 is in the environment (zeros otherwise). Writes
+ * min(cap, 4) values, returns 4. */
+int scfq_debug_merge_stages(double* ms, uint32_t cap);
 /* Stage times of the calling thread's last scfq_fa_index_buffer / scfq_fa_index_file, in milliseconds: ms[0] F1, the tile scan,
  * ms[1] F2, the scan over the tile records, ms[2] F3, the contig table's kernel, ms[3] unused (0) — HIP-event times, taken only
  * while SCFQ_FA_TIMING=1 is in the environment (zeros otherwise). Writes min(cap, 4) values, returns 4. */

@@ -12,6 +12,7 @@
 #include "../../include/sc_fqcount.h"
 #include "../../include/sc_fqcount_debug.h"      // --stats: the library's stage marks
 
+#include <fcntl.h>
 #include <limits.h>
 #include <signal.h>
 #include <sys/stat.h>
@@ -136,7 +137,8 @@ static void help_top(FILE* f) {
                "  fq-cycles        Per-position base composition and quality of a FASTQ\n"
                "  fq-kmers         K-mer spectrum of the sequence lines of a FASTQ\n"
                "  fq-adapters      Adapter content by read position of a FASTQ\n"
-               "  fq-insert-size   Insert sizes from the overlap of the mates of read pairs\n\n"
+               "  fq-insert-size   Insert sizes from the overlap of the mates of read pairs\n"
+               "  fq-merge         Merge overlapping read pairs into single reads\n\n"
                "FASTA\n  fa-gc            Calculate GC content surrouding a location\n\n"
                "Options:\n  -h, --help                 Show this help\n  -v, --version              Show version\n"
                "      --debug                Debug mode\n",
@@ -566,6 +568,126 @@ static int cmd_fq_insert_size(const std::vector<std::string>& params) {
     }
   }
   std::fflush(stdout);
+  return 0;
+}
+
+// command "fq-merge" (addition, not in the reference): R1.fq R2.fq, or --interleaved IN.fq; merged FASTQ to stdout, --unmerged1=PATH /
+// --unmerged2=PATH (--unmerged=PATH with --interleaved), --min-overlap=N, --max-mismatches=N, --max-mismatch-pct=N, --phred-offset=33|64,
+// --stats (header and row of scfq_format_merge_stats_tsv to stderr)
+static const char* kMergeStatsHeader = "pairs\tmerged\tpercent_merged\tnot_overlapped\ttoo_long\tunpaired\tmerged_bases\toverlap_bases\tmismatches\ttook_mate1\t"
+                                       "took_mate2\tneither_valid\tmerged_bytes\tunmerged1_bytes\tunmerged2_bytes";
+static int cmd_fq_merge(const std::vector<std::string>& params) {
+  auto help = [](FILE* f) {
+    std::fputs("Merge overlapping read pairs into single reads; the merged FASTQ goes to stdout\n\nUsage:\n  fq-merge [options] R1.fq R2.fq\n"
+               "  fq-merge [options] --interleaved IN.fq\n\n"
+               "Arguments:\n  R1.fq R2.fq      Input FASTQs: record i of each is pair i\n\nOptions:\n"
+               "      --interleaved          The one argument is an interleaved FASTQ: records 2i and 2i+1 are pair i\n"
+               "      --unmerged1=PATH       Mate 1 of the pairs that were not merged goes to PATH\n"
+               "      --unmerged2=PATH       Mate 2 of the pairs that were not merged goes to PATH\n"
+               "      --unmerged=PATH        With --interleaved: both mates of the pairs that were not merged, interleaved\n"
+               "      --min-overlap=N        Shortest overlap that is accepted (default: 30, 1 .. 512)\n"
+               "      --max-mismatches=N     Most mismatches inside the overlap (default: 5, 0 .. 65535)\n"
+               "      --max-mismatch-pct=N   ... and in percent of the overlap (default: 20, 0 .. 100)\n"
+               "      --phred-offset=N       Quality offset, 33 or 64 (default: 33)\n"
+               "      --stats                Print a header and a row of statistics to stderr\n"
+               "  -h, --help                 Show this help\n", f);
+  };
+  if (params.size() == 1) { help(stdout); return 0; }
+  bool only_positional = false, interleaved = false, stats = false;
+  scfq_merge_opts mo;
+  std::memset(&mo, 0, sizeof mo);
+  mo.struct_size = sizeof mo;
+  mo.min_overlap = 30; mo.max_mismatches = 5; mo.max_mismatch_pct = 20; mo.phred_offset = 33;
+  std::vector<std::string> files;
+  std::string un1, un2, un;
+  // --name=N with N in lo .. hi
+  auto number = [&](const std::string& a, const char* name, uint32_t lo, uint32_t hi, uint32_t* out) -> bool {
+    const std::string key = std::string("--") + name + "=";
+    if (a.compare(0, key.size(), key) != 0) return false;
+    const std::string v = a.substr(key.size());
+    const bool digits = !v.empty() && v.size() <= 6 && v.find_first_not_of("0123456789") == std::string::npos;
+    if (!digits || std::stoull(v) < lo || std::stoull(v) > hi) { help(stdout); quit_error(std::string("Error: Bad value for --") + name + ": " + v, 1); }
+    *out = (uint32_t)std::stoull(v);
+    return true;
+  };
+  auto path = [&](const std::string& a, const char* name, std::string* out) -> bool {
+    const std::string key = std::string("--") + name + "=";
+    if (a.compare(0, key.size(), key) != 0) return false;
+    *out = a.substr(key.size());
+    if (out->empty()) { help(stdout); quit_error(std::string("Error: Bad value for --") + name + ": ", 1); }
+    return true;
+  };
+  for (size_t i = 1; i < params.size(); ++i) {
+    const std::string& a = params[i];
+    if (only_positional || a.empty() || a[0] != '-' || a == "-") { files.push_back(a); continue; }
+    if (a == "--") { only_positional = true; continue; }
+    if (a == "-h" || a == "--help") { help(stdout); return 0; }
+    if (a == "--interleaved") interleaved = true;
+    else if (a == "--stats") stats = true;
+    else if (path(a, "unmerged1", &un1) || path(a, "unmerged2", &un2) || path(a, "unmerged", &un)) {
+    } else if (number(a, "min-overlap", 1, SCFQ_INSERT_MAX_LEN, &mo.min_overlap) || number(a, "max-mismatches", 0, 65535, &mo.max_mismatches) ||
+               number(a, "max-mismatch-pct", 0, 100, &mo.max_mismatch_pct)) {
+    } else if (number(a, "phred-offset", 33, 64, &mo.phred_offset)) {
+      if (mo.phred_offset != 33 && mo.phred_offset != 64) { help(stdout); quit_error("Error: Bad value for --phred-offset: " + std::to_string(mo.phred_offset), 1); }
+    } else {
+      help(stdout);
+      quit_error("Error: Unknown option: " + a, 1);
+    }
+  }
+  if (files.empty()) quit_error("No FASTQ specified", 3);
+  if (files.size() != (interleaved ? 1u : 2u)) { help(stdout); quit_error("Error: fq-merge takes R1.fq and R2.fq, or one FASTQ with --interleaved", 1); }
+  if (interleaved && (!un1.empty() || !un2.empty())) { help(stdout); quit_error("Error: --interleaved writes its unmerged pairs with --unmerged=PATH", 1); }
+  if (!interleaved && !un.empty()) { help(stdout); quit_error("Error: --unmerged=PATH goes with --interleaved; otherwise --unmerged1=PATH --unmerged2=PATH", 1); }
+  if (interleaved) { mo.flags |= SCFQ_MERGE_INTERLEAVED; un1 = un; }
+  for (const std::string& f : files)
+    if (f.size() < 3) quit_error("index out of bounds", 1);
+  // the inputs are looked at before an output file is made
+  for (const std::string& f : files)
+    if (access(f.c_str(), R_OK) != 0) quit_error("Unable to open file: " + f, f.compare(f.size() - 3, 3, ".gz") == 0 ? 1 : 2);   // as fq-count
+  int fd1 = -1, fd2 = -1;
+  // a call that fails leaves no output file behind: what this process created goes again
+  auto discard = [&]() {
+    // (only a regular file: a FIFO or a device the caller named is the caller's)
+    auto drop = [](int fd, const std::string& p) {
+      struct stat st;
+      const bool regular = fstat(fd, &st) == 0 && S_ISREG(st.st_mode);
+      close(fd);
+      if (regular) unlink(p.c_str());
+    };
+    if (fd1 >= 0) drop(fd1, un1);
+    if (fd2 >= 0) drop(fd2, un2);
+    fd1 = fd2 = -1;
+  };
+  auto create = [&](const std::string& p) -> int {
+    const int fd = open(p.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
+    if (fd < 0) { discard(); quit_error("Unable to create file: " + p, 1); }
+    return fd;
+  };
+  if (!un1.empty()) fd1 = create(un1);
+  if (!un2.empty()) fd2 = create(un2);
+  scfq_merge_stats st;
+  std::memset(&st, 0, sizeof st);
+  st.struct_size = sizeof st;
+  std::fflush(stdout);
+  const int rc = scfq_merge_files(files[0].c_str(), interleaved ? nullptr : files[1].c_str(), nullptr, &mo, 1, fd1, fd2, &st);
+  if (rc != SCFQ_OK && rc != SCFQ_EPIPE) discard();
+  else { if (fd1 >= 0) close(fd1); if (fd2 >= 0) close(fd2); }
+  if (rc == SCFQ_EOPEN) {
+    const std::string& bad = (!interleaved && access(files[0].c_str(), R_OK) == 0) ? files[1] : files[0];
+    quit_error("Unable to open file: " + bad, bad.compare(bad.size() - 3, 3, ".gz") == 0 ? 1 : 2);
+  }
+  if (rc == SCFQ_EPIPE) return 0;              // a reader of stdout that went away: quiet, as `sc fq-dedup | head`
+  if (rc != SCFQ_OK) {
+    std::string msg = scfq_strerror(rc);
+    const char* d = *scfq_merge_error_detail() ? scfq_merge_error_detail() : scfq_last_error_detail();
+    if (d && *d) { msg += ": "; msg += d; }
+    quit_error(msg, 1);
+  }
+  if (stats) {
+    char row[1024];
+    scfq_format_merge_stats_tsv(&st, row, sizeof row);
+    std::fprintf(stderr, "%s\n%s\n", kMergeStatsHeader, row);
+  }
   return 0;
 }
 
@@ -1030,6 +1152,7 @@ int main(int argc, char** argv) {
   if (params[0] == "fq-kmers") return cmd_fq_kmers(params);
   if (params[0] == "fq-adapters") return cmd_fq_adapters(params);
   if (params[0] == "fq-insert-size") return cmd_fq_insert_size(params);
+  if (params[0] == "fq-merge") return cmd_fq_merge(params);
   if (params[0] == "fa-gc") return cmd_fa_gc(params);
   if (params[0] != "fq-count") {
     help_top(stdout);

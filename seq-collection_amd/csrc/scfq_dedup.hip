@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
+#include "scfq_fdwrite.hpp"        // device memory -> pinned buffers -> write()
 #include "scfq_index_aux.hpp"      // what the index pass fills on its way: the header hashes
 #include "scfq_record_device.hpp"  // line_span
 #include "scfq_scratch.hpp"        // the pool, the leased stream, the resident input, the line index
@@ -386,44 +387,7 @@ __global__ __launch_bounds__(256) void dd_record_lengths(const uint8_t* base, ui
 // number of bytes in and out: no '\r' stripped, no '\n' added, nothing dropped) it is ONE contiguous copy of ~11 KB;
 // a group that is dropped entirely costs two loads.  Mixed groups go record by record, a record that is not verbatim line by line.
 //
-// The copy keeps EIGHT 16-byte loads per lane in flight before the first store.  Measured r4 and left out again: non-temporal stores
-// (8 % slower here, though 2 % faster in the aligned copy micro-benchmark), the body aligned to 64 or 128 bytes of the destination
-// instead of 16 (no difference): profiles/r04/dedup_ab.txt, copy_shapes.txt — the gather runs at what a copy reaches on this device.
-__device__ __forceinline__ void wave_copy(uint8_t* dst, const uint8_t* src, uint64_t len, uint32_t lane) {
-  typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-  uint64_t head = (16 - ((uintptr_t)dst & 15)) & 15;
-  if (head > len) head = len;
-  if (lane < head) dst[lane] = src[lane];
-  const uint64_t body = (len - head) / 16;
-  const uint8_t* sp = src + head;
-  uint8_t* dp = dst + head;
-  auto put = [&](const v4u& v, uint64_t k) { *reinterpret_cast<v4u*>(dp + k * 16) = v; };
-  uint64_t k = lane;
-  for (; k + 7 * 64 < body; k += 8 * 64) {
-    v4u v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) __builtin_memcpy(&v[u], sp + (k + 64u * u) * 16, 16);       // the source is arbitrarily aligned
-#pragma unroll
-    for (int u = 0; u < 8; ++u) put(v[u], k + 64u * u);
-  }
-  if (k + 3 * 64 < body) {
-    v4u v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) __builtin_memcpy(&v[u], sp + (k + 64u * u) * 16, 16);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) put(v[u], k + 64u * u);
-    k += 4 * 64;
-  }
-  {   // at most four steps are left: all their loads first as well
-    v4u v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) if (k + 64u * u < body) __builtin_memcpy(&v[u], sp + (k + 64u * u) * 16, 16);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) if (k + 64u * u < body) put(v[u], k + 64u * u);
-  }
-  for (uint64_t t = head + body * 16 + lane; t < len; t += 64) dst[t] = src[t];
-}
-
+// (the copy itself: wave_copy in scfq_record_device.hpp)
 __global__ __launch_bounds__(256) void dd_gather(const uint8_t* base, uint64_t n, const uint64_t* line_off, uint64_t lines,
                                                 uint64_t n_hdr, const uint64_t* group_off, uint64_t n_groups, const uint64_t* out_len, uint8_t* out,
                                                 uint64_t out_cap) {
@@ -617,21 +581,6 @@ int dedup_device(const uint8_t* d_in, uint64_t n, uint8_t* user_out, uint64_t us
   return SCFQ_OK;
 }
 
-int write_all(int fd, const uint8_t* p, uint64_t n) {
-  while (n) {
-    ssize_t w = write(fd, p, (size_t)std::min<uint64_t>(n, 1u << 30));
-    if (w < 0 && errno == EINTR) continue;
-    if (w < 0) {       // only a vanished reader is the quiet case (sc.nim:304); a full disk or an I/O error is an error
-      const int e = errno;
-      std::snprintf(g_derr, sizeof g_derr, "write: %s", std::strerror(e));
-      return e == EPIPE ? SCFQ_EPIPE : SCFQ_EIO;
-    }
-    p += w;
-    n -= (uint64_t)w;
-  }
-  return SCFQ_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -679,26 +628,9 @@ int scfq_dedup_file(const char* path, const scfq_opts* opts, int out_fd, scfq_de
   DevBuf result;
   result.adopt(d_out, stream);
   if (out_fd < 0 || nb == 0) { in.mark_clean(); return SCFQ_OK; }
-  // HBM -> two pinned buffers -> write(): the copy of chunk k+1 overlaps the write of chunk k
-  const uint64_t chunk = 32ull << 20;
-  uint8_t* pin[2] = {nullptr, nullptr};
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  for (int b = 0; b < 2; ++b) { SCFQ_SCRATCH_CHK(g_derr, hipHostMalloc(&pin[b], chunk, hipHostMallocDefault)); SCFQ_SCRATCH_CHK(g_derr, hipEventCreateWithFlags(&ev[b], hipEventDisableTiming)); }
-  struct PinGuard { uint8_t** p; hipEvent_t* e; ~PinGuard() { for (int b = 0; b < 2; ++b) { if (p[b]) (void)hipHostFree(p[b]); if (e[b]) (void)hipEventDestroy(e[b]); } } } pg{pin, ev};
-  const uint64_t n_chunks = (nb + chunk - 1) / chunk;
-  auto issue = [&](uint64_t k) -> hipError_t {
-    const uint64_t lo = k * chunk, len = std::min(chunk, nb - lo);
-    hipError_t e = hipMemcpyAsync(pin[k & 1], d_out + lo, len, hipMemcpyDeviceToHost, stream);
-    return e != hipSuccess ? e : hipEventRecord(ev[k & 1], stream);
-  };
-  SCFQ_SCRATCH_CHK(g_derr, issue(0));
-  for (uint64_t k = 0; k < n_chunks; ++k) {
-    SCFQ_SCRATCH_CHK(g_derr, hipEventSynchronize(ev[k & 1]));
-    if (k + 1 < n_chunks) SCFQ_SCRATCH_CHK(g_derr, issue(k + 1));
-    const uint64_t lo = k * chunk, len = std::min(chunk, nb - lo);
-    if ((rc = write_all(out_fd, pin[k & 1], len))) return rc;
-  }
-  return SCFQ_OK;      // (the last chunk was waited for by its event, not by the stream: the lease waits)
+  scfq_fdwrite::Pinned pinned;      // HBM -> two pinned buffers -> write()
+  if ((rc = pinned.init(g_derr))) return rc;
+  return pinned.device_to_fd(d_out, nb, out_fd, stream, g_derr);      // (the last chunk was waited for by its event, not by the stream: the lease waits)
 }
 
 }  // extern "C"

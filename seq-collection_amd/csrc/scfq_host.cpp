@@ -217,6 +217,24 @@ int scfq_format_insert_size_tsv(const scfq_insert_summary* s, char* buf, uint64_
   return m;
 }
 
+// the fq-merge row: integers but for the share of merged pairs
+int scfq_format_merge_stats_tsv(const scfq_merge_stats* s, char* buf, uint64_t cap) {
+  if (!s) return SCFQ_EARG;
+  char pct[96];
+  nim_float_to_str(100.0 * (double)s->merged / (double)s->pairs, pct, sizeof pct);
+  const uint64_t tail[] = {s->not_overlapped, s->too_long, s->unpaired, s->merged_bases, s->overlap_bases, s->mismatches, s->took_mate1,
+                           s->took_mate2, s->neither_valid, s->merged_bytes, s->unmerged1_bytes, s->unmerged2_bytes};
+  char tmp[1024];
+  int m = std::snprintf(tmp, sizeof tmp, "%llu\t%llu\t%s", (unsigned long long)s->pairs, (unsigned long long)s->merged, pct);
+  for (const uint64_t v : tail) m += std::snprintf(tmp + m, sizeof tmp - m, "\t%llu", (unsigned long long)v);
+  if (buf && cap) {
+    const uint64_t ncopy = ((uint64_t)m < cap - 1) ? (uint64_t)m : cap - 1;
+    std::memcpy(buf, tmp, ncopy);
+    buf[ncopy] = 0;
+  }
+  return m;
+}
+
 const char* scfq_strerror(int rc) {
   switch (rc) {
     case SCFQ_OK: return "ok";

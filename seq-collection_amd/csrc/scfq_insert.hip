@@ -23,6 +23,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "scfq_overlap.hpp"
 #include "scfq_record_device.hpp"
 #include "scfq_scratch.hpp"
 
@@ -213,7 +214,7 @@ __global__ __launch_bounds__(SCFQ_INSERT_HIST_BINS) void is_finish(unsigned long
   if (s == 0) out[kMode] = mode ? SCFQ_INSERT_HIST_BINS - 1 - (mode & (SCFQ_INSERT_HIST_BINS - 1)) : 0;
 }
 
-struct Params { uint32_t flags, min_overlap, max_mm, max_pct; };
+using scfq_overlap::Params;
 
 bool args_ok(const scfq_insert_opts* opts, const scfq_overlap_rec* recs, uint64_t rec_cap, const scfq_insert_summary* out, Params& p) {
   if (!out || out->struct_size != sizeof(scfq_insert_summary) || (!recs && rec_cap)) return false;
@@ -222,10 +223,7 @@ bool args_ok(const scfq_insert_opts* opts, const scfq_overlap_rec* recs, uint64_
   if (opts->struct_size != sizeof(scfq_insert_opts)) return false;
   p.flags = opts->flags; p.min_overlap = opts->min_overlap; p.max_mm = opts->max_mismatches; p.max_pct = opts->max_mismatch_pct;
   if (p.flags & ~(uint32_t)SCFQ_INSERT_INTERLEAVED) { std::snprintf(g_ierr, sizeof g_ierr, "unknown flag bits 0x%x", p.flags & ~(uint32_t)SCFQ_INSERT_INTERLEAVED); return false; }
-  if (p.min_overlap < 1 || p.min_overlap > SCFQ_INSERT_MAX_LEN) { std::snprintf(g_ierr, sizeof g_ierr, "min_overlap %u is not in 1 .. %d", p.min_overlap, SCFQ_INSERT_MAX_LEN); return false; }
-  if (p.max_mm > 65535) { std::snprintf(g_ierr, sizeof g_ierr, "max_mismatches %u is not in 0 .. 65535", p.max_mm); return false; }
-  if (p.max_pct > 100) { std::snprintf(g_ierr, sizeof g_ierr, "max_mismatch_pct %u is not in 0 .. 100", p.max_pct); return false; }
-  return true;
+  return scfq_overlap::params_in_range(p, g_ierr);
 }
 
 // in1, in2: the inputs, resident (in2 = nullptr: in1 is interleaved); everything runs on `stream`
@@ -237,23 +235,15 @@ int insert_device(const uint8_t* d1, uint64_t n1, const uint8_t* d2, uint64_t n2
   out->min_overlap = prm.min_overlap;
   out->max_mismatches = prm.max_mm;
   out->max_mismatch_pct = prm.max_pct;
-  DevBuf off1, off2, acc;
-  uint64_t lines1 = 0, lines2 = 0;
-  bool cr1 = true, cr2 = true;
-  int rc = SCFQ_OK;
-  {
-    const auto t_a = std::chrono::steady_clock::now();
-    if ((rc = scfq_scratch::build_line_index(d1, n1, stream, g_ierr, off1, &lines1, &cr1))) return rc;
-    if (!interleaved && (rc = scfq_scratch::build_line_index(d2, n2, stream, g_ierr, off2, &lines2, &cr2))) return rc;
-    g_stage_ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_a).count();
-  }
-  const uint64_t reads1 = (lines1 + 3) / 4, reads2 = (lines2 + 3) / 4;
-  out->lines1 = lines1; out->lines2 = lines2;
-  out->reads1 = reads1; out->reads2 = reads2;
-  if (reads1 >= (1ull << 31) || reads2 >= (1ull << 31)) { std::snprintf(g_ierr, sizeof g_ierr, "more than 2^31 records in one input"); return SCFQ_EARG; }
-  const uint64_t pairs = interleaved ? reads1 / 2 : std::min(reads1, reads2);
+  scfq_overlap::Indexed ix;
+  DevBuf acc;
+  int rc = scfq_overlap::index_inputs(d1, n1, d2, n2, interleaved, stream, g_ierr, ix, &g_stage_ms[0]);
+  out->lines1 = ix.lines1; out->lines2 = ix.lines2;
+  out->reads1 = ix.reads1; out->reads2 = ix.reads2;
+  if (rc) return rc;
+  const uint64_t pairs = ix.pairs;
   out->pairs = pairs;
-  out->unpaired = interleaved ? (reads1 & 1) : std::max(reads1, reads2) - pairs;
+  out->unpaired = ix.unpaired;
   if (recs && rec_cap < pairs) { std::snprintf(g_ierr, sizeof g_ierr, "the record table holds %llu pairs, the input has %llu", (unsigned long long)rec_cap, (unsigned long long)pairs); return SCFQ_EARG; }
   if (hist_host) std::memset(hist_host, 0, SCFQ_INSERT_HIST_BINS * sizeof(uint64_t));
   if (pairs == 0) return SCFQ_OK;
@@ -261,13 +251,8 @@ int insert_device(const uint8_t* d1, uint64_t n1, const uint8_t* d2, uint64_t n2
   static const bool timing = scfq_scratch::env_switch("SCFQ_INSERT_TIMING");
   scfq_scratch::StageClock clk(stream, timing);
   SCFQ_SCRATCH_CHK(g_ierr, hipMemsetAsync(acc.p, 0, kIsAcc * 8, stream));
-  const IsInput a = {d1, n1, off1.as<uint64_t>(), lines1, cr1};
-  const IsInput b = interleaved ? a : IsInput{d2, n2, off2.as<uint64_t>(), lines2, cr2};
-  const unsigned blocks = (unsigned)std::min<uint64_t>((pairs + kIsWaves - 1) / kIsWaves, kIsMaxBlocks);
   clk.mark(0);
-  hipLaunchKernelGGL(is_overlap, dim3(blocks), dim3(kIsThreads), 0, stream, a, b, interleaved ? 2ull : 1ull, interleaved ? 1ull : 0ull, pairs,
-                     prm.min_overlap, prm.max_mm, prm.max_pct, recs, acc.as<unsigned long long>());
-  SCFQ_SCRATCH_CHK(g_ierr, hipGetLastError());
+  if ((rc = scfq_overlap::queue_overlap(d1, n1, d2, n2, interleaved, ix, prm, recs, acc.as<unsigned long long>(), stream, g_ierr))) return rc;
   clk.mark(1);
   hipLaunchKernelGGL(is_finish, dim3(1), dim3(SCFQ_INSERT_HIST_BINS), 0, stream, acc.as<unsigned long long>());
   SCFQ_SCRATCH_CHK(g_ierr, hipGetLastError());
@@ -299,6 +284,47 @@ int run(scfq_scratch::ResidentInput& in1, scfq_scratch::ResidentInput& in2, bool
 }
 
 }  // namespace
+
+// ---- scfq_overlap.hpp: the part fq-merge runs as well ----
+namespace scfq_overlap {
+
+static_assert(kAccWords == kIsAcc, "scfq_overlap.hpp sizes P1's counters");
+
+bool params_in_range(const Params& p, char* errbuf) {
+  const size_t cap = scfq_scratch::kErrBytes;
+  if (p.min_overlap < 1 || p.min_overlap > SCFQ_INSERT_MAX_LEN) { std::snprintf(errbuf, cap, "min_overlap %u is not in 1 .. %d", p.min_overlap, SCFQ_INSERT_MAX_LEN); return false; }
+  if (p.max_mm > 65535) { std::snprintf(errbuf, cap, "max_mismatches %u is not in 0 .. 65535", p.max_mm); return false; }
+  if (p.max_pct > 100) { std::snprintf(errbuf, cap, "max_mismatch_pct %u is not in 0 .. 100", p.max_pct); return false; }
+  return true;
+}
+
+int index_inputs(const uint8_t* d1, uint64_t n1, const uint8_t* d2, uint64_t n2, bool interleaved, hipStream_t stream, char* errbuf, Indexed& ix,
+                 double* index_ms) {
+  int rc = SCFQ_OK;
+  const auto t_a = std::chrono::steady_clock::now();
+  if ((rc = scfq_scratch::build_line_index(d1, n1, stream, errbuf, ix.off1, &ix.lines1, &ix.cr1))) return rc;
+  if (!interleaved && (rc = scfq_scratch::build_line_index(d2, n2, stream, errbuf, ix.off2, &ix.lines2, &ix.cr2))) return rc;
+  *index_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_a).count();
+  ix.reads1 = (ix.lines1 + 3) / 4;
+  ix.reads2 = (ix.lines2 + 3) / 4;
+  if (ix.reads1 >= (1ull << 31) || ix.reads2 >= (1ull << 31)) { std::snprintf(errbuf, scfq_scratch::kErrBytes, "more than 2^31 records in one input"); return SCFQ_EARG; }
+  ix.pairs = interleaved ? ix.reads1 / 2 : std::min(ix.reads1, ix.reads2);
+  ix.unpaired = interleaved ? (ix.reads1 & 1) : std::max(ix.reads1, ix.reads2) - ix.pairs;
+  return SCFQ_OK;
+}
+
+int queue_overlap(const uint8_t* d1, uint64_t n1, const uint8_t* d2, uint64_t n2, bool interleaved, const Indexed& ix, const Params& prm,
+                  scfq_overlap_rec* recs, unsigned long long* acc, hipStream_t stream, char* errbuf) {
+  const IsInput a = {d1, n1, static_cast<const uint64_t*>(ix.off1.p), ix.lines1, ix.cr1};
+  const IsInput b = interleaved ? a : IsInput{d2, n2, static_cast<const uint64_t*>(ix.off2.p), ix.lines2, ix.cr2};
+  const unsigned blocks = (unsigned)std::min<uint64_t>((ix.pairs + kIsWaves - 1) / kIsWaves, kIsMaxBlocks);
+  hipLaunchKernelGGL(is_overlap, dim3(blocks), dim3(kIsThreads), 0, stream, a, b, interleaved ? 2ull : 1ull, interleaved ? 1ull : 0ull, ix.pairs,
+                     prm.min_overlap, prm.max_mm, prm.max_pct, recs, acc);
+  SCFQ_SCRATCH_CHK(errbuf, hipGetLastError());
+  return SCFQ_OK;
+}
+
+}  // namespace scfq_overlap
 
 extern "C" {
 

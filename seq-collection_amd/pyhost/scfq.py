@@ -53,6 +53,7 @@ EXPORTS = [
     "scfq_debug_adapters_stages",
     "scfq_insert_size_buffers", "scfq_insert_size_files", "scfq_format_insert_size_tsv", "scfq_insert_size_error_detail",
     "scfq_debug_insert_size_stages",
+    "scfq_merge_buffers", "scfq_merge_files", "scfq_format_merge_stats_tsv", "scfq_merge_error_detail", "scfq_debug_merge_stages",
     "scfq_fa_index_buffer", "scfq_fa_index_file", "scfq_fa_contig_at", "scfq_fa_contig_find", "scfq_fa_count_intervals",
     "scfq_fa_index_free", "scfq_fa_error_detail", "scfq_fa_parse_window", "scfq_fa_gc_interval", "scfq_format_fa_gc_value",
     "scfq_debug_fa_stages",
@@ -181,6 +182,25 @@ class InsertOpts(ctypes.Structure):
 class InsertSummary(ctypes.Structure):
     """scfq_insert_summary (25 uint64)"""
     _fields_ = [(n, ctypes.c_uint64) for n in INSERT_SUMMARY_FIELDS]
+
+
+SCFQ_MERGE_INTERLEAVED = 0x1
+MERGE_STATS_FIELDS = ("struct_size", "abi_version", "reads1", "reads2", "lines1", "lines2", "input_bytes1", "input_bytes2", "pairs", "unpaired",
+                      "merged", "not_overlapped", "too_long", "merged_bases", "overlap_bases", "mismatches", "took_mate1", "took_mate2",
+                      "neither_valid", "merged_bytes", "unmerged1_bytes", "unmerged2_bytes", "min_overlap", "max_mismatches", "max_mismatch_pct",
+                      "phred_offset")
+
+
+class MergeOpts(ctypes.Structure):
+    """scfq_merge_opts"""
+    _fields_ = [("struct_size", ctypes.c_uint64), ("flags", ctypes.c_uint32), ("min_overlap", ctypes.c_uint32),
+                ("max_mismatches", ctypes.c_uint32), ("max_mismatch_pct", ctypes.c_uint32), ("phred_offset", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+class MergeStats(ctypes.Structure):
+    """scfq_merge_stats (26 uint64)"""
+    _fields_ = [(n, ctypes.c_uint64) for n in MERGE_STATS_FIELDS]
 
 
 FA_SUMMARY_FIELDS = ("struct_size", "abi_version", "input_bytes", "tiles", "contigs", "bases", "gc_bases", "acgt_bases", "orphan_bases")
@@ -329,6 +349,14 @@ def lib():
         L.scfq_format_insert_size_tsv.argtypes = [ctypes.POINTER(InsertSummary), ctypes.c_char_p, ctypes.c_uint64]
         L.scfq_insert_size_error_detail.restype = ctypes.c_char_p
         L.scfq_debug_insert_size_stages.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]
+        L.scfq_merge_buffers.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(MergeOpts),
+                                         ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                         ctypes.c_int, ctypes.POINTER(MergeStats)]
+        L.scfq_merge_files.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_void_p, ctypes.POINTER(MergeOpts), ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_int, ctypes.POINTER(MergeStats)]
+        L.scfq_format_merge_stats_tsv.argtypes = [ctypes.POINTER(MergeStats), ctypes.c_char_p, ctypes.c_uint64]
+        L.scfq_merge_error_detail.restype = ctypes.c_char_p
+        L.scfq_debug_merge_stages.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]
         L.scfq_fa_index_buffer.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, pvp, ctypes.POINTER(FaSummary)]
         L.scfq_fa_index_file.argtypes = [ctypes.c_char_p, ctypes.c_void_p, pvp, ctypes.POINTER(FaSummary)]
         L.scfq_fa_contig_at.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(FaContig)]
@@ -853,6 +881,89 @@ def insert_size_stages():
     three are HIP-event times and zeros unless SCFQ_INSERT_TIMING=1 is in the environment"""
     ms = (ctypes.c_double * 4)()
     lib().scfq_debug_insert_size_stages(ms, 4)
+    return list(ms)
+
+
+def _new_merge_stats():
+    s = MergeStats()
+    s.struct_size = ctypes.sizeof(MergeStats)
+    return s
+
+
+def merge_opts(interleaved=False, min_overlap=30, max_mismatches=5, max_mismatch_pct=20, phred_offset=33):
+    o = MergeOpts()
+    o.struct_size = ctypes.sizeof(MergeOpts)
+    o.flags = SCFQ_MERGE_INTERLEAVED if interleaved else 0
+    o.min_overlap, o.max_mismatches, o.max_mismatch_pct, o.phred_offset = min_overlap, max_mismatches, max_mismatch_pct, phred_offset
+    return o
+
+
+def _merge_call(fn, what, params, phred_offset, interleaved, head, tail):
+    """params: None (the library's defaults) or (min_overlap, max_mismatches, max_mismatch_pct).  Returns the MergeStats; an
+    ScfqError carries them as `stats` (filled as far as the call got: complete when an output was too small)."""
+    s = _new_merge_stats()
+    o = None
+    if params is not None or interleaved or phred_offset != 33:
+        o = merge_opts(interleaved, *(params if params is not None else (30, 5, 20)), phred_offset)
+    rc = fn(*head, ctypes.byref(o) if o is not None else None, *tail, ctypes.byref(s))
+    if rc != 0:
+        e = ScfqError(rc, what, lib().scfq_merge_error_detail().decode() or lib().scfq_last_error_detail().decode())
+        e.stats = s
+        raise e
+    return s
+
+
+def _merge_outputs(outs):
+    """three (address, capacity) pairs or None -> the six arguments"""
+    flat = []
+    for o in outs:
+        flat += [ctypes.c_void_p(o[0]) if o and o[0] else None, o[1] if o else 0]
+    return flat
+
+
+def merge_device(ptr1, n1, ptr2=None, n2=0, params=None, phred_offset=33, merged=None, un1=None, un2=None):
+    """fq-merge of device-resident FASTQs; ptr2 = None: ptr1 is interleaved.  merged / un1 / un2: (device address, capacity) of an
+    output, or None: not written, its size is in the stats all the same (three None: the sizing call)."""
+    return _merge_call(lib().scfq_merge_buffers, "scfq_merge_buffers", params, phred_offset, ptr2 is None,
+                       [ctypes.c_void_p(ptr1), n1, ctypes.c_void_p(ptr2) if ptr2 is not None else None, n2, 1], _merge_outputs((merged, un1, un2)) + [1])
+
+
+def merge_host(data1, data2=None, params=None, phred_offset=33, caps=None):
+    """fq-merge of host buffers (bytes / numpy uint8); data2 = None: data1 is interleaved.  caps: the capacities of the three outputs
+    (an entry of None: that output is not produced); None: a sizing call first, then buffers that fit.  Returns (MergeStats,
+    merged, unmerged1, unmerged2), the outputs as bytes or None."""
+    a1, n1, keep1 = _host_ptr(data1)
+    a2, n2, keep2 = _host_ptr(data2) if data2 is not None else (None, 0, None)
+    head = [a1, n1, a2, n2, 0]
+    fn = lib().scfq_merge_buffers
+    if caps is None:
+        s = _merge_call(fn, "scfq_merge_buffers", params, phred_offset, data2 is None, head, [None, 0, None, 0, None, 0, 0])
+        caps = (s.merged_bytes, s.unmerged1_bytes, s.unmerged2_bytes if data2 is not None else None)
+    bufs = [None if c is None else ctypes.create_string_buffer(max(int(c), 1)) for c in caps]
+    outs = [None if b is None else (ctypes.addressof(b), int(c)) for b, c in zip(bufs, caps)]
+    s = _merge_call(fn, "scfq_merge_buffers", params, phred_offset, data2 is None, head, _merge_outputs(outs) + [0])
+    sizes = (s.merged_bytes, s.unmerged1_bytes, s.unmerged2_bytes)
+    return (s,) + tuple(None if b is None else b.raw[:int(k)] for b, k in zip(bufs, sizes))
+
+
+def merge_file(path1, path2=None, params=None, phred_offset=33, merged_fd=-1, un1_fd=-1, un2_fd=-1):
+    """path2 = None: path1 is interleaved.  A descriptor below 0: that output is not produced.  The outputs are written one after
+    another, each in full."""
+    return _merge_call(lib().scfq_merge_files, "scfq_merge_files", params, phred_offset, path2 is None,
+                       [os.fsencode(path1), os.fsencode(path2) if path2 is not None else None, None], [merged_fd, un1_fd, un2_fd])
+
+
+def format_merge_stats_tsv(s):
+    buf = ctypes.create_string_buffer(1024)
+    lib().scfq_format_merge_stats_tsv(ctypes.byref(s), buf, 1024)
+    return buf.value.decode()
+
+
+def merge_stages():
+    """(indexes, overlap kernel, lengths and scans, write kernel) milliseconds of this thread's last merge call; the last three are
+    HIP-event times and zeros unless SCFQ_MERGE_TIMING=1 is in the environment"""
+    ms = (ctypes.c_double * 4)()
+    lib().scfq_debug_merge_stages(ms, 4)
     return list(ms)
 
 
