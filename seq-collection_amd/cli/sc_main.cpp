@@ -1,110 +1,30 @@
-// sc_main.cpp — C++ host for the `sc fq-count` command over the C ABI (include/sc_fqcount.h).
+// sc_main.cpp — C++ host for the `sc` commands over the C ABI (include/sc_fqcount.h).  What the commands share (error and
+// filename-column helpers, the option parser, the per-file scaffold) is in sc_cli.hpp; this file holds one function per command.
 //
 // The reference host is Nim (sc.nim + src/fq_count.nim); no Nim toolchain exists in this image, so the
 // host side above the C ABI is written in C++ and mirrors the reference's surface for this path:
 //   sc.nim:103-116                 command "fq-count": -t/--header, -b/--basename, -a/--absolute, [fastq ...]
 //   sc.nim:274-293                 stdin '-' -> literal "STDIN"; bare `sc` -> help
 //   src/fq_count.nim:14-53         one TSV row per file, argv order; "Unable to open file" exit 2
-//   src/utils/helpers.nim:29-34    "Error <code>: <msg>" in red on stderr, exit <code>
-//   src/utils/helpers.nim:200-224  header / basename / absolute columns
 // Everything between "open the file" and "format the row" is one call into libsc_fqcount_hip.so.
 // GPU-only additions are new long options and never change the reference's 5-column row.
-#include "../../include/sc_fqcount.h"
+#include "sc_cli.hpp"
 #include "../../include/sc_fqcount_debug.h"      // --stats: the library's stage marks
 
 #include <fcntl.h>
-#include <limits.h>
 #include <signal.h>
-#include <sys/stat.h>
-#include <unistd.h>
 
 #include <algorithm>
 #include <atomic>
 #include <cctype>
 #include <condition_variable>
-#include <cstdio>
 #include <mutex>
 #include <thread>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
 
 static const char* kVersion = "0.0.2-mi355x";
 static const char* kHeader = "reads\tgc_content\tgc_bases\tn_bases\tbases";   // src/fq_count.nim:7-11
 
-static void error_msg(const std::string& msg, int code) {           // helpers.nim:29-30 (colorize fgRed)
-  std::fprintf(stderr, "\x1b[31mError %d: %s\x1b[0m\n", code, msg.c_str());
-}
-[[noreturn]] static void quit_error(const std::string& msg, int code = 1) {   // helpers.nim:32-34
-  error_msg(msg, code);
-  std::exit(code);
-}
-
-static std::string join_nonempty(const std::vector<std::string>& parts) {     // filterIt(it.len > 0).join("\t")
-  std::string out;
-  for (const auto& p : parts) {
-    if (p.empty()) continue;
-    if (!out.empty()) out += '\t';
-    out += p;
-  }
-  return out;
-}
-
-static std::string output_header(const std::string& header, bool basename, bool absolute) {   // helpers.nim:200-208
-  return join_nonempty({header, basename ? "basename" : "", absolute ? "absolute" : ""});
-}
-
-static std::string last_path_part(std::string p) {   // Nim os.lastPathPart
-  while (p.size() > 1 && p.back() == '/') p.pop_back();
-  if (p == "/") return "";
-  const size_t k = p.find_last_of('/');
-  return k == std::string::npos ? p : p.substr(k + 1);
-}
-
-static std::string normalize_join(const std::string& root, const std::string& rel) {   // Nim os.absolutePath/joinPath
-  std::vector<std::string> comp;
-  auto feed = [&](const std::string& s) {
-    size_t i = 0;
-    while (i <= s.size()) {
-      size_t j = s.find('/', i);
-      if (j == std::string::npos) j = s.size();
-      std::string c = s.substr(i, j - i);
-      if (c == "..") { if (!comp.empty()) comp.pop_back(); }
-      else if (!c.empty() && c != ".") comp.push_back(c);
-      i = j + 1;
-    }
-  };
-  feed(root);
-  feed(rel);
-  std::string out;
-  for (const auto& c : comp) { out += '/'; out += c; }
-  return out.empty() ? "/" : out;
-}
-
-static std::string absolute_path(const std::string& p) {
-  if (!p.empty() && p[0] == '/') return p;          // absolute inputs are returned verbatim
-  char cwd[PATH_MAX];
-  if (!getcwd(cwd, sizeof cwd)) return p;
-  return normalize_join(cwd, p);
-}
-
-static std::string get_absolute(const std::string& path) {   // helpers.nim:210-213
-  struct stat sb;
-  if (lstat(path.c_str(), &sb) == 0 && S_ISLNK(sb.st_mode)) {
-    char buf[PATH_MAX];
-    ssize_t n = readlink(path.c_str(), buf, sizeof buf - 1);
-    if (n >= 0) { buf[n] = 0; return absolute_path(buf); }   // relative targets resolve against the CWD (reference quirk)
-  }
-  return absolute_path(path);
-}
-
-static std::string output_w_fnames(const std::string& line, const std::string& path, bool basename, bool absolute) {
-  return join_nonempty({line, basename ? last_path_part(path) : "", absolute ? get_absolute(path) : ""});   // helpers.nim:215-224
-}
-
-static void help_fq_count(FILE* f) {   // docs/fq-count.md:5-19
-  std::fputs(
+static const char* const kHelpFqCount =   // docs/fq-count.md:5-19
       "Counts lines in a FASTQ\n\n"
       "Usage:\n"
       "  fq-count [options] [fastq ...]\n\n"
@@ -124,9 +44,7 @@ static void help_fq_count(FILE* f) {   // docs/fq-count.md:5-19
       "      --shard-rank=R --shard-world=W --rendezvous=HOST:PORT [--transport=rccl|tcp]\n"
       "                             One process per GPU: this process scans byte range R of W of every file on its device\n"
       "                             (--devices=ID, default R), the partials are exchanged (RCCL all-gather), rank 0 prints\n"
-      "                             the rows. Defaults come from RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT.\n",
-      f);
-}
+      "                             the rows. Defaults come from RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT.\n";
 
 static void help_top(FILE* f) {
   std::fprintf(f,
@@ -159,32 +77,18 @@ struct FileResult {
 };
 
 // proc fq_count*(fastq: string, basename: bool, absolute: bool)      src/fq_count.nim:14  (compute part)
-static FileResult fq_count_compute(const std::string& fastq, bool basename, bool absolute, const scfq_opts& opts, bool stats,
-                                   scfq_comm* comm = nullptr) {
+// (it runs on the threads of --jobs, so an error is handed back instead of quitting here)
+static FileResult fq_count_compute(const std::string& fastq, const Columns& cols, const scfq_opts& opts, scfq_comm* comm = nullptr) {
   FileResult r;
-  if (fastq.size() < 3) { r.exit_code = 1; r.error = "index out of bounds"; return r; }   // fastq[^3 .. ^1] raises; sc.nim:299-305 -> exit 1
-  scfq_counts c;
-  std::memset(&c, 0, sizeof c);
-  c.struct_size = sizeof c;
+  if (fastq.size() < 3) { r.exit_code = 1; r.error = kIndexOutOfBounds; return r; }   // as require_suffix_room()
+  scfq_counts c = fresh<scfq_counts>();
   // one process per GPU: this rank's byte range, exchange, every rank gets the whole file's counters
   const int rc = comm ? scfq_count_file_sharded(fastq.c_str(), &opts, comm, &c) : scfq_count_file(fastq.c_str(), &opts, &c);
-  if (rc == SCFQ_EOPEN) {
-    const bool gz = fastq.compare(fastq.size() - 3, 3, ".gz") == 0;
-    // plain: stream == nil -> quit_error(..., 2) (fq_count.nim:35-36); .gz: the stream constructor raises -> exit 1 (sc.nim:299-305)
-    r.exit_code = gz ? 1 : 2;
-    r.error = "Unable to open file: " + fastq;
-    return r;
-  }
-  if (rc != SCFQ_OK) {
-    r.exit_code = 1;
-    r.error = std::string(scfq_strerror(rc));
-    const char* d = scfq_last_error_detail();
-    if (d && *d) { r.error += ": "; r.error += d; }
-    return r;
-  }
+  if (rc == SCFQ_EOPEN) { r.exit_code = unable_to_open_code(fastq); r.error = unable_to_open(fastq); return r; }
+  if (rc != SCFQ_OK) { r.exit_code = 1; r.error = library_error(rc); return r; }
   char row[256];
   scfq_format_tsv(&c, row, sizeof row);
-  r.row = output_w_fnames(row, fastq, basename, absolute);
+  r.row = cols.row(row, fastq);
   char buf[512];
   if (opts.flags & SCFQ_STRUCT_CHECK) {
     std::snprintf(buf, sizeof buf, "%s\tbad_at=%llu\tbad_plus=%llu\n", fastq.c_str(), (unsigned long long)c.bad_at, (unsigned long long)c.bad_plus);
@@ -196,10 +100,8 @@ static FileResult fq_count_compute(const std::string& fastq, bool basename, bool
       if (c.qual_hist[v]) { std::snprintf(buf, sizeof buf, "\t%d:%llu", v, (unsigned long long)c.qual_hist[v]); r.extra += buf; }
     r.extra += "\n";
   }
-  if (stats) {
-    scfq_timing t;
-    std::memset(&t, 0, sizeof t);
-    t.struct_size = sizeof t;
+  if (opts.flags & SCFQ_TIMING) {          // --stats
+    scfq_timing t = fresh<scfq_timing>();
     scfq_last_timing(&t);
     const double gbs = t.scan_kernel_ms > 0 ? (double)t.scan_bytes / (t.scan_kernel_ms * 1e-3) / 1e9 : 0.0;
     char js[1024];
@@ -249,29 +151,27 @@ static std::string nim_float(double v) {
 
 // command "fq-dedup" (sc.nim:118-122): one positional FASTQ, no options; proc fq_dedup (src/fq_dedup.nim:14-84)
 static int cmd_fq_dedup(const std::vector<std::string>& params) {
-  auto help = [](FILE* f) {
-    std::fputs("Removes exact duplicates from FASTQ Files\n\nUsage:\n  fq-dedup [options] fastq\n\nArguments:\n"
-               "  fastq            Input FASTQ\n\nOptions:\n  -h, --help                 Show this help\n", f);
-  };
+  static const char* const help =
+      "Removes exact duplicates from FASTQ Files\n\nUsage:\n  fq-dedup [options] fastq\n\nArguments:\n"
+      "  fastq            Input FASTQ\n\nOptions:\n  -h, --help                 Show this help\n";
+  // the reference's grammar: every argument but -h is a file
   std::vector<std::string> files;
   for (size_t i = 1; i < params.size(); ++i) {
-    if (params[i] == "-h" || params[i] == "--help") { help(stdout); return 0; }
+    if (params[i] == "-h" || params[i] == "--help") { std::fputs(help, stdout); return 0; }
     files.push_back(params[i]);
   }
-  if (files.size() != 1) { help(stdout); quit_error(files.empty() ? "Missing argument: fastq" : "Unknown argument(s): " + files[1], 1); }
+  if (files.size() != 1) { std::fputs(help, stdout); quit_error(files.empty() ? "Missing argument: fastq" : "Unknown argument(s): " + files[1], 1); }
   const std::string& fastq = files[0];
   if (fastq == "STDIN") quit_error("This command does not support stdin");                    // sc.nim:58-60
   struct stat sb;
   if (stat(fastq.c_str(), &sb) != 0 || S_ISDIR(sb.st_mode))                                    // helpers.nim:39-43
     quit_error(fastq + " does not exist or is not readable");
-  scfq_dedup_stats st;
-  std::memset(&st, 0, sizeof st);
-  st.struct_size = sizeof st;
+  scfq_dedup_stats st = fresh<scfq_dedup_stats>();
   // the reference announces "No Duplicates Found" before pass 2 starts echoing (fq_dedup.nim:51-53); here the FASTQ goes
   // to fd 1 first and all diagnostics follow: stdout is byte-identical and the lines on stderr keep their order
   std::fflush(stdout);
   const int rc = scfq_dedup_file(fastq.c_str(), nullptr, 1, &st);
-  if (rc == SCFQ_EOPEN) quit_error("Unable to open file: " + fastq, 2);                         // fq_dedup.nim:37-38
+  if (rc == SCFQ_EOPEN) quit_unable_to_open(fastq, 2);                                          // fq_dedup.nim:37-38
   if (rc == SCFQ_EPIPE) return 0;              // `errno: 32 Broken pipe` is swallowed (sc.nim:304); any other IOError exits 1 (sc.nim:299-305)
   if (rc != SCFQ_OK) quit_error(std::string(scfq_strerror(rc)) + ": " + scfq_dedup_error_detail() + scfq_last_error_detail(), 1);
   if (st.duplicates == 0) std::fputs("No Duplicates Found\nCopying fq to stdout\n", stderr);   // :51-53 (check.len == 0)
@@ -284,41 +184,41 @@ static int cmd_fq_dedup(const std::vector<std::string>& params) {
 
 // command "fq-meta" (sc.nim:67-79): -n/--lines (default 100), -t/--header, -b/--basename, -a/--absolute, [fastq ...]
 static int cmd_fq_meta(const std::vector<std::string>& params) {
-  auto help = [](FILE* f) {
-    std::fputs("Output metadata for FASTQ\n\nUsage:\n  fq-meta [options] [fastq ...]\n\nArguments:\n  [fastq ...]      List of FASTQ files\n\n"
-               "Options:\n  -n, --lines=LINES          Number of sequences to sample (n_lines) for qual and index/barcode determination (default: 100)\n"
-               "  -t, --header               Output the header\n  -b, --basename             Add basename column\n"
-               "  -a, --absolute             Add column for absolute path\n  -h, --help                 Show this help\n"
-               "\nMI355X option (addition):\n      --whole-file           Quality range from the histogram of every quality line (device scan)\n", f);
-  };
-  bool header = false, basename = false, absolute = false;
+  static const char* const help =
+      "Output metadata for FASTQ\n\nUsage:\n  fq-meta [options] [fastq ...]\n\nArguments:\n  [fastq ...]      List of FASTQ files\n\n"
+      "Options:\n  -n, --lines=LINES          Number of sequences to sample (n_lines) for qual and index/barcode determination (default: 100)\n"
+      "  -t, --header               Output the header\n  -b, --basename             Add basename column\n"
+      "  -a, --absolute             Add column for absolute path\n  -h, --help                 Show this help\n"
+      "\nMI355X option (addition):\n      --whole-file           Quality range from the histogram of every quality line (device scan)\n";
+  // the reference's grammar (no "--", no short cluster, -n 5 / -n5 / -n=5 / --lines 5), so not a table for parse_options()
+  Columns cols;
   uint32_t flags = 0;
   std::string lines = "100";
   std::vector<std::string> files;
   for (size_t i = 1; i < params.size(); ++i) {
     const std::string& a = params[i];
-    if (a == "-h" || a == "--help") { help(stdout); return 0; }
-    else if (a == "-t" || a == "--header") header = true;
-    else if (a == "-b" || a == "--basename") basename = true;
-    else if (a == "-a" || a == "--absolute") absolute = true;
+    if (a == "-h" || a == "--help") { std::fputs(help, stdout); return 0; }
+    else if (a == "-t" || a == "--header") cols.header = true;
+    else if (a == "-b" || a == "--basename") cols.basename = true;
+    else if (a == "-a" || a == "--absolute") cols.absolute = true;
     else if (a == "--whole-file") flags |= SCFQ_META_WHOLE_FILE;
     else if ((a == "-n" || a == "--lines") && i + 1 < params.size()) lines = params[++i];
     else if (a.rfind("--lines=", 0) == 0) lines = a.substr(8);
     else if (a.rfind("-n", 0) == 0 && a.size() > 2 && a[1] == 'n') lines = a.substr(a[2] == '=' ? 3 : 2);
-    else if (a.size() > 1 && a[0] == '-' && a != "-") { help(stdout); quit_error("Error: Unknown option: " + a, 1); }
+    else if (a.size() > 1 && a[0] == '-' && a != "-") unknown_option(help, a);
     else files.push_back(a);
   }
   char* endp = nullptr;
   const long n = std::strtol(lines.c_str(), &endp, 10);
   if (lines.empty() || *endp || n < 0) quit_error("invalid integer: " + lines, 1);      // parseInt raises ValueError (sc.nim:79)
-  if (header) std::printf("%s\n", output_header(scfq_meta_header(), basename, absolute).c_str());   // sc.nim:75-76
+  cols.header_or_no_input(scfq_meta_header(), false);                                      // sc.nim:75-76 (no file is no error here)
   for (const auto& fastq : files) {                                                          // sc.nim:77-79
     char row[4096];
     const int rc = scfq_meta_file_tsv(fastq.c_str(), (uint32_t)n, flags, row, sizeof row);
-    if (rc == SCFQ_EOPEN) quit_error("Unable to open file: " + fastq, 2);                   // fq_meta.nim:223-224
-    if (rc == SCFQ_EARG) quit_error("index out of bounds", 1);                              // extract_read_info IndexError -> sc.nim:299-305
+    if (rc == SCFQ_EOPEN) quit_unable_to_open(fastq, 2);                                     // fq_meta.nim:223-224
+    if (rc == SCFQ_EARG) quit_error(kIndexOutOfBounds, 1);                                   // extract_read_info IndexError -> sc.nim:299-305
     if (rc < 0) quit_error(std::string(scfq_strerror(rc)) + ": " + scfq_last_error_detail(), 1);
-    std::printf("%s\n", output_w_fnames(row, fastq, basename, absolute).c_str());
+    cols.emit_row(row, fastq);
   }
   std::fflush(stdout);
   return 0;
@@ -327,60 +227,36 @@ static int cmd_fq_meta(const std::vector<std::string>& params) {
 // command "fq-readstats" (addition, not in the reference): -t/--header, -b/--basename, -a/--absolute as fq-count, [fastq ...]
 static const char* kReadStatsHeader = "reads\tbases\tmin_len\tmax_len\tmean_len\tn50\tl50\tn90\tl90\tmean_qual";
 static int cmd_fq_readstats(const std::vector<std::string>& params) {
-  auto help = [](FILE* f) {
-    std::fputs("Per-read length, N50, GC and quality of a FASTQ\n\nUsage:\n  fq-readstats [options] [fastq ...]\n\nArguments:\n"
-               "  [fastq ...]      Input FASTQ\n\nOptions:\n  -t, --header               Output the header\n"
-               "  -b, --basename             Add basename column\n  -a, --absolute             Add column for absolute path\n"
-               "      --hist=len|gc|qual     Print bin<TAB>count of the non-empty bins of a histogram instead of the row:\n"
-               "                             len: bit length of the read length; gc: percent G+C of the non-N bases (101: none);\n"
-               "                             qual: mean quality byte\n"
-               "  -h, --help                 Show this help\n", f);
-  };
-  if (params.size() == 1) { help(stdout); return 0; }
-  bool header = false, basename = false, absolute = false, only_positional = false;
+  static const char* const help =
+      "Per-read length, N50, GC and quality of a FASTQ\n\nUsage:\n  fq-readstats [options] [fastq ...]\n\nArguments:\n"
+      "  [fastq ...]      Input FASTQ\n\nOptions:\n  -t, --header               Output the header\n"
+      "  -b, --basename             Add basename column\n  -a, --absolute             Add column for absolute path\n"
+      "      --hist=len|gc|qual     Print bin<TAB>count of the non-empty bins of a histogram instead of the row:\n"
+      "                             len: bit length of the read length; gc: percent G+C of the non-N bases (101: none);\n"
+      "                             qual: mean quality byte\n"
+      "  -h, --help                 Show this help\n";
+  Columns cols;
   std::string hist;
   std::vector<std::string> files;
-  for (size_t i = 1; i < params.size(); ++i) {
-    const std::string& a = params[i];
-    if (only_positional || a.empty() || a[0] != '-' || a == "-") { files.push_back(a); continue; }
-    if (a == "--") { only_positional = true; continue; }
-    if (a == "-h" || a == "--help") { help(stdout); return 0; }
-    if (a == "--header") header = true;
-    else if (a == "--basename") basename = true;
-    else if (a == "--absolute") absolute = true;
-    else if (a == "--hist=len" || a == "--hist=gc" || a == "--hist=qual") hist = a.substr(7);
-    else if (a.size() >= 2 && a[1] != '-') {
-      for (size_t k = 1; k < a.size(); ++k) {
-        if (a[k] == 't') header = true;
-        else if (a[k] == 'b') basename = true;
-        else if (a[k] == 'a') absolute = true;
-        else if (a[k] == 'h') { help(stdout); return 0; }
-        else { help(stdout); quit_error(std::string("Error: Unknown option: -") + a[k], 1); }
-      }
-    } else {
-      help(stdout);
-      quit_error("Error: Unknown option: " + a, 1);
-    }
-  }
-  if (header) std::printf("%s\n", output_header(hist.empty() ? kReadStatsHeader : "bin\tcount", basename, absolute).c_str());
-  else if (files.empty()) quit_error("No FASTQ specified", 3);
+  const std::vector<Opt> table = cols.options({
+      opt_custom("hist", [&](std::string& v) {     // one of the three names; any other spelling is no option at all
+        if (v != "len" && v != "gc" && v != "qual") return Reject::unknown_option;
+        hist = v;
+        return Reject::none;
+      }),
+  });
+  if (!parse_options(params, help, table, &files)) return 0;
+  cols.header_or_no_input(hist.empty() ? kReadStatsHeader : "bin\tcount", files.empty());
   for (const auto& fastq : files) {
-    if (fastq.size() < 3) quit_error("index out of bounds", 1);
-    scfq_read_summary s;
-    std::memset(&s, 0, sizeof s);
-    s.struct_size = sizeof s;
+    require_suffix_room(fastq);
+    scfq_read_summary s = fresh<scfq_read_summary>();
     const int rc = scfq_read_stats_file(fastq.c_str(), nullptr, &s);
-    if (rc == SCFQ_EOPEN) quit_error("Unable to open file: " + fastq, fastq.compare(fastq.size() - 3, 3, ".gz") == 0 ? 1 : 2);   // as fq-count
-    if (rc != SCFQ_OK) {
-      std::string msg = scfq_strerror(rc);
-      const char* d = *scfq_read_stats_error_detail() ? scfq_read_stats_error_detail() : scfq_last_error_detail();
-      if (d && *d) { msg += ": "; msg += d; }
-      quit_error(msg, 1);
-    }
+    if (rc == SCFQ_EOPEN) quit_unable_to_open(fastq);
+    if (rc != SCFQ_OK) quit_error(library_error(rc, scfq_read_stats_error_detail()), 1);
     if (hist.empty()) {
       char row[512];
       scfq_format_read_stats_tsv(&s, row, sizeof row);
-      std::printf("%s\n", output_w_fnames(row, fastq, basename, absolute).c_str());
+      cols.emit_row(row, fastq);
     } else {
       const uint64_t* h = hist == "len" ? s.len_hist : (hist == "gc" ? s.gc_hist : s.meanq_hist);
       const int bins = hist == "len" ? SCFQ_LEN_HIST_BINS : (hist == "gc" ? SCFQ_GC_HIST_BINS : SCFQ_MEANQ_HIST_BINS);
@@ -388,7 +264,7 @@ static int cmd_fq_readstats(const std::vector<std::string>& params) {
         if (!h[k]) continue;
         char line[64];
         std::snprintf(line, sizeof line, "%d\t%llu", k, (unsigned long long)h[k]);
-        std::printf("%s\n", output_w_fnames(line, fastq, basename, absolute).c_str());
+        cols.emit_row(line, fastq);
       }
     }
   }
@@ -399,77 +275,38 @@ static int cmd_fq_readstats(const std::vector<std::string>& params) {
 // command "fq-cycles" (addition, not in the reference): -t/--header, -b/--basename, -a/--absolute as fq-count, --max-cycles=N, [fastq ...]
 static const char* kCyclesHeader = "cycle\tbases\tA\tC\tG\tT\tN\tother\tquals\tmean_qual";
 static int cmd_fq_cycles(const std::vector<std::string>& params) {
-  auto help = [](FILE* f) {
-    std::fputs("Per-position base composition and quality of a FASTQ\n\nUsage:\n  fq-cycles [options] [fastq ...]\n\nArguments:\n"
-               "  [fastq ...]      Input FASTQ\n\nOptions:\n  -t, --header               Output the header\n"
-               "  -b, --basename             Add basename column\n  -a, --absolute             Add column for absolute path\n"
-               "      --max-cycles=N         One row per position up to N (default: 1000, at most 16777216); what lies beyond\n"
-               "                             comes added up as one last row \">N\"\n"
-               "  -h, --help                 Show this help\n", f);
-  };
-  if (params.size() == 1) { help(stdout); return 0; }
-  bool header = false, basename = false, absolute = false, only_positional = false;
+  static const char* const help =
+      "Per-position base composition and quality of a FASTQ\n\nUsage:\n  fq-cycles [options] [fastq ...]\n\nArguments:\n"
+      "  [fastq ...]      Input FASTQ\n\nOptions:\n  -t, --header               Output the header\n"
+      "  -b, --basename             Add basename column\n  -a, --absolute             Add column for absolute path\n"
+      "      --max-cycles=N         One row per position up to N (default: 1000, at most 16777216); what lies beyond\n"
+      "                             comes added up as one last row \">N\"\n"
+      "  -h, --help                 Show this help\n";
+  Columns cols;
   uint64_t max_cycles = 1000;
   std::vector<std::string> files;
-  for (size_t i = 1; i < params.size(); ++i) {
-    const std::string& a = params[i];
-    if (only_positional || a.empty() || a[0] != '-' || a == "-") { files.push_back(a); continue; }
-    if (a == "--") { only_positional = true; continue; }
-    if (a == "-h" || a == "--help") { help(stdout); return 0; }
-    if (a == "--header") header = true;
-    else if (a == "--basename") basename = true;
-    else if (a == "--absolute") absolute = true;
-    else if (a.compare(0, 13, "--max-cycles=") == 0) {
-      const std::string v = a.substr(13);
-      const bool digits = !v.empty() && v.size() <= 8 && v.find_first_not_of("0123456789") == std::string::npos;
-      if (!digits || std::stoull(v) > SCFQ_CYCLES_MAX_CAP) { help(stdout); quit_error("Error: Bad value for --max-cycles: " + v, 1); }
-      max_cycles = std::stoull(v);
-    } else if (a.size() >= 2 && a[1] != '-') {
-      for (size_t k = 1; k < a.size(); ++k) {
-        if (a[k] == 't') header = true;
-        else if (a[k] == 'b') basename = true;
-        else if (a[k] == 'a') absolute = true;
-        else if (a[k] == 'h') { help(stdout); return 0; }
-        else { help(stdout); quit_error(std::string("Error: Unknown option: -") + a[k], 1); }
-      }
-    } else {
-      help(stdout);
-      quit_error("Error: Unknown option: " + a, 1);
-    }
-  }
-  if (header) std::printf("%s\n", output_header(kCyclesHeader, basename, absolute).c_str());
-  else if (files.empty()) quit_error("No FASTQ specified", 3);
+  const std::vector<Opt> table = cols.options({opt_number("max-cycles", 8, 0, SCFQ_CYCLES_MAX_CAP, &max_cycles)});
+  if (!parse_options(params, help, table, &files)) return 0;
+  cols.header_or_no_input(kCyclesHeader, files.empty());
   std::vector<scfq_cycle_row> rows;
   for (const auto& fastq : files) {
-    if (fastq.size() < 3) quit_error("index out of bounds", 1);
+    require_suffix_room(fastq);
     scfq_cycle_summary s;
-    int rc = SCFQ_OK;
-    // the sizing call first: the table is as long as the file's longest line, not as --max-cycles
-    for (int pass = 0; pass < 2 && rc == SCFQ_OK; ++pass) {
-      std::memset(&s, 0, sizeof s);
-      s.struct_size = sizeof s;
-      rc = scfq_cycles_file(fastq.c_str(), nullptr, rows.empty() ? nullptr : rows.data(), rows.size(), &s);
-      if (pass == 1 || rc != SCFQ_OK) break;
-      rows.assign((size_t)std::min<uint64_t>(max_cycles, std::max(s.max_seq_len, s.max_qual_len)), scfq_cycle_row());
-      if (rows.empty()) break;
-    }
-    if (rc == SCFQ_EOPEN) quit_error("Unable to open file: " + fastq, fastq.compare(fastq.size() - 3, 3, ".gz") == 0 ? 1 : 2);   // as fq-count
-    if (rc != SCFQ_OK) {
-      std::string msg = scfq_strerror(rc);
-      const char* d = *scfq_cycles_error_detail() ? scfq_cycles_error_detail() : scfq_last_error_detail();
-      if (d && *d) { msg += ": "; msg += d; }
-      quit_error(msg, 1);
-    }
+    // the table is as long as the file's longest line, not as --max-cycles
+    const int rc = size_then_fill(
+        &rows, &s, [&](scfq_cycle_row* r, uint64_t n, scfq_cycle_summary* out) { return scfq_cycles_file(fastq.c_str(), nullptr, r, n, out); },
+        [&](const scfq_cycle_summary& sized) { return std::min<uint64_t>(max_cycles, std::max(sized.max_seq_len, sized.max_qual_len)); });
+    if (rc == SCFQ_EOPEN) quit_unable_to_open(fastq);
+    if (rc != SCFQ_OK) quit_error(library_error(rc, scfq_cycles_error_detail()), 1);
     char row[512];
     for (uint64_t p = 0; p < s.cycles; ++p) {
       scfq_format_cycle_row_tsv(&rows[p], row, sizeof row);
-      std::printf("%s\n", output_w_fnames(std::to_string(p + 1) + "\t" + row, fastq, basename, absolute).c_str());
+      cols.emit_row(std::to_string(p + 1) + "\t" + row, fastq);
     }
     if (s.tail.bases || s.tail.quals) {
       scfq_format_cycle_row_tsv(&s.tail, row, sizeof row);
-      std::printf("%s\n", output_w_fnames(">" + std::to_string(max_cycles) + "\t" + row, fastq, basename, absolute).c_str());
+      cols.emit_row(">" + std::to_string(max_cycles) + "\t" + row, fastq);
     }
-    rows.clear();
   }
   std::fflush(stdout);
   return 0;
@@ -480,91 +317,50 @@ static int cmd_fq_cycles(const std::vector<std::string>& params) {
 static const char* kInsertHeader = "pairs\toverlapped\tpercent_overlapped\tmin\tmedian\tmean\tstd_dev\tmode\tmax\tread_through\tmismatch_rate";
 static const char* kInsertDistHeader = "insert_size\tcount";
 static int cmd_fq_insert_size(const std::vector<std::string>& params) {
-  auto help = [](FILE* f) {
-    std::fputs("Insert sizes from the overlap of the two mates of a read pair\n\nUsage:\n  fq-insert-size [options] R1.fq R2.fq [R1.fq R2.fq ...]\n\n"
-               "Arguments:\n  R1.fq R2.fq      Input FASTQs, two at a time: record i of each is pair i\n\nOptions:\n"
-               "  -t, --header               Output the header\n"
-               "  -b, --basename             Add basename column\n  -a, --absolute             Add column for absolute path\n"
-               "      --interleaved          Every argument is one interleaved FASTQ: records 2i and 2i+1 are pair i\n"
-               "      --min-overlap=N        Shortest overlap that is accepted (default: 30, 1 .. 512)\n"
-               "      --max-mismatches=N     Most mismatches inside the overlap (default: 5, 0 .. 65535)\n"
-               "      --max-mismatch-pct=N   ... and in percent of the overlap (default: 20, 0 .. 100)\n"
-               "      --dist                 One row \"insert_size count\" per insert size that occurs instead of the summary row\n"
-               "  -h, --help                 Show this help\n", f);
-  };
-  if (params.size() == 1) { help(stdout); return 0; }
-  bool header = false, basename = false, absolute = false, only_positional = false, interleaved = false, dist = false;
-  scfq_insert_opts io;
-  std::memset(&io, 0, sizeof io);
-  io.struct_size = sizeof io;
+  static const char* const help =
+      "Insert sizes from the overlap of the two mates of a read pair\n\nUsage:\n  fq-insert-size [options] R1.fq R2.fq [R1.fq R2.fq ...]\n\n"
+      "Arguments:\n  R1.fq R2.fq      Input FASTQs, two at a time: record i of each is pair i\n\nOptions:\n"
+      "  -t, --header               Output the header\n"
+      "  -b, --basename             Add basename column\n  -a, --absolute             Add column for absolute path\n"
+      "      --interleaved          Every argument is one interleaved FASTQ: records 2i and 2i+1 are pair i\n"
+      "      --min-overlap=N        Shortest overlap that is accepted (default: 30, 1 .. 512)\n"
+      "      --max-mismatches=N     Most mismatches inside the overlap (default: 5, 0 .. 65535)\n"
+      "      --max-mismatch-pct=N   ... and in percent of the overlap (default: 20, 0 .. 100)\n"
+      "      --dist                 One row \"insert_size count\" per insert size that occurs instead of the summary row\n"
+      "  -h, --help                 Show this help\n";
+  Columns cols;
+  bool dist = false;
+  scfq_insert_opts io = fresh<scfq_insert_opts>();
   io.min_overlap = 30; io.max_mismatches = 5; io.max_mismatch_pct = 20;
   std::vector<std::string> files;
-  // --name=N with N in lo .. hi
-  auto number = [&](const std::string& a, const char* name, uint32_t lo, uint32_t hi, uint32_t* out) -> bool {
-    const std::string key = std::string("--") + name + "=";
-    if (a.compare(0, key.size(), key) != 0) return false;
-    const std::string v = a.substr(key.size());
-    const bool digits = !v.empty() && v.size() <= 6 && v.find_first_not_of("0123456789") == std::string::npos;
-    if (!digits || std::stoull(v) < lo || std::stoull(v) > hi) { help(stdout); quit_error(std::string("Error: Bad value for --") + name + ": " + v, 1); }
-    *out = (uint32_t)std::stoull(v);
-    return true;
-  };
-  for (size_t i = 1; i < params.size(); ++i) {
-    const std::string& a = params[i];
-    if (only_positional || a.empty() || a[0] != '-' || a == "-") { files.push_back(a); continue; }
-    if (a == "--") { only_positional = true; continue; }
-    if (a == "-h" || a == "--help") { help(stdout); return 0; }
-    if (a == "--header") header = true;
-    else if (a == "--basename") basename = true;
-    else if (a == "--absolute") absolute = true;
-    else if (a == "--interleaved") interleaved = true;
-    else if (a == "--dist") dist = true;
-    else if (number(a, "min-overlap", 1, SCFQ_INSERT_MAX_LEN, &io.min_overlap) || number(a, "max-mismatches", 0, 65535, &io.max_mismatches) ||
-             number(a, "max-mismatch-pct", 0, 100, &io.max_mismatch_pct)) {
-    } else if (a.size() >= 2 && a[1] != '-') {
-      for (size_t k = 1; k < a.size(); ++k) {
-        if (a[k] == 't') header = true;
-        else if (a[k] == 'b') basename = true;
-        else if (a[k] == 'a') absolute = true;
-        else if (a[k] == 'h') { help(stdout); return 0; }
-        else { help(stdout); quit_error(std::string("Error: Unknown option: -") + a[k], 1); }
-      }
-    } else {
-      help(stdout);
-      quit_error("Error: Unknown option: " + a, 1);
-    }
-  }
-  if (!interleaved && files.size() % 2) { help(stdout); quit_error("Error: FASTQs come two at a time (R1 R2), or one at a time with --interleaved", 1); }
-  if (header) std::printf("%s\n", output_header(dist ? kInsertDistHeader : kInsertHeader, basename, absolute).c_str());
-  else if (files.empty()) quit_error("No FASTQ specified", 3);
-  if (interleaved) io.flags |= SCFQ_INSERT_INTERLEAVED;
+  const std::vector<Opt> table = cols.options({
+      opt_bits("interleaved", &io.flags, SCFQ_INSERT_INTERLEAVED),
+      opt_flag("dist", 0, &dist),
+      opt_number("min-overlap", 6, 1, SCFQ_INSERT_MAX_LEN, &io.min_overlap),
+      opt_number("max-mismatches", 6, 0, 65535, &io.max_mismatches),
+      opt_number("max-mismatch-pct", 6, 0, 100, &io.max_mismatch_pct),
+  });
+  if (!parse_options(params, help, table, &files)) return 0;
+  const bool interleaved = io.flags & SCFQ_INSERT_INTERLEAVED;
+  if (!interleaved && files.size() % 2) usage_error(help, "FASTQs come two at a time (R1 R2), or one at a time with --interleaved");
+  cols.header_or_no_input(dist ? kInsertDistHeader : kInsertHeader, files.empty());
   std::vector<uint64_t> hist(SCFQ_INSERT_HIST_BINS);
   for (size_t i = 0; i < files.size(); i += interleaved ? 1 : 2) {
     const std::string& r1 = files[i];
     const std::string* r2 = interleaved ? nullptr : &files[i + 1];
-    if (r1.size() < 3 || (r2 && r2->size() < 3)) quit_error("index out of bounds", 1);
-    scfq_insert_summary s;
-    std::memset(&s, 0, sizeof s);
-    s.struct_size = sizeof s;
+    require_suffix_room(r1);
+    if (r2) require_suffix_room(*r2);
+    scfq_insert_summary s = fresh<scfq_insert_summary>();
     const int rc = scfq_insert_size_files(r1.c_str(), r2 ? r2->c_str() : nullptr, nullptr, &io, nullptr, 0, hist.data(), &s);
-    if (rc == SCFQ_EOPEN) {
-      // (the first of the two that cannot be opened is the one the library stopped at)
-      const std::string& bad = (r2 && access(r1.c_str(), R_OK) == 0) ? *r2 : r1;
-      quit_error("Unable to open file: " + bad, bad.compare(bad.size() - 3, 3, ".gz") == 0 ? 1 : 2);   // as fq-count
-    }
-    if (rc != SCFQ_OK) {
-      std::string msg = scfq_strerror(rc);
-      const char* d = *scfq_insert_size_error_detail() ? scfq_insert_size_error_detail() : scfq_last_error_detail();
-      if (d && *d) { msg += ": "; msg += d; }
-      quit_error(msg, 1);
-    }
+    if (rc == SCFQ_EOPEN) quit_unable_to_open(first_unopenable(r1, r2));
+    if (rc != SCFQ_OK) quit_error(library_error(rc, scfq_insert_size_error_detail()), 1);
     if (dist) {
       for (uint32_t k = 0; k < SCFQ_INSERT_HIST_BINS; ++k)
-        if (hist[k]) std::printf("%s\n", output_w_fnames(std::to_string(k) + "\t" + std::to_string(hist[k]), r1, basename, absolute).c_str());
+        if (hist[k]) cols.emit_row(std::to_string(k) + "\t" + std::to_string(hist[k]), r1);
     } else {
       char row[1024];
       scfq_format_insert_size_tsv(&s, row, sizeof row);
-      std::printf("%s\n", output_w_fnames(row, r1, basename, absolute).c_str());
+      cols.emit_row(row, r1);
     }
   }
   std::fflush(stdout);
@@ -577,73 +373,55 @@ static int cmd_fq_insert_size(const std::vector<std::string>& params) {
 static const char* kMergeStatsHeader = "pairs\tmerged\tpercent_merged\tnot_overlapped\ttoo_long\tunpaired\tmerged_bases\toverlap_bases\tmismatches\ttook_mate1\t"
                                        "took_mate2\tneither_valid\tmerged_bytes\tunmerged1_bytes\tunmerged2_bytes";
 static int cmd_fq_merge(const std::vector<std::string>& params) {
-  auto help = [](FILE* f) {
-    std::fputs("Merge overlapping read pairs into single reads; the merged FASTQ goes to stdout\n\nUsage:\n  fq-merge [options] R1.fq R2.fq\n"
-               "  fq-merge [options] --interleaved IN.fq\n\n"
-               "Arguments:\n  R1.fq R2.fq      Input FASTQs: record i of each is pair i\n\nOptions:\n"
-               "      --interleaved          The one argument is an interleaved FASTQ: records 2i and 2i+1 are pair i\n"
-               "      --unmerged1=PATH       Mate 1 of the pairs that were not merged goes to PATH\n"
-               "      --unmerged2=PATH       Mate 2 of the pairs that were not merged goes to PATH\n"
-               "      --unmerged=PATH        With --interleaved: both mates of the pairs that were not merged, interleaved\n"
-               "      --min-overlap=N        Shortest overlap that is accepted (default: 30, 1 .. 512)\n"
-               "      --max-mismatches=N     Most mismatches inside the overlap (default: 5, 0 .. 65535)\n"
-               "      --max-mismatch-pct=N   ... and in percent of the overlap (default: 20, 0 .. 100)\n"
-               "      --phred-offset=N       Quality offset, 33 or 64 (default: 33)\n"
-               "      --stats                Print a header and a row of statistics to stderr\n"
-               "  -h, --help                 Show this help\n", f);
-  };
-  if (params.size() == 1) { help(stdout); return 0; }
-  bool only_positional = false, interleaved = false, stats = false;
-  scfq_merge_opts mo;
-  std::memset(&mo, 0, sizeof mo);
-  mo.struct_size = sizeof mo;
+  static const char* const help =
+      "Merge overlapping read pairs into single reads; the merged FASTQ goes to stdout\n\nUsage:\n  fq-merge [options] R1.fq R2.fq\n"
+      "  fq-merge [options] --interleaved IN.fq\n\n"
+      "Arguments:\n  R1.fq R2.fq      Input FASTQs: record i of each is pair i\n\nOptions:\n"
+      "      --interleaved          The one argument is an interleaved FASTQ: records 2i and 2i+1 are pair i\n"
+      "      --unmerged1=PATH       Mate 1 of the pairs that were not merged goes to PATH\n"
+      "      --unmerged2=PATH       Mate 2 of the pairs that were not merged goes to PATH\n"
+      "      --unmerged=PATH        With --interleaved: both mates of the pairs that were not merged, interleaved\n"
+      "      --min-overlap=N        Shortest overlap that is accepted (default: 30, 1 .. 512)\n"
+      "      --max-mismatches=N     Most mismatches inside the overlap (default: 5, 0 .. 65535)\n"
+      "      --max-mismatch-pct=N   ... and in percent of the overlap (default: 20, 0 .. 100)\n"
+      "      --phred-offset=N       Quality offset, 33 or 64 (default: 33)\n"
+      "      --stats                Print a header and a row of statistics to stderr\n"
+      "  -h, --help                 Show this help\n";
+  bool stats = false;
+  scfq_merge_opts mo = fresh<scfq_merge_opts>();
   mo.min_overlap = 30; mo.max_mismatches = 5; mo.max_mismatch_pct = 20; mo.phred_offset = 33;
   std::vector<std::string> files;
   std::string un1, un2, un;
-  // --name=N with N in lo .. hi
-  auto number = [&](const std::string& a, const char* name, uint32_t lo, uint32_t hi, uint32_t* out) -> bool {
-    const std::string key = std::string("--") + name + "=";
-    if (a.compare(0, key.size(), key) != 0) return false;
-    const std::string v = a.substr(key.size());
-    const bool digits = !v.empty() && v.size() <= 6 && v.find_first_not_of("0123456789") == std::string::npos;
-    if (!digits || std::stoull(v) < lo || std::stoull(v) > hi) { help(stdout); quit_error(std::string("Error: Bad value for --") + name + ": " + v, 1); }
-    *out = (uint32_t)std::stoull(v);
-    return true;
+  // (no row has a letter: the command has no short options)
+  const std::vector<Opt> table = {
+      opt_bits("interleaved", &mo.flags, SCFQ_MERGE_INTERLEAVED),
+      opt_flag("stats", 0, &stats),
+      opt_text("unmerged1", &un1),
+      opt_text("unmerged2", &un2),
+      opt_text("unmerged", &un),
+      opt_number("min-overlap", 6, 1, SCFQ_INSERT_MAX_LEN, &mo.min_overlap),
+      opt_number("max-mismatches", 6, 0, 65535, &mo.max_mismatches),
+      opt_number("max-mismatch-pct", 6, 0, 100, &mo.max_mismatch_pct),
+      opt_custom("phred-offset", [&](std::string& v) {     // a number in 33 .. 64 first, then one of the two
+        uint64_t n = 0;
+        if (!bounded_number(v, 6, 33, 64, &n)) return Reject::bad_value;
+        mo.phred_offset = (uint32_t)n;
+        if (n == 33 || n == 64) return Reject::none;
+        v = std::to_string(n);                             // (this message shows the number, not the text)
+        return Reject::bad_value;
+      }),
   };
-  auto path = [&](const std::string& a, const char* name, std::string* out) -> bool {
-    const std::string key = std::string("--") + name + "=";
-    if (a.compare(0, key.size(), key) != 0) return false;
-    *out = a.substr(key.size());
-    if (out->empty()) { help(stdout); quit_error(std::string("Error: Bad value for --") + name + ": ", 1); }
-    return true;
-  };
-  for (size_t i = 1; i < params.size(); ++i) {
-    const std::string& a = params[i];
-    if (only_positional || a.empty() || a[0] != '-' || a == "-") { files.push_back(a); continue; }
-    if (a == "--") { only_positional = true; continue; }
-    if (a == "-h" || a == "--help") { help(stdout); return 0; }
-    if (a == "--interleaved") interleaved = true;
-    else if (a == "--stats") stats = true;
-    else if (path(a, "unmerged1", &un1) || path(a, "unmerged2", &un2) || path(a, "unmerged", &un)) {
-    } else if (number(a, "min-overlap", 1, SCFQ_INSERT_MAX_LEN, &mo.min_overlap) || number(a, "max-mismatches", 0, 65535, &mo.max_mismatches) ||
-               number(a, "max-mismatch-pct", 0, 100, &mo.max_mismatch_pct)) {
-    } else if (number(a, "phred-offset", 33, 64, &mo.phred_offset)) {
-      if (mo.phred_offset != 33 && mo.phred_offset != 64) { help(stdout); quit_error("Error: Bad value for --phred-offset: " + std::to_string(mo.phred_offset), 1); }
-    } else {
-      help(stdout);
-      quit_error("Error: Unknown option: " + a, 1);
-    }
-  }
-  if (files.empty()) quit_error("No FASTQ specified", 3);
-  if (files.size() != (interleaved ? 1u : 2u)) { help(stdout); quit_error("Error: fq-merge takes R1.fq and R2.fq, or one FASTQ with --interleaved", 1); }
-  if (interleaved && (!un1.empty() || !un2.empty())) { help(stdout); quit_error("Error: --interleaved writes its unmerged pairs with --unmerged=PATH", 1); }
-  if (!interleaved && !un.empty()) { help(stdout); quit_error("Error: --unmerged=PATH goes with --interleaved; otherwise --unmerged1=PATH --unmerged2=PATH", 1); }
-  if (interleaved) { mo.flags |= SCFQ_MERGE_INTERLEAVED; un1 = un; }
-  for (const std::string& f : files)
-    if (f.size() < 3) quit_error("index out of bounds", 1);
+  if (!parse_options(params, help, table, &files)) return 0;
+  const bool interleaved = mo.flags & SCFQ_MERGE_INTERLEAVED;
+  if (files.empty()) quit_no_fastq();
+  if (files.size() != (interleaved ? 1u : 2u)) usage_error(help, "fq-merge takes R1.fq and R2.fq, or one FASTQ with --interleaved");
+  if (interleaved && (!un1.empty() || !un2.empty())) usage_error(help, "--interleaved writes its unmerged pairs with --unmerged=PATH");
+  if (!interleaved && !un.empty()) usage_error(help, "--unmerged=PATH goes with --interleaved; otherwise --unmerged1=PATH --unmerged2=PATH");
+  if (interleaved) un1 = un;
+  for (const std::string& f : files) require_suffix_room(f);
   // the inputs are looked at before an output file is made
   for (const std::string& f : files)
-    if (access(f.c_str(), R_OK) != 0) quit_error("Unable to open file: " + f, f.compare(f.size() - 3, 3, ".gz") == 0 ? 1 : 2);   // as fq-count
+    if (access(f.c_str(), R_OK) != 0) quit_unable_to_open(f);
   int fd1 = -1, fd2 = -1;
   // a call that fails leaves no output file behind: what this process created goes again
   auto discard = [&]() {
@@ -665,24 +443,14 @@ static int cmd_fq_merge(const std::vector<std::string>& params) {
   };
   if (!un1.empty()) fd1 = create(un1);
   if (!un2.empty()) fd2 = create(un2);
-  scfq_merge_stats st;
-  std::memset(&st, 0, sizeof st);
-  st.struct_size = sizeof st;
+  scfq_merge_stats st = fresh<scfq_merge_stats>();
   std::fflush(stdout);
   const int rc = scfq_merge_files(files[0].c_str(), interleaved ? nullptr : files[1].c_str(), nullptr, &mo, 1, fd1, fd2, &st);
   if (rc != SCFQ_OK && rc != SCFQ_EPIPE) discard();
   else { if (fd1 >= 0) close(fd1); if (fd2 >= 0) close(fd2); }
-  if (rc == SCFQ_EOPEN) {
-    const std::string& bad = (!interleaved && access(files[0].c_str(), R_OK) == 0) ? files[1] : files[0];
-    quit_error("Unable to open file: " + bad, bad.compare(bad.size() - 3, 3, ".gz") == 0 ? 1 : 2);
-  }
+  if (rc == SCFQ_EOPEN) quit_unable_to_open(first_unopenable(files[0], interleaved ? nullptr : &files[1]));
   if (rc == SCFQ_EPIPE) return 0;              // a reader of stdout that went away: quiet, as `sc fq-dedup | head`
-  if (rc != SCFQ_OK) {
-    std::string msg = scfq_strerror(rc);
-    const char* d = *scfq_merge_error_detail() ? scfq_merge_error_detail() : scfq_last_error_detail();
-    if (d && *d) { msg += ": "; msg += d; }
-    quit_error(msg, 1);
-  }
+  if (rc != SCFQ_OK) quit_error(library_error(rc, scfq_merge_error_detail()), 1);
   if (stats) {
     char row[1024];
     scfq_format_merge_stats_tsv(&st, row, sizeof row);
@@ -696,82 +464,50 @@ static int cmd_fq_merge(const std::vector<std::string>& params) {
 static const char* kKmersHeader = "kmer\tcount";
 static const char* kKmersTotalsHeader = "k\twindows\tkmers\tskipped\tshort_lines\tdistinct\tmax_count";
 static int cmd_fq_kmers(const std::vector<std::string>& params) {
-  auto help = [](FILE* f) {
-    std::fputs("K-mer spectrum of the sequence lines of a FASTQ\n\nUsage:\n  fq-kmers [options] [fastq ...]\n\nArguments:\n"
-               "  [fastq ...]      Input FASTQ\n\nOptions:\n  -t, --header               Output the header\n"
-               "  -b, --basename             Add basename column\n  -a, --absolute             Add column for absolute path\n"
-               "      --k=N                  Length of the k-mers, 1 .. 12 (default: 7); only windows of A C G T count\n"
-               "      --canonical            Count a k-mer and its reverse complement as the smaller of the two\n"
-               "      --top=N                The N largest counts, ties in k-mer order (default: every k-mer that occurs, in\n"
-               "                             k-mer order)\n"
-               "      --totals               One row per file instead: k windows kmers skipped short_lines distinct max_count\n"
-               "  -h, --help                 Show this help\n", f);
-  };
-  if (params.size() == 1) { help(stdout); return 0; }
-  bool header = false, basename = false, absolute = false, only_positional = false, canonical = false, totals = false, has_top = false;
-  uint32_t k = 7;
-  uint64_t top = 0;
+  static const char* const help =
+      "K-mer spectrum of the sequence lines of a FASTQ\n\nUsage:\n  fq-kmers [options] [fastq ...]\n\nArguments:\n"
+      "  [fastq ...]      Input FASTQ\n\nOptions:\n  -t, --header               Output the header\n"
+      "  -b, --basename             Add basename column\n  -a, --absolute             Add column for absolute path\n"
+      "      --k=N                  Length of the k-mers, 1 .. 12 (default: 7); only windows of A C G T count\n"
+      "      --canonical            Count a k-mer and its reverse complement as the smaller of the two\n"
+      "      --top=N                The N largest counts, ties in k-mer order (default: every k-mer that occurs, in\n"
+      "                             k-mer order)\n"
+      "      --totals               One row per file instead: k windows kmers skipped short_lines distinct max_count\n"
+      "  -h, --help                 Show this help\n";
+  const uint64_t kNoTop = ~0ull;          // (more than the 18 digits of --top=N can say)
+  Columns cols;
+  bool totals = false;
+  uint32_t k = 7, flags = 0;
+  uint64_t top = kNoTop;
   std::vector<std::string> files;
-  auto number = [&](const std::string& v, const char* opt, uint64_t lo, uint64_t hi) -> uint64_t {
-    const bool digits = !v.empty() && v.size() <= 18 && v.find_first_not_of("0123456789") == std::string::npos;
-    if (!digits || std::stoull(v) < lo || std::stoull(v) > hi) { help(stdout); quit_error(std::string("Error: Bad value for ") + opt + ": " + v, 1); }
-    return std::stoull(v);
-  };
-  for (size_t i = 1; i < params.size(); ++i) {
-    const std::string& a = params[i];
-    if (only_positional || a.empty() || a[0] != '-' || a == "-") { files.push_back(a); continue; }
-    if (a == "--") { only_positional = true; continue; }
-    if (a == "-h" || a == "--help") { help(stdout); return 0; }
-    if (a == "--header") header = true;
-    else if (a == "--basename") basename = true;
-    else if (a == "--absolute") absolute = true;
-    else if (a == "--canonical") canonical = true;
-    else if (a == "--totals") totals = true;
-    else if (a.compare(0, 4, "--k=") == 0) k = (uint32_t)number(a.substr(4), "--k", 1, SCFQ_KMERS_MAX_K);
-    else if (a.compare(0, 6, "--top=") == 0) { top = number(a.substr(6), "--top", 0, ~0ull); has_top = true; }
-    else if (a.size() >= 2 && a[1] != '-') {
-      for (size_t j = 1; j < a.size(); ++j) {
-        if (a[j] == 't') header = true;
-        else if (a[j] == 'b') basename = true;
-        else if (a[j] == 'a') absolute = true;
-        else if (a[j] == 'h') { help(stdout); return 0; }
-        else { help(stdout); quit_error(std::string("Error: Unknown option: -") + a[j], 1); }
-      }
-    } else {
-      help(stdout);
-      quit_error("Error: Unknown option: " + a, 1);
-    }
-  }
-  if (header) std::printf("%s\n", output_header(totals ? kKmersTotalsHeader : kKmersHeader, basename, absolute).c_str());
-  else if (files.empty()) quit_error("No FASTQ specified", 3);
+  const std::vector<Opt> options = cols.options({
+      opt_number("k", 18, 1, SCFQ_KMERS_MAX_K, &k),
+      opt_bits("canonical", &flags, SCFQ_KMERS_CANONICAL),
+      opt_number("top", 18, 0, ~0ull, &top),
+      opt_flag("totals", 0, &totals),
+  });
+  if (!parse_options(params, help, options, &files)) return 0;
+  cols.header_or_no_input(totals ? kKmersTotalsHeader : kKmersHeader, files.empty());
   const uint64_t entries = 1ull << (2 * k);
   std::vector<uint64_t> table(totals ? 0 : entries);
   std::vector<uint64_t> order;
   for (const auto& fastq : files) {
-    if (fastq.size() < 3) quit_error("index out of bounds", 1);
-    scfq_kmer_summary s;
-    std::memset(&s, 0, sizeof s);
-    s.struct_size = sizeof s;
-    const int rc = scfq_kmers_file(fastq.c_str(), nullptr, k, canonical ? SCFQ_KMERS_CANONICAL : 0u, table.empty() ? nullptr : table.data(),
-                                   table.size(), &s);
-    if (rc == SCFQ_EOPEN) quit_error("Unable to open file: " + fastq, fastq.compare(fastq.size() - 3, 3, ".gz") == 0 ? 1 : 2);   // as fq-count
-    if (rc != SCFQ_OK) {
-      std::string msg = scfq_strerror(rc);
-      const char* d = *scfq_kmers_error_detail() ? scfq_kmers_error_detail() : scfq_last_error_detail();
-      if (d && *d) { msg += ": "; msg += d; }
-      quit_error(msg, 1);
-    }
+    require_suffix_room(fastq);
+    scfq_kmer_summary s = fresh<scfq_kmer_summary>();
+    const int rc = scfq_kmers_file(fastq.c_str(), nullptr, k, flags, table.empty() ? nullptr : table.data(), table.size(), &s);
+    if (rc == SCFQ_EOPEN) quit_unable_to_open(fastq);
+    if (rc != SCFQ_OK) quit_error(library_error(rc, scfq_kmers_error_detail()), 1);
     char row[64];
     if (totals) {
       const std::string line = std::to_string(s.k) + "\t" + std::to_string(s.windows) + "\t" + std::to_string(s.kmers) + "\t" +
                                std::to_string(s.skipped) + "\t" + std::to_string(s.short_lines) + "\t" + std::to_string(s.distinct) + "\t" +
                                std::to_string(s.max_count);
-      std::printf("%s\n", output_w_fnames(line, fastq, basename, absolute).c_str());
+      cols.emit_row(line, fastq);
       continue;
     }
     order.clear();
     for (uint64_t e = 0; e < entries; ++e) if (table[e]) order.push_back(e);
-    if (has_top) {
+    if (top != kNoTop) {
       // the N largest counts, ties by ascending index (order is ascending already)
       const size_t keep = (size_t)std::min<uint64_t>(top, order.size());
       std::partial_sort(order.begin(), order.begin() + keep, order.end(),
@@ -780,7 +516,7 @@ static int cmd_fq_kmers(const std::vector<std::string>& params) {
     }
     for (const uint64_t e : order) {
       scfq_format_kmer_tsv(k, e, table[e], row, sizeof row);
-      std::printf("%s\n", output_w_fnames(row, fastq, basename, absolute).c_str());
+      cols.emit_row(row, fastq);
     }
   }
   std::fflush(stdout);
@@ -791,64 +527,40 @@ static int cmd_fq_kmers(const std::vector<std::string>& params) {
 // --max-positions=N, --counts, --totals, [fastq ...]
 static const char* kAdaptersTotalsHeader = "adapter\tsequence\treads\treads_with\tpercent\thits";
 static int cmd_fq_adapters(const std::vector<std::string>& params) {
-  auto help = [](FILE* f) {
-    std::fputs("Adapter content by read position of a FASTQ\n\nUsage:\n  fq-adapters [options] [fastq ...]\n\nArguments:\n"
-               "  [fastq ...]      Input FASTQ\n\nOptions:\n  -t, --header               Output the header\n"
-               "  -b, --basename             Add basename column\n  -a, --absolute             Add column for absolute path\n"
-               "      --adapter=NAME:SEQ     Look for SEQ (1 .. 32 letters of A C G T) and call it NAME; up to eight, and giving any\n"
-               "                             replaces the built-in set (Illumina universal and small RNA, Nextera, SOLiD, poly-A, poly-G)\n"
-               "      --max-positions=N      One row per position up to N (default: 1000, at most 16777216); what lies beyond\n"
-               "                             comes as one last row \">N\"\n"
-               "      --counts               The reads whose first occurrence starts at the position, as integers (default: the\n"
-               "                             percentage of the reads in which it starts at or before the position); the \">N\" row\n"
-               "                             then holds the reads whose first occurrence starts beyond N\n"
-               "      --totals               One row per adapter and file instead: adapter sequence reads reads_with percent hits,\n"
-               "                             and a row \"any\"\n"
-               "  -h, --help                 Show this help\n", f);
-  };
-  if (params.size() == 1) { help(stdout); return 0; }
-  bool header = false, basename = false, absolute = false, only_positional = false, counts = false, totals = false;
+  static const char* const help =
+      "Adapter content by read position of a FASTQ\n\nUsage:\n  fq-adapters [options] [fastq ...]\n\nArguments:\n"
+      "  [fastq ...]      Input FASTQ\n\nOptions:\n  -t, --header               Output the header\n"
+      "  -b, --basename             Add basename column\n  -a, --absolute             Add column for absolute path\n"
+      "      --adapter=NAME:SEQ     Look for SEQ (1 .. 32 letters of A C G T) and call it NAME; up to eight, and giving any\n"
+      "                             replaces the built-in set (Illumina universal and small RNA, Nextera, SOLiD, poly-A, poly-G)\n"
+      "      --max-positions=N      One row per position up to N (default: 1000, at most 16777216); what lies beyond\n"
+      "                             comes as one last row \">N\"\n"
+      "      --counts               The reads whose first occurrence starts at the position, as integers (default: the\n"
+      "                             percentage of the reads in which it starts at or before the position); the \">N\" row\n"
+      "                             then holds the reads whose first occurrence starts beyond N\n"
+      "      --totals               One row per adapter and file instead: adapter sequence reads reads_with percent hits,\n"
+      "                             and a row \"any\"\n"
+      "  -h, --help                 Show this help\n";
+  Columns cols;
+  bool counts = false, totals = false;
   uint64_t max_positions = 1000;
   std::vector<std::string> files, names, seqs;
-  for (size_t i = 1; i < params.size(); ++i) {
-    const std::string& a = params[i];
-    if (only_positional || a.empty() || a[0] != '-' || a == "-") { files.push_back(a); continue; }
-    if (a == "--") { only_positional = true; continue; }
-    if (a == "-h" || a == "--help") { help(stdout); return 0; }
-    if (a == "--header") header = true;
-    else if (a == "--basename") basename = true;
-    else if (a == "--absolute") absolute = true;
-    else if (a == "--counts") counts = true;
-    else if (a == "--totals") totals = true;
-    else if (a.compare(0, 16, "--max-positions=") == 0) {
-      const std::string v = a.substr(16);
-      const bool digits = !v.empty() && v.size() <= 8 && v.find_first_not_of("0123456789") == std::string::npos;
-      if (!digits || std::stoull(v) > SCFQ_ADAPTERS_MAX_CAP) { help(stdout); quit_error("Error: Bad value for --max-positions: " + v, 1); }
-      max_positions = std::stoull(v);
-    } else if (a.compare(0, 10, "--adapter=") == 0) {
-      const std::string v = a.substr(10);
-      const size_t colon = v.find(':');
-      const std::string name = colon == std::string::npos ? "" : v.substr(0, colon), seq = colon == std::string::npos ? "" : v.substr(colon + 1);
-      if (name.empty() || name.find('\t') != std::string::npos || seq.empty() || seq.size() > SCFQ_ADAPTERS_MAX_LEN ||
-          seq.find_first_not_of("ACGT") != std::string::npos || names.size() >= SCFQ_ADAPTERS_MAX_PROBES) {
-        help(stdout);
-        quit_error("Error: Bad value for --adapter: " + v, 1);
-      }
-      names.push_back(name);
-      seqs.push_back(seq);
-    } else if (a.size() >= 2 && a[1] != '-') {
-      for (size_t k = 1; k < a.size(); ++k) {
-        if (a[k] == 't') header = true;
-        else if (a[k] == 'b') basename = true;
-        else if (a[k] == 'a') absolute = true;
-        else if (a[k] == 'h') { help(stdout); return 0; }
-        else { help(stdout); quit_error(std::string("Error: Unknown option: -") + a[k], 1); }
-      }
-    } else {
-      help(stdout);
-      quit_error("Error: Unknown option: " + a, 1);
-    }
-  }
+  const std::vector<Opt> table = cols.options({
+      opt_flag("counts", 0, &counts),
+      opt_flag("totals", 0, &totals),
+      opt_number("max-positions", 8, 0, SCFQ_ADAPTERS_MAX_CAP, &max_positions),
+      opt_custom("adapter", [&](std::string& v) {
+        const size_t colon = v.find(':');
+        const std::string name = colon == std::string::npos ? "" : v.substr(0, colon), seq = colon == std::string::npos ? "" : v.substr(colon + 1);
+        if (name.empty() || name.find('\t') != std::string::npos || seq.empty() || seq.size() > SCFQ_ADAPTERS_MAX_LEN ||
+            seq.find_first_not_of("ACGT") != std::string::npos || names.size() >= SCFQ_ADAPTERS_MAX_PROBES)
+          return Reject::bad_value;
+        names.push_back(name);
+        seqs.push_back(seq);
+        return Reject::none;
+      }),
+  });
+  if (!parse_options(params, help, table, &files)) return 0;
   if (names.empty()) {
     const char *name = nullptr, *seq = nullptr;
     for (uint32_t i = 0; scfq_adapters_default(i, &name, &seq) > 0; ++i) { names.push_back(name); seqs.push_back(seq); }
@@ -856,32 +568,20 @@ static int cmd_fq_adapters(const std::vector<std::string>& params) {
   const uint32_t np = (uint32_t)names.size();
   std::vector<const char*> probes;
   for (const auto& s : seqs) probes.push_back(s.c_str());
-  if (header) {
-    std::string h = "position";
-    for (const auto& nm : names) h += "\t" + nm;
-    std::printf("%s\n", output_header(totals ? std::string(kAdaptersTotalsHeader) : h + "\tany", basename, absolute).c_str());
-  } else if (files.empty()) quit_error("No FASTQ specified", 3);
+  std::string positions_header = "position";
+  for (const auto& nm : names) positions_header += "\t" + nm;
+  cols.header_or_no_input(totals ? std::string(kAdaptersTotalsHeader) : positions_header + "\tany", files.empty());
   std::vector<scfq_adapter_row> rows;
   for (const auto& fastq : files) {
-    if (fastq.size() < 3) quit_error("index out of bounds", 1);
+    require_suffix_room(fastq);
     scfq_adapter_summary s;
-    int rc = SCFQ_OK;
-    // the sizing call first: the table is as long as the file's longest sequence line, not as --max-positions
-    for (int pass = 0; pass < 2 && rc == SCFQ_OK; ++pass) {
-      std::memset(&s, 0, sizeof s);
-      s.struct_size = sizeof s;
-      rc = scfq_adapters_file(fastq.c_str(), nullptr, probes.data(), np, rows.empty() ? nullptr : rows.data(), rows.size(), &s);
-      if (pass == 1 || rc != SCFQ_OK || totals) break;
-      rows.assign((size_t)std::min<uint64_t>(max_positions, s.max_seq_len), scfq_adapter_row());
-      if (rows.empty()) break;
-    }
-    if (rc == SCFQ_EOPEN) quit_error("Unable to open file: " + fastq, fastq.compare(fastq.size() - 3, 3, ".gz") == 0 ? 1 : 2);   // as fq-count
-    if (rc != SCFQ_OK) {
-      std::string msg = scfq_strerror(rc);
-      const char* d = *scfq_adapters_error_detail() ? scfq_adapters_error_detail() : scfq_last_error_detail();
-      if (d && *d) { msg += ": "; msg += d; }
-      quit_error(msg, 1);
-    }
+    // the table is as long as the file's longest sequence line, not as --max-positions; --totals needs no table
+    const int rc = size_then_fill(
+        &rows, &s,
+        [&](scfq_adapter_row* r, uint64_t n, scfq_adapter_summary* out) { return scfq_adapters_file(fastq.c_str(), nullptr, probes.data(), np, r, n, out); },
+        [&](const scfq_adapter_summary& sized) { return totals ? 0 : std::min<uint64_t>(max_positions, sized.max_seq_len); });
+    if (rc == SCFQ_EOPEN) quit_unable_to_open(fastq);
+    if (rc != SCFQ_OK) quit_error(library_error(rc, scfq_adapters_error_detail()), 1);
     char row[1024];
     if (totals) {
       uint64_t hits = 0;
@@ -891,26 +591,24 @@ static int cmd_fq_adapters(const std::vector<std::string>& params) {
                                  std::to_string(with) + "\t" + nim_float(100.0 * (double)with / (double)s.reads) + "\t" +
                                  std::to_string(j < np ? s.hits[j] : hits);
         if (j < np) hits += s.hits[j];
-        std::printf("%s\n", output_w_fnames(line, fastq, basename, absolute).c_str());
+        cols.emit_row(line, fastq);
       }
       continue;
     }
     // the rows as they are with --counts; added up from position 1 otherwise
-    scfq_adapter_row acc;
-    std::memset(&acc, 0, sizeof acc);
+    scfq_adapter_row acc = scfq_adapter_row();
     for (uint64_t p = 0; p < s.positions; ++p) {
       for (uint32_t j = 0; j < np; ++j) acc.first[j] += rows[p].first[j];
       acc.any += rows[p].any;
       scfq_format_adapter_row_tsv(counts ? &rows[p] : &acc, np, s.reads, counts, row, sizeof row);
-      std::printf("%s\n", output_w_fnames(std::to_string(p + 1) + "\t" + row, fastq, basename, absolute).c_str());
+      cols.emit_row(std::to_string(p + 1) + "\t" + row, fastq);
     }
     bool tail = s.tail.any != 0;
     for (uint32_t j = 0; j < np; ++j) tail = tail || s.tail.first[j] != 0;
     if (tail) {
       scfq_format_adapter_row_tsv(counts ? &s.tail : &s.total, np, s.reads, counts, row, sizeof row);
-      std::printf("%s\n", output_w_fnames(">" + std::to_string(max_positions) + "\t" + row, fastq, basename, absolute).c_str());
+      cols.emit_row(">" + std::to_string(max_positions) + "\t" + row, fastq);
     }
-    rows.clear();
   }
   std::fflush(stdout);
   return 0;
@@ -969,7 +667,7 @@ static std::vector<FaPosition> fa_positions(const std::string& pos_in) {
   if (lower.size() >= 4 && lower.compare(lower.size() - 4, 4, ".bcf") == 0)
     quit_error("BCF position files are not supported: " + pos_in + " (give chr:pos, or a text file: BED, VCF, TSV)", 1);
   std::string text;
-  if (!fa_read_text(pos_in, &text)) quit_error("Unable to open file: " + pos_in, 2);
+  if (!fa_read_text(pos_in, &text)) quit_unable_to_open(pos_in, 2);
   const char* seps = "\t: ";
   size_t at = 0;
   for (long long n = 1; at < text.size(); ++n) {
@@ -1038,14 +736,14 @@ static bool fa_key_less(const FaSortKey& a, const FaSortKey& b) {
 }
 
 static int cmd_fa_gc(const std::vector<std::string>& params) {
-  auto help = [](FILE* f) {
-    std::fputs("Calculate GC content surrouding a location\n\nUsage:\n  fa-gc [options] fasta [windows ...]\n\nArguments:\n"
-               "  fasta            Input FASTA (plain, .gz or BGZF)\n"
-               "  [windows ...]    sequence length up and downstream (50 --> ~100bp window [see docs])\n\nOptions:\n"
-               "  -p, --pos=POS              VCF, BED, or string position (e.g. chr1:8675309)\n"
-               "  -h, --help                 Show this help\n", f);
-  };
-  if (params.size() == 1) { help(stdout); return 0; }
+  static const char* const help =
+      "Calculate GC content surrouding a location\n\nUsage:\n  fa-gc [options] fasta [windows ...]\n\nArguments:\n"
+      "  fasta            Input FASTA (plain, .gz or BGZF)\n"
+      "  [windows ...]    sequence length up and downstream (50 --> ~100bp window [see docs])\n\nOptions:\n"
+      "  -p, --pos=POS              VCF, BED, or string position (e.g. chr1:8675309)\n"
+      "  -h, --help                 Show this help\n";
+  if (params.size() == 1) { std::fputs(help, stdout); return 0; }
+  // the reference's grammar (-p X / -p=X / --pos X / --pos=X: a value in the next argument), so not a table for parse_options()
   std::string pos_in;
   std::vector<std::string> args;
   bool only_positional = false;
@@ -1053,15 +751,15 @@ static int cmd_fa_gc(const std::vector<std::string>& params) {
     const std::string& a = params[i];
     if (only_positional || a.empty() || a[0] != '-' || a == "-") { args.push_back(a); continue; }
     if (a == "--") { only_positional = true; continue; }
-    if (a == "-h" || a == "--help") { help(stdout); return 0; }
+    if (a == "-h" || a == "--help") { std::fputs(help, stdout); return 0; }
     if (a == "-p" || a == "--pos") {
-      if (i + 1 >= params.size()) { help(stdout); quit_error("Error: Missing value for " + a, 1); }
+      if (i + 1 >= params.size()) usage_error(help, "Missing value for " + a);
       pos_in = params[++i];
     } else if (a.compare(0, 6, "--pos=") == 0) pos_in = a.substr(6);
     else if (a.compare(0, 3, "-p=") == 0) pos_in = a.substr(3);
-    else { help(stdout); quit_error("Error: Unknown option: " + a, 1); }
+    else unknown_option(help, a);
   }
-  if (args.empty()) { help(stdout); quit_error("Error: Missing FASTA", 1); }
+  if (args.empty()) usage_error(help, "Missing FASTA");
   if (pos_in.empty()) quit_error("Must provide --pos: (chr:100 / bed / vcf )", 1);
   if (args.size() < 2) quit_error("Must provide a list of windows: (e.g. 100 200 500)", 1);
   const std::string fasta = args[0];
@@ -1081,13 +779,8 @@ static int cmd_fa_gc(const std::vector<std::string>& params) {
 
   scfq_fa_index* index = nullptr;
   const int rc = scfq_fa_index_file(fasta.c_str(), nullptr, &index, nullptr);
-  if (rc == SCFQ_EOPEN) quit_error("Unable to open file: " + fasta, 2);
-  if (rc != SCFQ_OK) {
-    std::string msg = scfq_strerror(rc);
-    const char* d = *scfq_fa_error_detail() ? scfq_fa_error_detail() : scfq_last_error_detail();
-    if (d && *d) { msg += ": "; msg += d; }
-    quit_error(msg, 1);
-  }
+  if (rc == SCFQ_EOPEN) quit_unable_to_open(fasta, 2);
+  if (rc != SCFQ_OK) quit_error(library_error(rc, scfq_fa_error_detail()), 1);
   std::string header = "chrom\tpos";
   for (const uint64_t w : windows) header += "\tgc_" + std::to_string(2 * w);
   std::printf("%s\n", header.c_str());
@@ -1114,12 +807,7 @@ static int cmd_fa_gc(const std::vector<std::string>& params) {
   }
   std::vector<scfq_fa_counts> counts(cells.size());
   const int qrc = scfq_fa_count_intervals(index, cells.data(), cells.size(), counts.data());
-  if (qrc != SCFQ_OK) {
-    std::string msg = scfq_strerror(qrc);
-    const char* d = *scfq_fa_error_detail() ? scfq_fa_error_detail() : scfq_last_error_detail();
-    if (d && *d) { msg += ": "; msg += d; }
-    quit_error(msg, 1);
-  }
+  if (qrc != SCFQ_OK) quit_error(library_error(qrc, scfq_fa_error_detail()), 1);
   for (size_t r = 0; r < rows.size(); ++r) {
     std::string line = rows[r]->chrom + "\t" + std::to_string(rows[r]->pos);
     for (size_t k = 0; k < windows.size(); ++k) {
@@ -1136,83 +824,46 @@ static int cmd_fa_gc(const std::vector<std::string>& params) {
   return 0;
 }
 
-int main(int argc, char** argv) {
-  scfq_debug_stage_mark("sc: main entered");
-  signal(SIGPIPE, SIG_IGN);   // sc.nim:45-46
-  std::vector<std::string> params(argv + 1, argv + argc);
-  if (stdin_is_fifo())        // sc.nim:274-284
-    for (auto& p : params)
-      if (p == "-") { p = "STDIN"; break; }
-  if (params.empty() || params[0] == "-h" || params[0] == "--help") { help_top(stdout); return 0; }
-  if (params[0] == "-v" || params[0] == "--version") { std::printf("%s\n", kVersion); return 0; }
-  if (params[0] == "fq-dedup") return cmd_fq_dedup(params);
-  if (params[0] == "fq-meta") return cmd_fq_meta(params);
-  if (params[0] == "fq-readstats") return cmd_fq_readstats(params);
-  if (params[0] == "fq-cycles") return cmd_fq_cycles(params);
-  if (params[0] == "fq-kmers") return cmd_fq_kmers(params);
-  if (params[0] == "fq-adapters") return cmd_fq_adapters(params);
-  if (params[0] == "fq-insert-size") return cmd_fq_insert_size(params);
-  if (params[0] == "fq-merge") return cmd_fq_merge(params);
-  if (params[0] == "fa-gc") return cmd_fa_gc(params);
-  if (params[0] != "fq-count") {
-    help_top(stdout);
-    quit_error("Unknown command: " + params[0] + " (this build provides the FASTQ commands only)", 1);
-  }
-  if (params.size() == 1) { help_fq_count(stdout); return 0; }   // sc.nim:288-290: len <= 1 -> "-h"
-
-  bool header = false, basename = false, absolute = false, stats = false;
-  int jobs = 0;      // 0: not given
+// command "fq-count" (sc.nim:103-116) and the MI355X additions of its help
+static int cmd_fq_count(const std::vector<std::string>& params) {
+  Columns cols;
+  bool debug = false;      // --debug is accepted and ignored
+  int jobs = 0;            // 0: not given
   int shard_rank = -1, shard_world = 0, transport = SCFQ_COMM_RCCL;
   std::string rendezvous;
   std::vector<std::string> files;
   std::vector<int32_t> devices;
-  uint32_t flags = 0;
-  bool only_positional = false;
-  for (size_t i = 1; i < params.size(); ++i) {
-    const std::string& a = params[i];
-    if (only_positional || a.empty() || a[0] != '-' || a == "-") { files.push_back(a); continue; }
-    if (a == "--") { only_positional = true; continue; }
-    if (a == "-h" || a == "--help") { help_fq_count(stdout); return 0; }
-    if (a == "--header") header = true;
-    else if (a == "--basename") basename = true;
-    else if (a == "--absolute") absolute = true;
-    else if (a == "--debug") {}
-    else if (a == "--struct-check") flags |= SCFQ_STRUCT_CHECK;
-    else if (a == "--qual-hist") flags |= SCFQ_QUAL_HIST;
-    else if (a == "--stats") { stats = true; flags |= SCFQ_TIMING; }
-    else if (a.rfind("--jobs=", 0) == 0) jobs = std::max(1, std::atoi(a.substr(7).c_str()));
-    else if (a.rfind("--shard-rank=", 0) == 0) shard_rank = std::atoi(a.substr(13).c_str());
-    else if (a.rfind("--shard-world=", 0) == 0) shard_world = std::atoi(a.substr(14).c_str());
-    else if (a.rfind("--rendezvous=", 0) == 0) rendezvous = a.substr(13);
-    else if (a == "--transport=tcp") transport = SCFQ_COMM_TCP;
-    else if (a == "--transport=rccl") transport = SCFQ_COMM_RCCL;
-    else if (a.rfind("--devices=", 0) == 0) {
-      const std::string list = a.substr(10);
-      size_t p = 0;
-      while (p < list.size()) {
-        size_t q = list.find(',', p);
-        if (q == std::string::npos) q = list.size();
-        devices.push_back(std::atoi(list.substr(p, q - p).c_str()));
-        p = q + 1;
-      }
-    } else if (a.size() >= 2 && a[1] != '-') {
-      for (size_t k = 1; k < a.size(); ++k) {   // combined short flags: -tb
-        if (a[k] == 't') header = true;
-        else if (a[k] == 'b') basename = true;
-        else if (a[k] == 'a') absolute = true;
-        else if (a[k] == 'h') { help_fq_count(stdout); return 0; }
-        else { help_fq_count(stdout); quit_error(std::string("Error: Unknown option: -") + a[k], 1); }
-      }
-    } else {
-      help_fq_count(stdout);
-      quit_error("Error: Unknown option: " + a, 1);   // UsageError funnel, sc.nim:294-298
-    }
-  }
-
-  scfq_opts opts;
-  std::memset(&opts, 0, sizeof opts);
-  opts.struct_size = sizeof opts;
-  opts.flags = flags;
+  scfq_opts opts = fresh<scfq_opts>();
+  // these numbers are read leniently (atoi): what is no number counts as 0
+  auto lenient = [](int* out, int at_least = INT_MIN) {
+    return [out, at_least](std::string& v) { *out = std::max(at_least, std::atoi(v.c_str())); return Reject::none; };
+  };
+  const std::vector<Opt> table = cols.options({
+      opt_flag("debug", 0, &debug),
+      opt_bits("struct-check", &opts.flags, SCFQ_STRUCT_CHECK),
+      opt_bits("qual-hist", &opts.flags, SCFQ_QUAL_HIST),
+      opt_bits("stats", &opts.flags, SCFQ_TIMING),
+      opt_custom("jobs", lenient(&jobs, 1)),
+      opt_custom("shard-rank", lenient(&shard_rank)),
+      opt_custom("shard-world", lenient(&shard_world)),
+      opt_custom("rendezvous", [&](std::string& v) { rendezvous = v; return Reject::none; }),     // (may be empty)
+      opt_custom("transport", [&](std::string& v) {
+        if (v != "tcp" && v != "rccl") return Reject::unknown_option;
+        transport = v == "tcp" ? SCFQ_COMM_TCP : SCFQ_COMM_RCCL;
+        return Reject::none;
+      }),
+      opt_custom("devices", [&](std::string& list) {
+        size_t p = 0;
+        while (p < list.size()) {
+          size_t q = list.find(',', p);
+          if (q == std::string::npos) q = list.size();
+          devices.push_back(std::atoi(list.substr(p, q - p).c_str()));
+          p = q + 1;
+        }
+        return Reject::none;
+      }),
+  });
+  if (!parse_options(params, kHelpFqCount, table, &files)) return 0;
   opts.n_devices = (int32_t)devices.size();
   opts.device_ids = devices.empty() ? nullptr : devices.data();
   if (const char* e = std::getenv("SC_GPU_CHUNK")) opts.chunk_bytes = std::strtoull(e, nullptr, 10);
@@ -1234,10 +885,9 @@ int main(int argc, char** argv) {
     scfq_comm* comm = nullptr;
     const int rc = scfq_comm_init_rendezvous(host.c_str(), port, shard_world, shard_rank, devices[0], transport, 0, &comm);
     if (rc) quit_error(std::string(scfq_strerror(rc)) + ": " + scfq_comm_error_detail(), 1);
-    if (header && shard_rank == 0) std::printf("%s\n", output_header(kHeader, basename, absolute).c_str());
-    else if (!header && files.empty()) quit_error("No FASTQ specified", 3);
+    if (!cols.header || shard_rank == 0) cols.header_or_no_input(kHeader, files.empty());   // (the header comes from rank 0 alone)
     for (const auto& f : files) {
-      const FileResult r = fq_count_compute(f, basename, absolute, opts, stats, comm);
+      const FileResult r = fq_count_compute(f, cols, opts, comm);
       if (r.exit_code || shard_rank == 0) fq_count_emit(r);       // every rank quits with the reference's message on an error
       else if (!r.extra.empty()) std::fputs(r.extra.c_str(), stderr);      // (the additions' stderr lines, e.g. --stats of this rank's share)
     }
@@ -1246,8 +896,7 @@ int main(int argc, char** argv) {
     return 0;
   }
 
-  if (header) std::printf("%s\n", output_header(kHeader, basename, absolute).c_str());   // sc.nim:110-111
-  else if (files.empty()) quit_error("No FASTQ specified", 3);                           // sc.nim:112-113
+  cols.header_or_no_input(kHeader, files.empty());                                       // sc.nim:110-113
   // several devices in one process: their RCCL communicators come up BEFORE the first row (while one is created the library
   // points descriptor 1 at descriptor 2 — RCCL prints a banner on stdout — and a row printed in that window would be lost to
   // stderr); a failure here is reported by the first counting call
@@ -1257,7 +906,7 @@ int main(int argc, char** argv) {
   // kernels): rows still come out in argv order and the first failing file ends the run where the sequential loop would have.
   if (jobs == 0) jobs = devices.size() > 1 ? 1 : (int)std::min<size_t>(2, std::max<size_t>(1, files.size()));
   if (jobs <= 1 || files.size() <= 1) {
-    for (const auto& f : files) fq_count_emit(fq_count_compute(f, basename, absolute, opts, stats));   // sc.nim:114-116
+    for (const auto& f : files) fq_count_emit(fq_count_compute(f, cols, opts));   // sc.nim:114-116
   } else {
     // --jobs=N: up to N files in flight (each a session on its own device context: inflate / read of one file overlaps
     // the scans of the others); rows are still emitted strictly in argv order, and the first failing file ends the
@@ -1274,7 +923,7 @@ int main(int argc, char** argv) {
         for (;;) {
           const size_t i = next.fetch_add(1);
           if (i >= files.size()) return;
-          FileResult r = fq_count_compute(files[i], basename, absolute, opts, stats);
+          FileResult r = fq_count_compute(files[i], cols, opts);
           { std::lock_guard<std::mutex> lk(mu); results[i] = std::move(r); done[i] = 1; }
           cv.notify_all();
         }
@@ -1297,4 +946,24 @@ int main(int argc, char** argv) {
   std::fflush(stderr);
   if (std::getenv("SC_CLEAN_EXIT")) { scfq_shutdown(); return 0; }
   _exit(0);
+}
+
+int main(int argc, char** argv) {
+  scfq_debug_stage_mark("sc: main entered");
+  signal(SIGPIPE, SIG_IGN);   // sc.nim:45-46
+  std::vector<std::string> params(argv + 1, argv + argc);
+  if (stdin_is_fifo())        // sc.nim:274-284
+    for (auto& p : params)
+      if (p == "-") { p = "STDIN"; break; }
+  if (params.empty() || params[0] == "-h" || params[0] == "--help") { help_top(stdout); return 0; }
+  if (params[0] == "-v" || params[0] == "--version") { std::printf("%s\n", kVersion); return 0; }
+  static const struct { const char* name; int (*run)(const std::vector<std::string>&); } commands[] = {
+      {"fq-count", cmd_fq_count},       {"fq-dedup", cmd_fq_dedup},       {"fq-meta", cmd_fq_meta},
+      {"fq-readstats", cmd_fq_readstats}, {"fq-cycles", cmd_fq_cycles},   {"fq-kmers", cmd_fq_kmers},
+      {"fq-adapters", cmd_fq_adapters}, {"fq-insert-size", cmd_fq_insert_size}, {"fq-merge", cmd_fq_merge},
+      {"fa-gc", cmd_fa_gc}};
+  for (const auto& c : commands)
+    if (params[0] == c.name) return c.run(params);
+  help_top(stdout);
+  quit_error("Unknown command: " + params[0] + " (this build provides the FASTQ commands only)", 1);
 }

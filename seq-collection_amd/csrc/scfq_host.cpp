@@ -92,6 +92,17 @@ static int nim_float_to_str(double v, char* f, size_t cap) {
   return m;
 }
 
+// the end of every scfq_format_*: as much of the m bytes of text as fits into buf[cap], always terminated; the full length
+// comes back, so a call without a buffer is the sizing call
+static int copy_out(const char* text, int m, char* buf, uint64_t cap) {
+  if (buf && cap) {
+    const uint64_t ncopy = ((uint64_t)m < cap - 1) ? (uint64_t)m : cap - 1;
+    std::memcpy(buf, text, ncopy);
+    buf[ncopy] = 0;
+  }
+  return m;
+}
+
 int scfq_format_tsv(const scfq_counts* c, char* buf, uint64_t cap) {
   if (!c) return SCFQ_EARG;
   // $(gc_cnt.float / (total_len - n_cnt).float)      src/fq_count.nim:48 (int64 -> float64)
@@ -102,12 +113,7 @@ int scfq_format_tsv(const scfq_counts* c, char* buf, uint64_t cap) {
   const int m = std::snprintf(tmp, sizeof tmp, "%llu\t%s\t%llu\t%llu\t%llu", (unsigned long long)c->reads, f,
                               (unsigned long long)c->gc_bases, (unsigned long long)c->n_bases,
                               (unsigned long long)c->bases);
-  if (buf && cap) {
-    const uint64_t ncopy = ((uint64_t)m < cap - 1) ? (uint64_t)m : cap - 1;
-    std::memcpy(buf, tmp, ncopy);
-    buf[ncopy] = 0;
-  }
-  return m;
+  return copy_out(tmp, m, buf, cap);
 }
 
 // the fq-readstats row: mean_len and mean_qual by the same `$float` rule
@@ -121,12 +127,7 @@ int scfq_format_read_stats_tsv(const scfq_read_summary* s, char* buf, uint64_t c
                               (unsigned long long)s->bases, (unsigned long long)s->min_len, (unsigned long long)s->max_len, ml,
                               (unsigned long long)s->n50, (unsigned long long)s->l50, (unsigned long long)s->n90,
                               (unsigned long long)s->l90, mq);
-  if (buf && cap) {
-    const uint64_t ncopy = ((uint64_t)m < cap - 1) ? (uint64_t)m : cap - 1;
-    std::memcpy(buf, tmp, ncopy);
-    buf[ncopy] = 0;
-  }
-  return m;
+  return copy_out(tmp, m, buf, cap);
 }
 
 // the fq-cycles row: other = bases - a - c - g - t - n, mean_qual by the same `$float` rule
@@ -139,12 +140,7 @@ int scfq_format_cycle_row_tsv(const scfq_cycle_row* r, char* buf, uint64_t cap) 
                               (unsigned long long)r->a, (unsigned long long)r->c, (unsigned long long)r->g, (unsigned long long)r->t,
                               (unsigned long long)r->n, (unsigned long long)(r->bases - r->a - r->c - r->g - r->t - r->n),
                               (unsigned long long)r->quals, mq);
-  if (buf && cap) {
-    const uint64_t ncopy = ((uint64_t)m < cap - 1) ? (uint64_t)m : cap - 1;
-    std::memcpy(buf, tmp, ncopy);
-    buf[ncopy] = 0;
-  }
-  return m;
+  return copy_out(tmp, m, buf, cap);
 }
 
 // the fq-kmers row: the k letters of the index, first base first, and the count
@@ -153,12 +149,7 @@ int scfq_format_kmer_tsv(uint32_t k, uint64_t index, uint64_t count, char* buf, 
   char tmp[64];
   for (uint32_t i = 0; i < k; ++i) tmp[i] = "ACGT"[(index >> (2 * (k - 1 - i))) & 3u];
   const int m = (int)k + std::snprintf(tmp + k, sizeof tmp - k, "\t%llu", (unsigned long long)count);
-  if (buf && cap) {
-    const uint64_t ncopy = ((uint64_t)m < cap - 1) ? (uint64_t)m : cap - 1;
-    std::memcpy(buf, tmp, ncopy);
-    buf[ncopy] = 0;
-  }
-  return m;
+  return copy_out(tmp, m, buf, cap);
 }
 
 // the built-in probes of fq-adapters: the names and 12-mers the common QC tools use
@@ -186,12 +177,7 @@ int scfq_format_adapter_row_tsv(const scfq_adapter_row* r, uint32_t n_probes, ui
     else m += nim_float_to_str(100.0 * (double)v / (double)reads, tmp + m, 96);
   }
   tmp[m] = 0;
-  if (buf && cap) {
-    const uint64_t ncopy = ((uint64_t)m < cap - 1) ? (uint64_t)m : cap - 1;
-    std::memcpy(buf, tmp, ncopy);
-    buf[ncopy] = 0;
-  }
-  return m;
+  return copy_out(tmp, m, buf, cap);
 }
 
 // the fq-insert-size row.  The variance's numerator is exact (128 bits) and becomes a double once, so a checker with big integers
@@ -209,12 +195,7 @@ int scfq_format_insert_size_tsv(const scfq_insert_summary* s, char* buf, uint64_
                               (unsigned long long)s->overlapped, pct, (unsigned long long)s->min_insert, (unsigned long long)s->median_insert,
                               mean, sd, (unsigned long long)s->mode_insert, (unsigned long long)s->max_insert,
                               (unsigned long long)s->read_through, mr);
-  if (buf && cap) {
-    const uint64_t ncopy = ((uint64_t)m < cap - 1) ? (uint64_t)m : cap - 1;
-    std::memcpy(buf, tmp, ncopy);
-    buf[ncopy] = 0;
-  }
-  return m;
+  return copy_out(tmp, m, buf, cap);
 }
 
 // the fq-merge row: integers but for the share of merged pairs
@@ -227,12 +208,7 @@ int scfq_format_merge_stats_tsv(const scfq_merge_stats* s, char* buf, uint64_t c
   char tmp[1024];
   int m = std::snprintf(tmp, sizeof tmp, "%llu\t%llu\t%s", (unsigned long long)s->pairs, (unsigned long long)s->merged, pct);
   for (const uint64_t v : tail) m += std::snprintf(tmp + m, sizeof tmp - m, "\t%llu", (unsigned long long)v);
-  if (buf && cap) {
-    const uint64_t ncopy = ((uint64_t)m < cap - 1) ? (uint64_t)m : cap - 1;
-    std::memcpy(buf, tmp, ncopy);
-    buf[ncopy] = 0;
-  }
-  return m;
+  return copy_out(tmp, m, buf, cap);
 }
 
 const char* scfq_strerror(int rc) {
