@@ -630,6 +630,114 @@ int scfq_merge_files(const char* path1, const char* path2, const scfq_opts* opts
 int scfq_format_merge_stats_tsv(const scfq_merge_stats* s, char* buf, uint64_t cap);
 const char* scfq_merge_error_detail(void);       /* static, thread-local */
 
+/* ---- `sc fq-trim` (addition, not in the reference): adapter, poly-G, quality and overlap trimming of the 3' ends ---------
+ * Inputs are one FASTQ (single-end), two FASTQs (record i of each is pair i, pairs = min(reads1, reads2), unpaired the
+ * difference) or, with SCFQ_TRIM_INTERLEAVED, one interleaved FASTQ (records 2i and 2i+1). Lines, records and texts are
+ * those of fq-readstats above; a line the input does not have is empty. For a read, S is the text of its sequence line
+ * (length L), Q that of its quality line (length LQ), q(i) = Q[i] - Q0 as a SIGNED integer and 0 for i >= LQ, Q0 being
+ * phred_offset, 33 or 64.
+ * A read with L > SCFQ_TRIM_MAX_LEN is too_long: no step looks at it and its record is echoed as fq-dedup echoes a kept
+ * record (each line the record has as text + '\n'). Every other read gets ONE cut point e, starting at e = L; the steps
+ * lower it in this order and each sees the read as S[0, e):
+ *  1 Overlap (paired input, unless SCFQ_TRIM_NO_OVERLAP). The offset d* of fq-insert-size above is looked for with
+ *    min_overlap / max_mismatches / max_mismatch_pct (defaults 30 / 5 / 20, the same ranges). A pair with an accepted
+ *    offset has the insert s = d* + Lb, and both mates get e = min(L, s). A pair with a too-long mate has no offset.
+ *  2 Adapters. 0 .. SCFQ_TRIM_MAX_PROBES probes of 1 .. 32 letters, each exactly 'A', 'C', 'G' or 'T' (the default set:
+ *    scfq_adapters_default without the entries whose names begin with "poly", five probes). Probe j of length m matches
+ *    at p in [0, e) iff t = min(m, e - p) >= min_adapter_overlap (1 .. 32, default 5) and, mm being the number of k in
+ *    [0, t) with S[p+k] != probe[k] (byte for byte: 'N' and lower case are mismatches), 100 * mm <= adapter_mismatch_pct
+ *    * t (0 .. 100, default 10). e becomes the smallest p at which a probe matches; adapter_reads[j] counts the read
+ *    for the lowest j that matches there.
+ *  3 Poly-G tail (poly_g, 0 = off, the default; 1 .. 512). g is the length of the longest suffix of S[0, e) that is all
+ *    'G'; if g >= poly_g then e -= g.
+ *  4 Quality window (window 1 .. 32, default 4; window_quality 0 .. 93, 0 = off, the default). p is the smallest
+ *    position with p + window <= e and q(p) + .. + q(p + window - 1) < window_quality * window; if there is one, e = p.
+ *  5 Minimum length (min_length 0 .. 512, default 15). A read with e < min_length is short. A short single-end read is
+ *    dropped; a pair is dropped when either mate is short. A too-long read is never short.
+ * The record of a kept read that is not too long: the header text, '\n', S[0, e), '\n', the text of the separator line,
+ * '\n', Q[0, min(LQ, e)), '\n' — always four lines ("\r\n" comes out as '\n', a last line without a newline gains one).
+ * Records keep their input order. Two inputs give out1 and out2, interleaved input one output (mate 1, then mate 2),
+ * single-end input one output. Records counted in `unpaired` go nowhere and are counted nowhere else.
+ * All values are integers and exact. Device pipeline over the HBM-resident inputs: line index (K5) of each, P1 of
+ * fq-insert-size (the same kernel) for paired input, T1 — a wave per read: the read as bit planes, the probes against
+ * every position by shifts and population counts, poly-G from the planes, the window sums from a wave prefix sum; 8 bytes
+ * per read —, T2 — a thread per read or pair: output lengths per group of 32 and the statistics —, one exclusive scan per
+ * output, and T3 — a wave per group: the records copied or written as their four pieces. */
+#define SCFQ_TRIM_MAX_LEN      SCFQ_INSERT_MAX_LEN
+#define SCFQ_TRIM_MAX_PROBES   8
+#define SCFQ_TRIM_INTERLEAVED  0x1u
+#define SCFQ_TRIM_NO_OVERLAP   0x2u
+#define SCFQ_TRIM_NO_ADAPTERS  0x4u
+typedef struct scfq_trim_opts {     /* 128 bytes */
+  uint64_t struct_size;             /* sizeof(scfq_trim_opts) */
+  uint32_t flags;                   /* SCFQ_TRIM_INTERLEAVED | SCFQ_TRIM_NO_OVERLAP | SCFQ_TRIM_NO_ADAPTERS */
+  uint32_t min_overlap;
+  uint32_t max_mismatches;
+  uint32_t max_mismatch_pct;
+  uint32_t min_adapter_overlap;
+  uint32_t adapter_mismatch_pct;
+  uint32_t poly_g;
+  uint32_t window;
+  uint32_t window_quality;
+  uint32_t min_length;
+  uint32_t phred_offset;            /* 33 or 64 */
+  uint32_t n_probes;                /* 0 without SCFQ_TRIM_NO_ADAPTERS: the default set; with it: must be 0 */
+  uint32_t reserved[2];             /* 0 */
+  const char* probes[SCFQ_TRIM_MAX_PROBES];   /* entries [0, n_probes), NUL-terminated; the rest is not looked at */
+} scfq_trim_opts;
+
+typedef struct scfq_trim_stats {       /* 49 x 8 bytes */
+  uint64_t struct_size;   /* caller sets to sizeof(scfq_trim_stats) before the call */
+  uint64_t abi_version;   /* library writes SCFQ_ABI_VERSION */
+  uint64_t reads1, reads2;             /* as scfq_insert_summary, down to `unpaired`; single-end: reads2 = pairs = unpaired = 0 */
+  uint64_t lines1, lines2;
+  uint64_t input_bytes1, input_bytes2;
+  uint64_t pairs, unpaired;
+  uint64_t reads_in, reads_out;        /* reads_in: reads1, or 2 * pairs; reads_in = reads_out + dropped_reads */
+  uint64_t too_long;                   /* reads */
+  uint64_t short_reads;                /* reads with e < min_length */
+  uint64_t dropped_reads;              /* paired input: every read of a dropped pair */
+  uint64_t bases_in, bases_out;        /* sums of L over reads_in and of e over reads_out */
+  uint64_t cut_overlap, cut_adapter, cut_polyg, cut_quality;          /* reads the step lowered */
+  uint64_t bases_overlap, bases_adapter, bases_polyg, bases_quality;  /* bases the step removed */
+  uint64_t adapter_reads[SCFQ_TRIM_MAX_PROBES];   /* sum = cut_adapter */
+  uint64_t bases_dropped;              /* sum of e over dropped reads (L for a too-long one) */
+  uint64_t overlapped_pairs;           /* pairs with an accepted offset */
+  uint64_t out1_bytes, out2_bytes;     /* sizes of the outputs, written or not */
+  uint64_t flags, min_overlap, max_mismatches, max_mismatch_pct, min_adapter_overlap, adapter_mismatch_pct, poly_g, window,
+      window_quality, min_length, phred_offset, n_probes;   /* the parameters as used */
+} scfq_trim_stats;
+
+/* r1 / r2 in host (is_device = 0) or device memory, both of one kind; r2 = NULL with n2 = 0: single-end input or, with
+ * SCFQ_TRIM_INTERLEAVED, the interleaved one (the flag with a second buffer is SCFQ_EARG). opts = NULL: the defaults. The
+ * outputs are both host (out_is_device = 0) or both device memory. An output pointer of NULL with capacity 0 is not
+ * written; its size is reported in stats all the same, so a call with two NULLs is the sizing call. An output that is too
+ * small returns SCFQ_EARG with text naming the output and both sizes: stats is filled, every field, and NO byte is written
+ * to ANY output (T3 compares the scanned totals with the capacities before it stores). out2 without a second input is
+ * SCFQ_EARG, with text. SCFQ_EARG for a NULL stats or a wrong struct_size (stats' or opts'), a NULL input with n > 0, a
+ * NULL output with a capacity; with text in scfq_trim_error_detail(): unknown flag bits, a parameter out of range,
+ * phred_offset other than 33 or 64, reserved not 0, more than SCFQ_TRIM_MAX_PROBES probes, probes together with
+ * SCFQ_TRIM_NO_ADAPTERS, a NULL, empty or too long probe, a probe byte that is not A C G T. Device pointers follow the
+ * scfq_set_wait_stream contract of scfq_index_lines. One device, inputs and outputs whole and resident, fewer than 2^31
+ * records per input, as scfq_merge_buffers; there is no CPU fallback (SCFQ_EHIP without a device). */
+int scfq_trim_buffers(const void* r1, uint64_t n1, const void* r2, uint64_t n2, int is_device, const scfq_trim_opts* opts,
+                      void* out1, uint64_t cap1, void* out2, uint64_t cap2, int out_is_device, scfq_trim_stats* stats);
+/* path2 = NULL: path1 is single-end or, with SCFQ_TRIM_INTERLEAVED in topts, interleaved (the flag with a path2 is
+ * SCFQ_EARG; so is an out2_fd >= 0 without a path2). Stages the whole (inflated) inputs with scfq_stage_file, ".gz" and
+ * BGZF by suffix as everywhere else. A descriptor below 0: that output is not produced (its size is still in stats). The
+ * outputs are written one after another, each in full: out1, then out2. A reader that has gone away is SCFQ_EPIPE and any
+ * other failing write SCFQ_EIO, text in scfq_trim_error_detail(), as scfq_merge_files; stats is complete then. */
+int scfq_trim_files(const char* path1, const char* path2, const scfq_opts* opts, const scfq_trim_opts* topts, int out1_fd,
+                    int out2_fd, scfq_trim_stats* stats);
+/* "<reads_in>\t<reads_out>\t<dropped_reads>\t<short_reads>\t<too_long>\t<pairs>\t<unpaired>\t<overlapped_pairs>\t
+ * <bases_in>\t<bases_out>\t<bases_dropped>\t<cut_overlap>\t<bases_overlap>\t<cut_adapter>\t<bases_adapter>\t<cut_polyg>\t
+ * <bases_polyg>\t<cut_quality>\t<bases_quality>\t<adapter_reads>\t<out1_bytes>\t<out2_bytes>" without trailing newline,
+ * all integers; <adapter_reads> is adapter_reads[0 .. n_probes) joined by ',', or "-" without a probe. Returns the number
+ * of bytes needed (excluding NUL); writes at most cap bytes incl. NUL. SCFQ_EARG for a NULL s or n_probes above
+ * SCFQ_TRIM_MAX_PROBES. */
+int scfq_format_trim_stats_tsv(const scfq_trim_stats* s, char* buf, uint64_t cap);
+const char* scfq_trim_error_detail(void);        /* static, thread-local */
+
 /* ---- `sc fa-gc` (FASTA group): src/fa_gc.nim, docs/fa-gc.md, sc.nim:84-96 --------------------------------------------
  * GC content of the windows [pos - w, pos + w] around 1-based positions of a FASTA. The contract:
  *   Lines.   A header line is a line whose first byte is '>' (a line that starts at byte 0 of the input included); every

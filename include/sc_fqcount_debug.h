@@ -84,6 +84,10 @@ int scfq_debug_insert_size_stages(double* ms, uint32_t cap);
  * kernel — [1..3] are HIP-event times, taken only while SCFQ_MERGE_TIMING=1 is in the environment (zeros otherwise). Writes
  * min(cap, 4) values, returns 4. */
 int scfq_debug_merge_stages(double* ms, uint32_t cap);
+/* Stage times of the calling thread's last scfq_trim_buffers / scfq_trim_files, in milliseconds: ms[0] P1, the overlap kernel (0
+ * for single-end input), ms[1] T1, the decision kernel, ms[2] T2 with its scans, ms[3] T3, the write kernel — HIP-event times,
+ * taken only while SCFQ_TRIM_TIMING=1 is in the environment (zeros otherwise). Writes min(cap, 4) values, returns 4. */
+int scfq_debug_trim_stages(double* ms, uint32_t cap);
 /* Stage times of the calling thread's last scfq_fa_index_buffer / scfq_fa_index_file, in milliseconds: ms[0] F1, the tile scan,
  * ms[1] F2, the scan over the tile records, ms[2] F3, the contig table's kernel, ms[3] unused (0) — HIP-event times, taken only
  * while SCFQ_FA_TIMING=1 is in the environment (zeros otherwise). Writes min(cap, 4) values, returns 4. */

@@ -459,6 +459,131 @@ static int cmd_fq_merge(const std::vector<std::string>& params) {
   return 0;
 }
 
+// command "fq-trim" (addition, not in the reference): IN.fq, R1.fq R2.fq with --out1=PATH --out2=PATH, or --interleaved IN.fq; the
+// trimmed FASTQ of one input goes to stdout; --adapter=NAME:SEQ, --no-adapters, --min-adapter-overlap=N, --adapter-mismatch-pct=N,
+// --poly-g=N, --window=N, --window-quality=N, --min-length=N, --no-overlap-trim, --min-overlap=N, --max-mismatches=N,
+// --max-mismatch-pct=N, --phred-offset=33|64, --stats (header and row of scfq_format_trim_stats_tsv to stderr)
+static const char* kTrimStatsHeader = "reads_in\treads_out\tdropped_reads\tshort_reads\ttoo_long\tpairs\tunpaired\toverlapped_pairs\tbases_in\tbases_out\t"
+                                      "bases_dropped\tcut_overlap\tbases_overlap\tcut_adapter\tbases_adapter\tcut_polyg\tbases_polyg\tcut_quality\t"
+                                      "bases_quality\tadapter_reads\tout1_bytes\tout2_bytes";
+static int cmd_fq_trim(const std::vector<std::string>& params) {
+  static const char* const help =
+      "Cut adapters, poly-G tails, bad quality and read-through off the 3' ends of reads; pairs stay in step\n\nUsage:\n"
+      "  fq-trim [options] IN.fq > out.fq\n  fq-trim [options] --out1=PATH --out2=PATH R1.fq R2.fq\n"
+      "  fq-trim [options] --interleaved IN.fq > out.fq\n\n"
+      "Arguments:\n  IN.fq            One FASTQ: single-end reads, or pairs with --interleaved; the result goes to stdout\n"
+      "  R1.fq R2.fq      Two FASTQs: record i of each is pair i\n\nOptions:\n"
+      "      --interleaved          The one argument is an interleaved FASTQ: records 2i and 2i+1 are pair i\n"
+      "      --out1=PATH            With R1.fq R2.fq: the trimmed mate 1 goes to PATH\n"
+      "      --out2=PATH            With R1.fq R2.fq: the trimmed mate 2 goes to PATH\n"
+      "      --adapter=NAME:SEQ     Cut at SEQ (1 .. 32 letters of A C G T) and call it NAME; up to eight, and giving any\n"
+      "                             replaces the built-in set (Illumina universal and small RNA, Nextera, SOLiD)\n"
+      "      --no-adapters          Look for no adapter\n"
+      "      --min-adapter-overlap=N   Shortest part of an adapter that is cut at the end of a read (default: 5, 1 .. 32)\n"
+      "      --adapter-mismatch-pct=N  Most mismatches in percent of the compared letters (default: 10, 0 .. 100)\n"
+      "      --poly-g=N             Cut a tail of N or more G (default: 0 = off, 1 .. 512)\n"
+      "      --window=N             Width of the quality window (default: 4, 1 .. 32)\n"
+      "      --window-quality=N     Cut at the first window whose mean quality is below N (default: 0 = off, 1 .. 93)\n"
+      "      --min-length=N         Drop a read, or its pair, that is left shorter than N (default: 15, 0 .. 512)\n"
+      "      --no-overlap-trim      Pairs: do not cut read-through found by the overlap of the mates\n"
+      "      --min-overlap=N        Shortest overlap that is accepted (default: 30, 1 .. 512)\n"
+      "      --max-mismatches=N     Most mismatches inside the overlap (default: 5, 0 .. 65535)\n"
+      "      --max-mismatch-pct=N   ... and in percent of the overlap (default: 20, 0 .. 100)\n"
+      "      --phred-offset=N       Quality offset, 33 or 64 (default: 33)\n"
+      "      --stats                Print a header and a row of statistics to stderr\n"
+      "  -h, --help                 Show this help\n";
+  bool stats = false;
+  scfq_trim_opts to = fresh<scfq_trim_opts>();
+  to.min_overlap = 30; to.max_mismatches = 5; to.max_mismatch_pct = 20; to.min_adapter_overlap = 5; to.adapter_mismatch_pct = 10;
+  to.window = 4; to.min_length = 15; to.phred_offset = 33;
+  std::vector<std::string> files, names, seqs;
+  std::string out1, out2;
+  // (no row has a letter: the command has no short options)
+  const std::vector<Opt> table = {
+      opt_bits("interleaved", &to.flags, SCFQ_TRIM_INTERLEAVED),
+      opt_bits("no-overlap-trim", &to.flags, SCFQ_TRIM_NO_OVERLAP),
+      opt_bits("no-adapters", &to.flags, SCFQ_TRIM_NO_ADAPTERS),
+      opt_flag("stats", 0, &stats),
+      opt_text("out1", &out1),
+      opt_text("out2", &out2),
+      opt_custom("adapter", [&](std::string& v) {          // (fq-adapters' rule)
+        const size_t colon = v.find(':');
+        const std::string name = colon == std::string::npos ? "" : v.substr(0, colon), seq = colon == std::string::npos ? "" : v.substr(colon + 1);
+        if (name.empty() || name.find('\t') != std::string::npos || seq.empty() || seq.size() > SCFQ_ADAPTERS_MAX_LEN ||
+            seq.find_first_not_of("ACGT") != std::string::npos || names.size() >= SCFQ_TRIM_MAX_PROBES)
+          return Reject::bad_value;
+        names.push_back(name);
+        seqs.push_back(seq);
+        return Reject::none;
+      }),
+      opt_number("min-adapter-overlap", 6, 1, 32, &to.min_adapter_overlap),
+      opt_number("adapter-mismatch-pct", 6, 0, 100, &to.adapter_mismatch_pct),
+      opt_number("poly-g", 6, 0, SCFQ_TRIM_MAX_LEN, &to.poly_g),
+      opt_number("window", 6, 1, 32, &to.window),
+      opt_number("window-quality", 6, 0, 93, &to.window_quality),
+      opt_number("min-length", 6, 0, SCFQ_TRIM_MAX_LEN, &to.min_length),
+      opt_number("min-overlap", 6, 1, SCFQ_INSERT_MAX_LEN, &to.min_overlap),
+      opt_number("max-mismatches", 6, 0, 65535, &to.max_mismatches),
+      opt_number("max-mismatch-pct", 6, 0, 100, &to.max_mismatch_pct),
+      opt_custom("phred-offset", [&](std::string& v) {     // a number in 33 .. 64 first, then one of the two
+        uint64_t n = 0;
+        if (!bounded_number(v, 6, 33, 64, &n)) return Reject::bad_value;
+        to.phred_offset = (uint32_t)n;
+        if (n == 33 || n == 64) return Reject::none;
+        v = std::to_string(n);                             // (this message shows the number, not the text)
+        return Reject::bad_value;
+      }),
+  };
+  if (!parse_options(params, help, table, &files)) return 0;
+  const bool interleaved = to.flags & SCFQ_TRIM_INTERLEAVED;
+  if (files.empty()) quit_no_fastq();
+  if (files.size() > 2 || (interleaved && files.size() != 1)) usage_error(help, "fq-trim takes one FASTQ, R1.fq and R2.fq, or one FASTQ with --interleaved");
+  const bool two = files.size() == 2;
+  if ((to.flags & SCFQ_TRIM_NO_ADAPTERS) && !names.empty()) usage_error(help, "--no-adapters goes without --adapter=NAME:SEQ");
+  if (two && (out1.empty() || out2.empty())) usage_error(help, "R1.fq R2.fq write to --out1=PATH and --out2=PATH");
+  if (!two && (!out1.empty() || !out2.empty())) usage_error(help, "--out1=PATH and --out2=PATH go with R1.fq R2.fq; one input is written to stdout");
+  to.n_probes = (uint32_t)seqs.size();
+  for (size_t j = 0; j < seqs.size(); ++j) to.probes[j] = seqs[j].c_str();
+  for (const std::string& f : files) require_suffix_room(f);
+  // the inputs are looked at before an output file is made
+  for (const std::string& f : files)
+    if (access(f.c_str(), R_OK) != 0) quit_unable_to_open(f);
+  int fd1 = 1, fd2 = -1;
+  // a call that fails leaves no output file behind: what this process created goes again
+  auto discard = [&]() {
+    // (only a regular file: a FIFO or a device the caller named is the caller's)
+    auto drop = [](int fd, const std::string& p) {
+      struct stat st;
+      const bool regular = fstat(fd, &st) == 0 && S_ISREG(st.st_mode);
+      close(fd);
+      if (regular) unlink(p.c_str());
+    };
+    if (two && fd1 >= 0) drop(fd1, out1);
+    if (two && fd2 >= 0) drop(fd2, out2);
+    fd1 = fd2 = -1;
+  };
+  auto create = [&](const std::string& p) -> int {
+    const int fd = open(p.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
+    if (fd < 0) { discard(); quit_error("Unable to create file: " + p, 1); }
+    return fd;
+  };
+  if (two) { fd1 = -1; fd1 = create(out1); fd2 = create(out2); }
+  scfq_trim_stats st = fresh<scfq_trim_stats>();
+  std::fflush(stdout);
+  const int rc = scfq_trim_files(files[0].c_str(), two ? files[1].c_str() : nullptr, nullptr, &to, fd1, fd2, &st);
+  if (rc != SCFQ_OK && rc != SCFQ_EPIPE) discard();
+  else if (two) { close(fd1); close(fd2); }
+  if (rc == SCFQ_EOPEN) quit_unable_to_open(first_unopenable(files[0], two ? &files[1] : nullptr));
+  if (rc == SCFQ_EPIPE) return 0;              // a reader of stdout that went away: quiet, as `sc fq-dedup | head`
+  if (rc != SCFQ_OK) quit_error(library_error(rc, scfq_trim_error_detail()), 1);
+  if (stats) {
+    char row[1024];
+    scfq_format_trim_stats_tsv(&st, row, sizeof row);
+    std::fprintf(stderr, "%s\n%s\n", kTrimStatsHeader, row);
+  }
+  return 0;
+}
+
 // command "fq-kmers" (addition, not in the reference): -t/--header, -b/--basename, -a/--absolute as fq-count, --k=N, --canonical, --top=N,
 // --totals, [fastq ...]
 static const char* kKmersHeader = "kmer\tcount";
@@ -961,7 +1086,7 @@ int main(int argc, char** argv) {
       {"fq-count", cmd_fq_count},       {"fq-dedup", cmd_fq_dedup},       {"fq-meta", cmd_fq_meta},
       {"fq-readstats", cmd_fq_readstats}, {"fq-cycles", cmd_fq_cycles},   {"fq-kmers", cmd_fq_kmers},
       {"fq-adapters", cmd_fq_adapters}, {"fq-insert-size", cmd_fq_insert_size}, {"fq-merge", cmd_fq_merge},
-      {"fa-gc", cmd_fa_gc}};
+      {"fq-trim", cmd_fq_trim},         {"fa-gc", cmd_fa_gc}};
   for (const auto& c : commands)
     if (params[0] == c.name) return c.run(params);
   help_top(stdout);

@@ -211,6 +211,21 @@ int scfq_format_merge_stats_tsv(const scfq_merge_stats* s, char* buf, uint64_t c
   return copy_out(tmp, m, buf, cap);
 }
 
+// the fq-trim row: integers only; the reads per probe as one field
+int scfq_format_trim_stats_tsv(const scfq_trim_stats* s, char* buf, uint64_t cap) {
+  if (!s || s->n_probes > SCFQ_TRIM_MAX_PROBES) return SCFQ_EARG;
+  const uint64_t head[] = {s->reads_in,     s->reads_out,    s->dropped_reads, s->short_reads, s->too_long,      s->pairs,     s->unpaired,
+                           s->overlapped_pairs, s->bases_in, s->bases_out,     s->bases_dropped, s->cut_overlap, s->bases_overlap, s->cut_adapter,
+                           s->bases_adapter, s->cut_polyg,   s->bases_polyg,   s->cut_quality, s->bases_quality};
+  char tmp[1024];
+  int m = 0;
+  for (const uint64_t v : head) m += std::snprintf(tmp + m, sizeof tmp - m, "%llu\t", (unsigned long long)v);
+  for (uint64_t j = 0; j < s->n_probes; ++j) m += std::snprintf(tmp + m, sizeof tmp - m, j ? ",%llu" : "%llu", (unsigned long long)s->adapter_reads[j]);
+  if (!s->n_probes) m += std::snprintf(tmp + m, sizeof tmp - m, "-");
+  m += std::snprintf(tmp + m, sizeof tmp - m, "\t%llu\t%llu", (unsigned long long)s->out1_bytes, (unsigned long long)s->out2_bytes);
+  return copy_out(tmp, m, buf, cap);
+}
+
 const char* scfq_strerror(int rc) {
   switch (rc) {
     case SCFQ_OK: return "ok";

@@ -54,6 +54,7 @@ EXPORTS = [
     "scfq_insert_size_buffers", "scfq_insert_size_files", "scfq_format_insert_size_tsv", "scfq_insert_size_error_detail",
     "scfq_debug_insert_size_stages",
     "scfq_merge_buffers", "scfq_merge_files", "scfq_format_merge_stats_tsv", "scfq_merge_error_detail", "scfq_debug_merge_stages",
+    "scfq_trim_buffers", "scfq_trim_files", "scfq_format_trim_stats_tsv", "scfq_trim_error_detail", "scfq_debug_trim_stages",
     "scfq_fa_index_buffer", "scfq_fa_index_file", "scfq_fa_contig_at", "scfq_fa_contig_find", "scfq_fa_count_intervals",
     "scfq_fa_index_free", "scfq_fa_error_detail", "scfq_fa_parse_window", "scfq_fa_gc_interval", "scfq_format_fa_gc_value",
     "scfq_debug_fa_stages",
@@ -201,6 +202,27 @@ class MergeOpts(ctypes.Structure):
 class MergeStats(ctypes.Structure):
     """scfq_merge_stats (26 uint64)"""
     _fields_ = [(n, ctypes.c_uint64) for n in MERGE_STATS_FIELDS]
+
+
+SCFQ_TRIM_INTERLEAVED, SCFQ_TRIM_NO_OVERLAP, SCFQ_TRIM_NO_ADAPTERS = 0x1, 0x2, 0x4
+SCFQ_TRIM_MAX_LEN, SCFQ_TRIM_MAX_PROBES = 512, 8
+TRIM_PARAM_FIELDS = ("flags", "min_overlap", "max_mismatches", "max_mismatch_pct", "min_adapter_overlap", "adapter_mismatch_pct", "poly_g", "window",
+                     "window_quality", "min_length", "phred_offset", "n_probes")
+TRIM_STATS_FIELDS = ("struct_size", "abi_version", "reads1", "reads2", "lines1", "lines2", "input_bytes1", "input_bytes2", "pairs", "unpaired",
+                     "reads_in", "reads_out", "too_long", "short_reads", "dropped_reads", "bases_in", "bases_out", "cut_overlap", "cut_adapter",
+                     "cut_polyg", "cut_quality", "bases_overlap", "bases_adapter", "bases_polyg", "bases_quality", "adapter_reads", "bases_dropped",
+                     "overlapped_pairs", "out1_bytes", "out2_bytes") + TRIM_PARAM_FIELDS
+
+
+class TrimOpts(ctypes.Structure):
+    """scfq_trim_opts (128 bytes)"""
+    _fields_ = [("struct_size", ctypes.c_uint64)] + [(n, ctypes.c_uint32) for n in TRIM_PARAM_FIELDS] + \
+               [("reserved", ctypes.c_uint32 * 2), ("probes", ctypes.c_char_p * 8)]
+
+
+class TrimStats(ctypes.Structure):
+    """scfq_trim_stats (49 uint64)"""
+    _fields_ = [(n, ctypes.c_uint64 * 8 if n == "adapter_reads" else ctypes.c_uint64) for n in TRIM_STATS_FIELDS]
 
 
 FA_SUMMARY_FIELDS = ("struct_size", "abi_version", "input_bytes", "tiles", "contigs", "bases", "gc_bases", "acgt_bases", "orphan_bases")
@@ -357,6 +379,13 @@ def lib():
         L.scfq_format_merge_stats_tsv.argtypes = [ctypes.POINTER(MergeStats), ctypes.c_char_p, ctypes.c_uint64]
         L.scfq_merge_error_detail.restype = ctypes.c_char_p
         L.scfq_debug_merge_stages.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]
+        L.scfq_trim_buffers.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(TrimOpts),
+                                        ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(TrimStats)]
+        L.scfq_trim_files.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_void_p, ctypes.POINTER(TrimOpts), ctypes.c_int, ctypes.c_int,
+                                      ctypes.POINTER(TrimStats)]
+        L.scfq_format_trim_stats_tsv.argtypes = [ctypes.POINTER(TrimStats), ctypes.c_char_p, ctypes.c_uint64]
+        L.scfq_trim_error_detail.restype = ctypes.c_char_p
+        L.scfq_debug_trim_stages.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]
         L.scfq_fa_index_buffer.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, pvp, ctypes.POINTER(FaSummary)]
         L.scfq_fa_index_file.argtypes = [ctypes.c_char_p, ctypes.c_void_p, pvp, ctypes.POINTER(FaSummary)]
         L.scfq_fa_contig_at.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(FaContig)]
@@ -964,6 +993,93 @@ def merge_stages():
     HIP-event times and zeros unless SCFQ_MERGE_TIMING=1 is in the environment"""
     ms = (ctypes.c_double * 4)()
     lib().scfq_debug_merge_stages(ms, 4)
+    return list(ms)
+
+
+def _new_trim_stats():
+    s = TrimStats()
+    s.struct_size = ctypes.sizeof(TrimStats)
+    return s
+
+
+def trim_opts(interleaved=False, no_overlap=False, no_adapters=False, probes=None, min_overlap=30, max_mismatches=5, max_mismatch_pct=20,
+              min_adapter_overlap=5, adapter_mismatch_pct=10, poly_g=0, window=4, window_quality=0, min_length=15, phred_offset=33):
+    """probes: None (the built-in set, or none with no_adapters) or up to eight sequences (bytes or str)"""
+    o = TrimOpts()
+    o.struct_size = ctypes.sizeof(TrimOpts)
+    o.flags = (SCFQ_TRIM_INTERLEAVED if interleaved else 0) | (SCFQ_TRIM_NO_OVERLAP if no_overlap else 0) | (SCFQ_TRIM_NO_ADAPTERS if no_adapters else 0)
+    o.min_overlap, o.max_mismatches, o.max_mismatch_pct = min_overlap, max_mismatches, max_mismatch_pct
+    o.min_adapter_overlap, o.adapter_mismatch_pct, o.poly_g = min_adapter_overlap, adapter_mismatch_pct, poly_g
+    o.window, o.window_quality, o.min_length, o.phred_offset = window, window_quality, min_length, phred_offset
+    seqs = [p.encode() if isinstance(p, str) else bytes(p) for p in (probes or ())]
+    o.n_probes = len(seqs)
+    for j, p in enumerate(seqs[:8]):
+        o.probes[j] = p
+    return o
+
+
+def _trim_call(fn, what, opts, head, tail):
+    """opts: None (the library's defaults) or a TrimOpts.  Returns the TrimStats; an ScfqError carries them as `stats` (filled as far
+    as the call got: complete when an output was too small)."""
+    s = _new_trim_stats()
+    rc = fn(*head, ctypes.byref(opts) if opts is not None else None, *tail, ctypes.byref(s))
+    if rc != 0:
+        e = ScfqError(rc, what, lib().scfq_trim_error_detail().decode() or lib().scfq_last_error_detail().decode())
+        e.stats = s
+        raise e
+    return s
+
+
+def _trim_outputs(outs):
+    """two (address, capacity) pairs or None -> the four arguments"""
+    flat = []
+    for o in outs:
+        flat += [ctypes.c_void_p(o[0]) if o and o[0] else None, o[1] if o else 0]
+    return flat
+
+
+def trim_device(ptr1, n1, ptr2=None, n2=0, opts=None, out1=None, out2=None):
+    """fq-trim of device-resident FASTQs; ptr2 = None: ptr1 is single-end or, with the flag in opts, interleaved.  out1 / out2: (device
+    address, capacity) of an output, or None: not written, its size is in the stats all the same (two None: the sizing call)."""
+    return _trim_call(lib().scfq_trim_buffers, "scfq_trim_buffers", opts,
+                      [ctypes.c_void_p(ptr1), n1, ctypes.c_void_p(ptr2) if ptr2 is not None else None, n2, 1], _trim_outputs((out1, out2)) + [1])
+
+
+def trim_host(data1, data2=None, opts=None, caps=None):
+    """fq-trim of host buffers (bytes / numpy uint8); data2 = None: one input.  caps: the capacities of the two outputs (an entry of
+    None: that output is not produced); None: a sizing call first, then buffers that fit.  Returns (TrimStats, out1, out2), the outputs
+    as bytes or None."""
+    a1, n1, keep1 = _host_ptr(data1)
+    a2, n2, keep2 = _host_ptr(data2) if data2 is not None else (None, 0, None)
+    head = [a1, n1, a2, n2, 0]
+    fn = lib().scfq_trim_buffers
+    if caps is None:
+        s = _trim_call(fn, "scfq_trim_buffers", opts, head, [None, 0, None, 0, 0])
+        caps = (s.out1_bytes, s.out2_bytes if data2 is not None else None)
+    bufs = [None if c is None else ctypes.create_string_buffer(max(int(c), 1)) for c in caps]
+    outs = [None if b is None else (ctypes.addressof(b), int(c)) for b, c in zip(bufs, caps)]
+    s = _trim_call(fn, "scfq_trim_buffers", opts, head, _trim_outputs(outs) + [0])
+    sizes = (s.out1_bytes, s.out2_bytes)
+    return (s,) + tuple(None if b is None else b.raw[:int(k)] for b, k in zip(bufs, sizes))
+
+
+def trim_file(path1, path2=None, opts=None, out1_fd=-1, out2_fd=-1):
+    """path2 = None: one input.  A descriptor below 0: that output is not produced.  The outputs are written one after the other."""
+    return _trim_call(lib().scfq_trim_files, "scfq_trim_files", opts,
+                      [os.fsencode(path1), os.fsencode(path2) if path2 is not None else None, None], [out1_fd, out2_fd])
+
+
+def format_trim_stats_tsv(s):
+    buf = ctypes.create_string_buffer(1024)
+    lib().scfq_format_trim_stats_tsv(ctypes.byref(s), buf, 1024)
+    return buf.value.decode()
+
+
+def trim_stages():
+    """(overlap kernel, decision kernel, lengths and scans, write kernel) milliseconds of this thread's last trim call: HIP-event times,
+    zeros unless SCFQ_TRIM_TIMING=1 is in the environment"""
+    ms = (ctypes.c_double * 4)()
+    lib().scfq_debug_trim_stages(ms, 4)
     return list(ms)
 
 
