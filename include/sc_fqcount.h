@@ -738,6 +738,142 @@ int scfq_trim_files(const char* path1, const char* path2, const scfq_opts* opts,
 int scfq_format_trim_stats_tsv(const scfq_trim_stats* s, char* buf, uint64_t cap);
 const char* scfq_trim_error_detail(void);        /* static, thread-local */
 
+/* ---- `sc fq-screen` (addition, not in the reference): k-mer contaminant screen and filter ----------------------------------
+ * Which reads share k-mers with one of up to SCFQ_SCREEN_MAX_REFS named references, and optionally the reads that match
+ * none of them (or, with SCFQ_SCREEN_KEEP_MATCHED, only those that match). Pairs stay in step.
+ * References. 1 .. 16 references, reference r with a name of 1 .. 63 bytes without tab, newline or ':'; two references
+ *  may not share a name. A reference is FASTA text by the fa-gc rule below: a header line is a line whose first byte is
+ *  '>', every other line is a sequence line. A sequence byte is a byte 0x21 .. 0x7E of a sequence line (fa-gc's base: '\r'
+ *  and blanks are none); 'a' .. 'z' are upper-cased. A contig is the sequence bytes between two header lines (or an end of
+ *  the text); the bytes before the first header line are a contig of their own when there are any. A window is k
+ *  consecutive sequence bytes of one contig: line ends do not break it, a header line does. A window is a k-mer iff every
+ *  byte is then one of A C G T. Its key is the canonical index of fq-kmers above in 64 bits: codes A=0 C=1 G=2 T=3, first
+ *  base most significant, key = min(index, index of the reverse complement); k = 8 .. SCFQ_SCREEN_MAX_K, default 31. The
+ *  index is the set of keys, each with a 16-bit mask of the references that contain it. The sequence bytes of all
+ *  references together are at most SCFQ_SCREEN_MAX_REF_BASES; a reference without a sequence byte is an error, one with
+ *  fewer than k is not (it has no k-mer).
+ * Reads. Lines, records and texts are those of fq-readstats above; S is the text of the sequence line, L its length (below
+ *  2^32, otherwise unlimited). A read has max(0, L - k + 1) windows; a window is a k-mer iff every byte is EXACTLY 'A', 'C',
+ *  'G' or 'T' (lower case and 'N' are not, as in fq-kmers and fq-trim), otherwise it is skipped. hits[r] is the number of
+ *  the read's k-mers whose key is in the index with bit r. Reference r MATCHES the read iff hits[r] >= max(1, min_hits)
+ *  (1 .. 65535, default 1) and 100 * hits[r] >= min_hit_pct * kmers (0 .. 100, default 0), kmers being the read's own number
+ *  of k-mers. The read's mask is the set of matching references; best is the matching reference with the most hits, the
+ *  lowest index on a tie, 0xFF without one (best_hits is then 0). A read with L < k has mask 0 and is a short read. A
+ *  pair is matched iff either mate's mask is not 0; a single-end read iff its own is.
+ * Outputs. out1 / out2 receive the records of the reads or pairs that are NOT matched (with SCFQ_SCREEN_KEEP_MATCHED: that
+ *  are), in input order, each echoed as fq-dedup echoes a kept record: each line the record has as text + '\n'. Input
+ *  forms and pairing are fq-trim's: one FASTQ; two (pairs = min(reads1, reads2), the rest `unpaired`, counted nowhere
+ *  else); one interleaved FASTQ with SCFQ_SCREEN_INTERLEAVED (both mates to out1, no out2).
+ * All values are integers and exact. Device pipeline: S0 on the host (the references into one upper-cased byte string with
+ *  a separator between contigs), S1 — a thread per run of positions rolls both strands and inserts min(fwd, rc) into an
+ *  open-addressing table of 64-bit keys (compare-and-swap, linear probing) and ORs the reference's bit into the slot's mask
+ *  word —, a counting pass over the slots; per call: line index (K5), S2 — a wave per read: the read as 2-bit codes and an
+ *  invalid-bit plane in LDS, every lane its windows by a funnel shift, a bit prefilter in LDS in front of the table probe;
+ *  16 bytes per read —, S3 — a thread per read or pair: keep or not, output lengths per group of 32, the statistics —, one
+ *  exclusive scan per output, S4 — a wave per group copies the kept records. Every probe loop is bounded by the number of
+ *  slots and the table always has an empty slot. */
+#define SCFQ_SCREEN_MAX_REFS       16
+#define SCFQ_SCREEN_MAX_K          32
+#define SCFQ_SCREEN_MAX_REF_BASES  (1ull << 27)
+#define SCFQ_SCREEN_INTERLEAVED    0x1u
+#define SCFQ_SCREEN_KEEP_MATCHED   0x2u
+typedef struct scfq_screen_index scfq_screen_index;   /* opaque: the table on the device, names and per-reference numbers on the host */
+typedef struct scfq_screen_ref {
+  const char* name;      /* NUL-terminated */
+  const void* text;      /* host memory: the FASTA text */
+  uint64_t n;
+} scfq_screen_ref;
+typedef struct scfq_screen_ref_summary {
+  uint64_t contigs, bases, windows, kmers;
+  uint64_t distinct;     /* slots with bit r */
+  uint64_t shared;       /* slots with bit r and another bit */
+} scfq_screen_ref_summary;
+typedef struct scfq_screen_summary {   /* 6 + 16 x 6 words */
+  uint64_t struct_size;   /* caller sets to sizeof(scfq_screen_summary) before the call */
+  uint64_t abi_version;   /* library writes SCFQ_ABI_VERSION */
+  uint64_t n_refs, k;
+  uint64_t distinct;      /* keys of the index */
+  uint64_t slots;         /* of the table: a power of two, >= 1024, > the windows of all references */
+  scfq_screen_ref_summary ref[SCFQ_SCREEN_MAX_REFS];
+} scfq_screen_summary;
+typedef struct scfq_screen_opts {
+  uint64_t struct_size;   /* sizeof(scfq_screen_opts) */
+  uint32_t flags;         /* SCFQ_SCREEN_INTERLEAVED | SCFQ_SCREEN_KEEP_MATCHED */
+  uint32_t min_hits;      /* 1 .. 65535 */
+  uint32_t min_hit_pct;   /* 0 .. 100 */
+  uint32_t reserved;      /* 0 */
+} scfq_screen_opts;
+typedef struct scfq_screen_rec {   /* the per-read table: 16 bytes per read; paired input: mate m of pair p is entry 2p + m */
+  uint32_t kmers;         /* k-mers of the read */
+  uint32_t hit_kmers;     /* of them, those whose key is in the index at all */
+  uint32_t best_hits;     /* hits[best], 0 without a match */
+  uint16_t mask;
+  uint8_t best;           /* 0xFF without a match */
+  uint8_t reserved;       /* 0 */
+} scfq_screen_rec;
+typedef struct scfq_screen_stats {     /* 94 x 8 bytes */
+  uint64_t struct_size;   /* caller sets to sizeof(scfq_screen_stats) before the call */
+  uint64_t abi_version;   /* library writes SCFQ_ABI_VERSION */
+  uint64_t reads1, reads2;             /* as scfq_trim_stats, down to `unpaired` */
+  uint64_t lines1, lines2;
+  uint64_t input_bytes1, input_bytes2;
+  uint64_t pairs, unpaired;
+  uint64_t reads_in, reads_out;        /* reads_in: reads1, or 2 * pairs; reads_in = reads_out + dropped_reads */
+  uint64_t dropped_reads;              /* paired input: every read of a pair that is not written */
+  uint64_t matched_reads;              /* reads with a mask other than 0 */
+  uint64_t matched_pairs;              /* pairs with such a mate; single-end input: 0 */
+  uint64_t multi_reads;                /* reads whose mask has two or more bits */
+  uint64_t short_reads;                /* L < k */
+  uint64_t bases_in, bases_out;        /* sums of L */
+  uint64_t windows, kmers, skipped;    /* windows = kmers + skipped */
+  uint64_t hit_kmers;
+  uint64_t ref_reads[SCFQ_SCREEN_MAX_REFS];        /* reads with bit r */
+  uint64_t ref_only_reads[SCFQ_SCREEN_MAX_REFS];   /* reads whose mask is exactly bit r: sum + multi_reads = matched_reads */
+  uint64_t ref_best_reads[SCFQ_SCREEN_MAX_REFS];   /* sum = matched_reads */
+  uint64_t ref_kmer_hits[SCFQ_SCREEN_MAX_REFS];    /* sum of hits[r] over reads_in */
+  uint64_t out1_bytes, out2_bytes;     /* sizes of the outputs, written or not */
+  uint64_t flags, min_hits, min_hit_pct, k, n_refs;   /* the parameters as used */
+} scfq_screen_stats;
+
+/* Builds the index of n_refs references in HOST memory; sum may be NULL. SCFQ_EARG with text in
+ * scfq_screen_error_detail(), decided before any device call: k outside 8 .. 32, n_refs outside 1 .. 16, a NULL, empty,
+ * too long or repeated name or one with a tab, newline or ':', a NULL text, a reference without a sequence byte, more than
+ * SCFQ_SCREEN_MAX_REF_BASES sequence bytes, a forced table (SCFQ_SCREEN_TABLE_BITS) with no more slots than the
+ * references have windows. SCFQ_EARG without text for a NULL out or a wrong sum->struct_size. *out is NULL after every
+ * failure. The index lives on the device that is current at the call. */
+int scfq_screen_index_buffers(const scfq_screen_ref* refs, uint32_t n_refs, uint32_t k, scfq_screen_index** out,
+                              scfq_screen_summary* sum);
+/* The same from files: ".gz" and BGZF by suffix (the library's readers inflate them), SCFQ_EOPEN for a file that cannot be
+ * opened. names[i] = NULL: the file's base name up to its first '.'. */
+int scfq_screen_index_files(const char* const* names, const char* const* paths, uint32_t n_refs, uint32_t k,
+                            const scfq_opts* opts, scfq_screen_index** out, scfq_screen_summary* sum);
+void scfq_screen_index_free(scfq_screen_index* index);   /* NULL is fine */
+int scfq_screen_index_summary(const scfq_screen_index* index, scfq_screen_summary* sum);
+/* the name of reference r, owned by the index; NULL for a NULL index or r >= n_refs */
+const char* scfq_screen_ref_name(const scfq_screen_index* index, uint32_t r);
+/* r1 / r2, the outputs, the sizing call, a too-small output (SCFQ_EARG naming it, stats complete, NO byte written to ANY
+ * output: S4 compares the scanned totals with the capacities before it stores) and the device-pointer rules are those of
+ * scfq_trim_buffers. recs_device: NULL, or DEVICE memory for rec_cap entries of the per-read table; fewer than reads_in is
+ * SCFQ_EARG with text and nothing is written. SCFQ_EARG with text, before any launch: a NULL index, unknown flag bits,
+ * min_hits or min_hit_pct out of range, reserved not 0, out2 without a second input, a second buffer with
+ * SCFQ_SCREEN_INTERLEAVED. opts = NULL: the defaults. There is no CPU fallback (SCFQ_EHIP without a device). */
+int scfq_screen_buffers(const scfq_screen_index* index, const void* r1, uint64_t n1, const void* r2, uint64_t n2,
+                        int is_device, const scfq_screen_opts* opts, scfq_screen_rec* recs_device, uint64_t rec_cap,
+                        void* out1, uint64_t cap1, void* out2, uint64_t cap2, int out_is_device, scfq_screen_stats* stats);
+/* As scfq_trim_files: staged inputs, descriptors below 0 are not produced, out1 then out2, SCFQ_EPIPE / SCFQ_EIO.
+ * recs_host: NULL, or HOST memory for rec_cap entries of the per-read table. */
+int scfq_screen_files(const scfq_screen_index* index, const char* path1, const char* path2, const scfq_opts* opts,
+                      const scfq_screen_opts* sopts, int out1_fd, int out2_fd, scfq_screen_rec* recs_host, uint64_t rec_cap,
+                      scfq_screen_stats* stats);
+/* One report row, without trailing newline. r < n_refs: "<name>\t<ref_bases>\t<ref_kmers>\t<reads_in>\t<ref_reads[r]>\t
+ * <pct_reads>\t<ref_only_reads[r]>\t<ref_best_reads[r]>\t<ref_kmer_hits[r]>"; r = n_refs, the row "*": "*", the sums of
+ * bases and kmers over the references, reads_in, matched_reads, its percentage, matched_reads - multi_reads, multi_reads,
+ * hit_kmers. pct_reads = 10000 * reads / reads_in in integers (0 for reads_in = 0), printed with two decimals. Returns
+ * the number of bytes needed (excluding NUL); writes at most cap bytes incl. NUL. SCFQ_EARG for a NULL argument, r >
+ * n_refs, or stats of another index (n_refs or k differ). */
+int scfq_format_screen_row_tsv(const scfq_screen_stats* s, const scfq_screen_index* index, uint32_t r, char* buf, uint64_t cap);
+const char* scfq_screen_error_detail(void);      /* static, thread-local */
+
 /* ---- `sc fa-gc` (FASTA group): src/fa_gc.nim, docs/fa-gc.md, sc.nim:84-96 --------------------------------------------
  * GC content of the windows [pos - w, pos + w] around 1-based positions of a FASTA. The contract:
  *   Lines.   A header line is a line whose first byte is '>' (a line that starts at byte 0 of the input included); every

@@ -88,6 +88,13 @@ int scfq_debug_merge_stages(double* ms, uint32_t cap);
  * for single-end input), ms[1] T1, the decision kernel, ms[2] T2 with its scans, ms[3] T3, the write kernel — HIP-event times,
  * taken only while SCFQ_TRIM_TIMING=1 is in the environment (zeros otherwise). Writes min(cap, 4) values, returns 4. */
 int scfq_debug_trim_stages(double* ms, uint32_t cap);
+/* Stage times of the calling thread's last scfq_screen_buffers / scfq_screen_files, in milliseconds: ms[0] the line indexes of
+ * paired input (host clock, 0 for single-end input), ms[1] S2, the lookup kernel, ms[2] S3 with its scans, ms[3] S4, the write
+ * kernel — the last three HIP-event times, taken only while SCFQ_SCREEN_TIMING=1 is in the environment (zeros otherwise). Writes
+ * min(cap, 4) values, returns 4. */
+int scfq_debug_screen_stages(double* ms, uint32_t cap);
+/* S1, the build kernel of that index, in milliseconds by HIP events; 0 for a NULL index. */
+double scfq_debug_screen_build_ms(const scfq_screen_index* index);
 /* Stage times of the calling thread's last scfq_fa_index_buffer / scfq_fa_index_file, in milliseconds: ms[0] F1, the tile scan,
  * ms[1] F2, the scan over the tile records, ms[2] F3, the contig table's kernel, ms[3] unused (0) — HIP-event times, taken only
  * while SCFQ_FA_TIMING=1 is in the environment (zeros otherwise). Writes min(cap, 4) values, returns 4. */

@@ -584,6 +584,134 @@ static int cmd_fq_trim(const std::vector<std::string>& params) {
   return 0;
 }
 
+// command "fq-screen" (addition, not in the reference): --ref=NAME:PATH (or --ref=PATH) up to 16 times, then IN.fq, R1.fq R2.fq or
+// --interleaved IN.fq; the report goes to stdout, reads only where --out / --out1 / --out2 say; --k=N, --min-hits=N, --min-hit-pct=N,
+// --keep-matched, --per-read=PATH, -t/--header, -b/--basename, -a/--absolute
+static const char* kScreenHeader = "ref\tref_bases\tref_kmers\treads_in\treads\tpct_reads\tonly_reads\tbest_reads\tkmer_hits";
+static int cmd_fq_screen(const std::vector<std::string>& params) {
+  static const char* const help =
+      "Screen reads for k-mers of reference sequences (spike-ins, vectors, rRNA, another species) and filter by it; pairs stay in step\n\nUsage:\n"
+      "  fq-screen [options] --ref=NAME:PATH [--ref=...] IN.fq\n  fq-screen [options] --ref=... [--out1=PATH --out2=PATH] R1.fq R2.fq\n"
+      "  fq-screen [options] --ref=... --interleaved [--out=PATH] IN.fq\n\n"
+      "Arguments:\n  IN.fq            One FASTQ: single-end reads, or pairs with --interleaved\n"
+      "  R1.fq R2.fq      Two FASTQs: record i of each is pair i\n\nOptions:\n"
+      "      --ref=NAME:PATH        A reference FASTA (all its contigs) and its name in the report; up to 16. --ref=PATH alone:\n"
+      "                             the name is the file's base name up to its first '.'\n"
+      "      --k=N                  Length of the k-mers (default: 31, 8 .. 32)\n"
+      "      --min-hits=N           A reference matches a read that shares N k-mers with it (default: 1, 1 .. 65535)\n"
+      "      --min-hit-pct=N        ... and N percent of the read's own k-mers (default: 0, 0 .. 100)\n"
+      "      --interleaved          The one argument is an interleaved FASTQ: records 2i and 2i+1 are pair i\n"
+      "      --out=PATH             With one FASTQ: the reads, or pairs, that match no reference go to PATH\n"
+      "      --out1=PATH            With R1.fq R2.fq: mate 1 of those pairs goes to PATH\n"
+      "      --out2=PATH            With R1.fq R2.fq: mate 2 of those pairs goes to PATH\n"
+      "      --keep-matched         Write the reads, or pairs, that match a reference instead\n"
+      "      --per-read=PATH        One row per read to PATH: read_index kmers hit_kmers best best_hits mask\n"
+      "  -t, --header               Output the header\n  -b, --basename             Add a column with the basename of the first FASTQ\n"
+      "  -a, --absolute             Add a column with the absolute path of the first FASTQ\n"
+      "  -h, --help                 Show this help\n";
+  Columns cols;
+  scfq_screen_opts so = fresh<scfq_screen_opts>();
+  so.min_hits = 1;
+  uint32_t k = 31;
+  std::vector<std::string> files, names, paths;
+  std::string out, out1, out2, per_read;
+  const std::vector<Opt> table = cols.options({
+      opt_custom("ref", [&](std::string& v) {
+        const size_t colon = v.find(':');
+        std::string name = colon == std::string::npos ? "" : v.substr(0, colon), path = colon == std::string::npos ? v : v.substr(colon + 1);
+        if (colon == std::string::npos) { name = last_path_part(path); name = name.substr(0, name.find('.')); }
+        if (name.empty() || name.size() > 63 || name.find('\t') != std::string::npos || name.find('\n') != std::string::npos || path.empty() ||
+            names.size() >= SCFQ_SCREEN_MAX_REFS)
+          return Reject::bad_value;
+        for (const std::string& n : names) if (n == name) return Reject::bad_value;
+        names.push_back(name);
+        paths.push_back(path);
+        return Reject::none;
+      }),
+      opt_number("k", 6, 8, SCFQ_SCREEN_MAX_K, &k),
+      opt_number("min-hits", 6, 1, 65535, &so.min_hits),
+      opt_number("min-hit-pct", 6, 0, 100, &so.min_hit_pct),
+      opt_bits("interleaved", &so.flags, SCFQ_SCREEN_INTERLEAVED),
+      opt_bits("keep-matched", &so.flags, SCFQ_SCREEN_KEEP_MATCHED),
+      opt_text("out", &out),
+      opt_text("out1", &out1),
+      opt_text("out2", &out2),
+      opt_text("per-read", &per_read),
+  });
+  if (!parse_options(params, help, table, &files)) return 0;
+  const bool interleaved = so.flags & SCFQ_SCREEN_INTERLEAVED;
+  if (names.empty()) usage_error(help, "fq-screen needs a reference: --ref=NAME:PATH");
+  if (files.empty()) quit_no_fastq();
+  if (files.size() > 2 || (interleaved && files.size() != 1)) usage_error(help, "fq-screen takes one FASTQ, R1.fq and R2.fq, or one FASTQ with --interleaved");
+  const bool two = files.size() == 2;
+  if (two && !out.empty()) usage_error(help, "R1.fq R2.fq write to --out1=PATH and --out2=PATH");
+  if (two && out1.empty() != out2.empty()) usage_error(help, "--out1=PATH and --out2=PATH go together");
+  if (!two && (!out1.empty() || !out2.empty())) usage_error(help, "--out1=PATH and --out2=PATH go with R1.fq R2.fq; one input is written to --out=PATH");
+  for (const std::string& f : files) require_suffix_room(f);
+  // the inputs and the references are looked at before an output file is made
+  for (const std::string& f : files)
+    if (access(f.c_str(), R_OK) != 0) quit_unable_to_open(f);
+  for (const std::string& f : paths)
+    if (access(f.c_str(), R_OK) != 0) quit_unable_to_open(f, 2);
+  std::vector<const char*> name_ptrs, path_ptrs;
+  for (size_t r = 0; r < names.size(); ++r) { name_ptrs.push_back(names[r].c_str()); path_ptrs.push_back(paths[r].c_str()); }
+  scfq_screen_index* index = nullptr;
+  scfq_screen_summary sum = fresh<scfq_screen_summary>();
+  int rc = scfq_screen_index_files(name_ptrs.data(), path_ptrs.data(), (uint32_t)names.size(), k, nullptr, &index, &sum);
+  if (rc != SCFQ_OK) quit_error(library_error(rc, scfq_screen_error_detail()), 1);
+  const std::string p1 = two ? out1 : out;
+  int fd1 = -1, fd2 = -1;
+  // a call that fails leaves no output file behind: what this process created goes again (fq-trim's rule)
+  auto discard = [&]() {
+    auto drop = [](int fd, const std::string& p) {
+      struct stat st;
+      const bool regular = fstat(fd, &st) == 0 && S_ISREG(st.st_mode);
+      close(fd);
+      if (regular) unlink(p.c_str());
+    };
+    if (fd1 >= 0) drop(fd1, p1);
+    if (fd2 >= 0) drop(fd2, out2);
+    fd1 = fd2 = -1;
+  };
+  auto create = [&](const std::string& p) -> int {
+    const int fd = open(p.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
+    if (fd < 0) { discard(); quit_error("Unable to create file: " + p, 1); }
+    return fd;
+  };
+  if (!p1.empty()) fd1 = create(p1);
+  if (two && !out2.empty()) fd2 = create(out2);
+  scfq_screen_stats st = fresh<scfq_screen_stats>();
+  const char* path2 = two ? files[1].c_str() : nullptr;
+  std::vector<scfq_screen_rec> recs;
+  if (!per_read.empty()) {
+    // the table's length is the number of reads: a call without outputs tells it (the screen runs twice with --per-read)
+    rc = scfq_screen_files(index, files[0].c_str(), path2, nullptr, &so, -1, -1, nullptr, 0, &st);
+    if (rc == SCFQ_OK) recs.assign((size_t)st.reads_in, scfq_screen_rec());
+    st = fresh<scfq_screen_stats>();
+  }
+  if (rc == SCFQ_OK) rc = scfq_screen_files(index, files[0].c_str(), path2, nullptr, &so, fd1, fd2, recs.empty() ? nullptr : recs.data(), recs.size(), &st);
+  if (rc != SCFQ_OK) discard();
+  else { if (fd1 >= 0) close(fd1); if (fd2 >= 0) close(fd2); }
+  if (rc == SCFQ_EOPEN) quit_unable_to_open(first_unopenable(files[0], two ? &files[1] : nullptr));
+  if (rc != SCFQ_OK) quit_error(library_error(rc, scfq_screen_error_detail()), 1);
+  if (!per_read.empty()) {
+    FILE* f = std::fopen(per_read.c_str(), "w");
+    if (!f) quit_error("Unable to create file: " + per_read, 1);
+    for (size_t i = 0; i < recs.size(); ++i)
+      std::fprintf(f, "%zu\t%u\t%u\t%s\t%u\t%u\n", i, recs[i].kmers, recs[i].hit_kmers, recs[i].best == 0xFF ? "-" : scfq_screen_ref_name(index, recs[i].best),
+                   recs[i].best_hits, (unsigned)recs[i].mask);
+    if (std::fclose(f) != 0) quit_error("Unable to write file: " + per_read, 1);
+  }
+  if (cols.header) std::printf("%s\n", output_header(kScreenHeader, cols.basename, cols.absolute).c_str());
+  for (uint32_t r = 0; r <= names.size(); ++r) {
+    char row[1024];
+    scfq_format_screen_row_tsv(&st, index, r, row, sizeof row);
+    cols.emit_row(row, files[0]);
+  }
+  scfq_screen_index_free(index);
+  return 0;
+}
+
 // command "fq-kmers" (addition, not in the reference): -t/--header, -b/--basename, -a/--absolute as fq-count, --k=N, --canonical, --top=N,
 // --totals, [fastq ...]
 static const char* kKmersHeader = "kmer\tcount";
@@ -1086,7 +1214,7 @@ int main(int argc, char** argv) {
       {"fq-count", cmd_fq_count},       {"fq-dedup", cmd_fq_dedup},       {"fq-meta", cmd_fq_meta},
       {"fq-readstats", cmd_fq_readstats}, {"fq-cycles", cmd_fq_cycles},   {"fq-kmers", cmd_fq_kmers},
       {"fq-adapters", cmd_fq_adapters}, {"fq-insert-size", cmd_fq_insert_size}, {"fq-merge", cmd_fq_merge},
-      {"fq-trim", cmd_fq_trim},         {"fa-gc", cmd_fa_gc}};
+      {"fq-trim", cmd_fq_trim},         {"fq-screen", cmd_fq_screen},     {"fa-gc", cmd_fa_gc}};
   for (const auto& c : commands)
     if (params[0] == c.name) return c.run(params);
   help_top(stdout);

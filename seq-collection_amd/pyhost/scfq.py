@@ -55,6 +55,9 @@ EXPORTS = [
     "scfq_debug_insert_size_stages",
     "scfq_merge_buffers", "scfq_merge_files", "scfq_format_merge_stats_tsv", "scfq_merge_error_detail", "scfq_debug_merge_stages",
     "scfq_trim_buffers", "scfq_trim_files", "scfq_format_trim_stats_tsv", "scfq_trim_error_detail", "scfq_debug_trim_stages",
+    "scfq_screen_index_buffers", "scfq_screen_index_files", "scfq_screen_index_free", "scfq_screen_index_summary", "scfq_screen_ref_name",
+    "scfq_screen_buffers", "scfq_screen_files", "scfq_format_screen_row_tsv", "scfq_screen_error_detail", "scfq_debug_screen_stages",
+    "scfq_debug_screen_build_ms",
     "scfq_fa_index_buffer", "scfq_fa_index_file", "scfq_fa_contig_at", "scfq_fa_contig_find", "scfq_fa_count_intervals",
     "scfq_fa_index_free", "scfq_fa_error_detail", "scfq_fa_parse_window", "scfq_fa_gc_interval", "scfq_format_fa_gc_value",
     "scfq_debug_fa_stages",
@@ -225,6 +228,46 @@ class TrimStats(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64 * 8 if n == "adapter_reads" else ctypes.c_uint64) for n in TRIM_STATS_FIELDS]
 
 
+SCFQ_SCREEN_INTERLEAVED, SCFQ_SCREEN_KEEP_MATCHED = 0x1, 0x2
+SCFQ_SCREEN_MAX_REFS, SCFQ_SCREEN_MAX_K, SCFQ_SCREEN_MAX_REF_BASES = 16, 32, 1 << 27
+SCREEN_REF_FIELDS = ("contigs", "bases", "windows", "kmers", "distinct", "shared")
+SCREEN_PER_REF_FIELDS = ("ref_reads", "ref_only_reads", "ref_best_reads", "ref_kmer_hits")
+SCREEN_STATS_FIELDS = ("struct_size", "abi_version", "reads1", "reads2", "lines1", "lines2", "input_bytes1", "input_bytes2", "pairs", "unpaired",
+                       "reads_in", "reads_out", "dropped_reads", "matched_reads", "matched_pairs", "multi_reads", "short_reads", "bases_in",
+                       "bases_out", "windows", "kmers", "skipped", "hit_kmers") + SCREEN_PER_REF_FIELDS + \
+                      ("out1_bytes", "out2_bytes", "flags", "min_hits", "min_hit_pct", "k", "n_refs")
+
+
+class ScreenRef(ctypes.Structure):
+    """scfq_screen_ref"""
+    _fields_ = [("name", ctypes.c_char_p), ("text", ctypes.c_void_p), ("n", ctypes.c_uint64)]
+
+
+class ScreenRefSummary(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in SCREEN_REF_FIELDS]
+
+
+class ScreenSummary(ctypes.Structure):
+    """scfq_screen_summary (6 + 16 x 6 uint64)"""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("struct_size", "abi_version", "n_refs", "k", "distinct", "slots")] + [("ref", ScreenRefSummary * 16)]
+
+
+class ScreenOpts(ctypes.Structure):
+    """scfq_screen_opts (24 bytes)"""
+    _fields_ = [("struct_size", ctypes.c_uint64)] + [(n, ctypes.c_uint32) for n in ("flags", "min_hits", "min_hit_pct", "reserved")]
+
+
+class ScreenRec(ctypes.Structure):
+    """scfq_screen_rec (16 bytes)"""
+    _fields_ = [("kmers", ctypes.c_uint32), ("hit_kmers", ctypes.c_uint32), ("best_hits", ctypes.c_uint32), ("mask", ctypes.c_uint16),
+                ("best", ctypes.c_uint8), ("reserved", ctypes.c_uint8)]
+
+
+class ScreenStats(ctypes.Structure):
+    """scfq_screen_stats (94 uint64)"""
+    _fields_ = [(n, ctypes.c_uint64 * 16 if n in SCREEN_PER_REF_FIELDS else ctypes.c_uint64) for n in SCREEN_STATS_FIELDS]
+
+
 FA_SUMMARY_FIELDS = ("struct_size", "abi_version", "input_bytes", "tiles", "contigs", "bases", "gc_bases", "acgt_bases", "orphan_bases")
 
 
@@ -386,6 +429,24 @@ def lib():
         L.scfq_format_trim_stats_tsv.argtypes = [ctypes.POINTER(TrimStats), ctypes.c_char_p, ctypes.c_uint64]
         L.scfq_trim_error_detail.restype = ctypes.c_char_p
         L.scfq_debug_trim_stages.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]
+        L.scfq_screen_index_buffers.argtypes = [ctypes.POINTER(ScreenRef), ctypes.c_uint32, ctypes.c_uint32, pvp, ctypes.POINTER(ScreenSummary)]
+        L.scfq_screen_index_files.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_char_p), ctypes.c_uint32, ctypes.c_uint32,
+                                              ctypes.c_void_p, pvp, ctypes.POINTER(ScreenSummary)]
+        L.scfq_screen_index_free.argtypes = [vp]
+        L.scfq_screen_index_free.restype = None
+        L.scfq_screen_index_summary.argtypes = [vp, ctypes.POINTER(ScreenSummary)]
+        L.scfq_screen_ref_name.argtypes = [vp, ctypes.c_uint32]
+        L.scfq_screen_ref_name.restype = ctypes.c_char_p
+        L.scfq_screen_buffers.argtypes = [vp, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ScreenOpts),
+                                          ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                          ctypes.c_int, ctypes.POINTER(ScreenStats)]
+        L.scfq_screen_files.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_void_p, ctypes.POINTER(ScreenOpts), ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ScreenStats)]
+        L.scfq_format_screen_row_tsv.argtypes = [ctypes.POINTER(ScreenStats), vp, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_uint64]
+        L.scfq_screen_error_detail.restype = ctypes.c_char_p
+        L.scfq_debug_screen_stages.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]
+        L.scfq_debug_screen_build_ms.argtypes = [vp]
+        L.scfq_debug_screen_build_ms.restype = ctypes.c_double
         L.scfq_fa_index_buffer.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, pvp, ctypes.POINTER(FaSummary)]
         L.scfq_fa_index_file.argtypes = [ctypes.c_char_p, ctypes.c_void_p, pvp, ctypes.POINTER(FaSummary)]
         L.scfq_fa_contig_at.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(FaContig)]
@@ -1080,6 +1141,144 @@ def trim_stages():
     zeros unless SCFQ_TRIM_TIMING=1 is in the environment"""
     ms = (ctypes.c_double * 4)()
     lib().scfq_debug_trim_stages(ms, 4)
+    return list(ms)
+
+
+def _screen_error(rc, what):
+    return ScfqError(rc, what, lib().scfq_screen_error_detail().decode() or lib().scfq_last_error_detail().decode())
+
+
+class ScreenIndex:
+    """scfq_screen_index: the k-mer table of up to 16 references on the device.  `summary` is the ScreenSummary of the build, `names` the
+    references' names.  close() (or the end of a `with`) frees it."""
+
+    def __init__(self, handle, summary):
+        self._h, self.summary = handle, summary
+        self.names = [lib().scfq_screen_ref_name(handle, r).decode("latin-1") for r in range(summary.n_refs)]
+        self.k = int(summary.k)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def build_ms(self):
+        return lib().scfq_debug_screen_build_ms(self._h)
+
+    def close(self):
+        if self._h:
+            lib().scfq_screen_index_free(self._h)
+        self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _new_screen_summary():
+    s = ScreenSummary()
+    s.struct_size = ctypes.sizeof(ScreenSummary)
+    return s
+
+
+def screen_index_host(refs, k=31):
+    """refs: a list of (name, FASTA text as bytes / numpy uint8)"""
+    arr = (ScreenRef * max(len(refs), 1))()
+    keep = []
+    for i, (name, text) in enumerate(refs[:len(arr)]):
+        addr, n, held = _host_ptr(text)
+        raw = name.encode("latin-1") if isinstance(name, str) else name
+        keep.append((held, raw))
+        arr[i] = ScreenRef(raw, addr.value if hasattr(addr, "value") else addr, n)
+    h, s = ctypes.c_void_p(), _new_screen_summary()
+    rc = lib().scfq_screen_index_buffers(arr, len(refs), k, ctypes.byref(h), ctypes.byref(s))
+    if rc != 0:
+        raise _screen_error(rc, "scfq_screen_index_buffers")
+    return ScreenIndex(h, s)
+
+
+def screen_index_files(paths, names=None, k=31):
+    """names: None, or a list with a name or None (the file's base name up to its first '.') per path"""
+    n = len(paths)
+    pa = (ctypes.c_char_p * max(n, 1))(*[os.fsencode(p) for p in paths])
+    na = None
+    if names is not None:
+        na = (ctypes.c_char_p * max(n, 1))(*[None if x is None else (x.encode("latin-1") if isinstance(x, str) else x) for x in names])
+    h, s = ctypes.c_void_p(), _new_screen_summary()
+    rc = lib().scfq_screen_index_files(na, pa, n, k, None, ctypes.byref(h), ctypes.byref(s))
+    if rc != 0:
+        raise _screen_error(rc, "scfq_screen_index_files")
+    return ScreenIndex(h, s)
+
+
+def screen_opts(interleaved=False, keep_matched=False, min_hits=1, min_hit_pct=0, flags=None, reserved=0):
+    o = ScreenOpts()
+    o.struct_size = ctypes.sizeof(ScreenOpts)
+    o.flags = flags if flags is not None else (SCFQ_SCREEN_INTERLEAVED if interleaved else 0) | (SCFQ_SCREEN_KEEP_MATCHED if keep_matched else 0)
+    o.min_hits, o.min_hit_pct, o.reserved = min_hits, min_hit_pct, reserved
+    return o
+
+
+def _screen_call(fn, what, index, opts, head, tail):
+    """Returns the ScreenStats; an ScfqError carries them as `stats` (complete when an output was too small)."""
+    s = ScreenStats()
+    s.struct_size = ctypes.sizeof(ScreenStats)
+    handle = index.handle if isinstance(index, ScreenIndex) else index
+    rc = fn(handle, *head, ctypes.byref(opts) if opts is not None else None, *tail, ctypes.byref(s))
+    if rc != 0:
+        e = _screen_error(rc, what)
+        e.stats = s
+        raise e
+    return s
+
+
+def screen_device(index, ptr1, n1, ptr2=None, n2=0, opts=None, out1=None, out2=None, recs=None):
+    """fq-screen of device-resident FASTQs (the pointer rules of trim_device).  out1 / out2: (device address, capacity) or None; recs:
+    (device address, entries) of the per-read table or None."""
+    return _screen_call(lib().scfq_screen_buffers, "scfq_screen_buffers", index, opts,
+                        [ctypes.c_void_p(ptr1), n1, ctypes.c_void_p(ptr2) if ptr2 is not None else None, n2, 1],
+                        [ctypes.c_void_p(recs[0]) if recs else None, recs[1] if recs else 0] + _trim_outputs((out1, out2)) + [1])
+
+
+def screen_host(index, data1, data2=None, opts=None, caps=None):
+    """fq-screen of host buffers; caps as trim_host's.  Returns (ScreenStats, out1, out2), the outputs as bytes or None."""
+    a1, n1, keep1 = _host_ptr(data1)
+    a2, n2, keep2 = _host_ptr(data2) if data2 is not None else (None, 0, None)
+    head = [a1, n1, a2, n2, 0]
+    fn = lib().scfq_screen_buffers
+    if caps is None:
+        s = _screen_call(fn, "scfq_screen_buffers", index, opts, head, [None, 0, None, 0, None, 0, 0])
+        caps = (s.out1_bytes, s.out2_bytes if data2 is not None else None)
+    bufs = [None if c is None else ctypes.create_string_buffer(max(int(c), 1)) for c in caps]
+    outs = [None if b is None else (ctypes.addressof(b), int(c)) for b, c in zip(bufs, caps)]
+    s = _screen_call(fn, "scfq_screen_buffers", index, opts, head, [None, 0] + _trim_outputs(outs) + [0])
+    sizes = (s.out1_bytes, s.out2_bytes)
+    return (s,) + tuple(None if b is None else b.raw[:int(k)] for b, k in zip(bufs, sizes))
+
+
+def screen_file(index, path1, path2=None, opts=None, out1_fd=-1, out2_fd=-1, recs=None):
+    """recs: None, or a ctypes array of ScreenRec that receives the per-read table"""
+    return _screen_call(lib().scfq_screen_files, "scfq_screen_files", index, opts,
+                        [os.fsencode(path1), os.fsencode(path2) if path2 is not None else None, None],
+                        [out1_fd, out2_fd, ctypes.cast(recs, ctypes.c_void_p) if recs is not None else None, len(recs) if recs is not None else 0])
+
+
+def format_screen_row_tsv(s, index, r):
+    buf = ctypes.create_string_buffer(1024)
+    n = lib().scfq_format_screen_row_tsv(ctypes.byref(s), index.handle, r, buf, 1024)
+    if n < 0:
+        raise ScfqError(n, "scfq_format_screen_row_tsv")
+    return buf.value.decode("latin-1")
+
+
+def screen_stages():
+    """(line indexes of paired input, lookup kernel, lengths and scans, write kernel) milliseconds of this thread's last screen call; the
+    last three are HIP-event times and zeros unless SCFQ_SCREEN_TIMING=1 is in the environment"""
+    ms = (ctypes.c_double * 4)()
+    lib().scfq_debug_screen_stages(ms, 4)
     return list(ms)
 
 
