@@ -52,8 +52,20 @@ int scfq_debug_gz_shard_fix(scfq_partial* p, uint64_t* hist, int true_prev, int 
 int64_t scfq_debug_stages(char* buf, uint64_t cap);
 void scfq_debug_stage_mark(const char* what);
 /* The scan kernel instance and range geometry of the calling thread's last scan launch, e.g.
- * "fq_scan_tiles<false, 0, 2, true, false> tiles_per_range=100" (same contract as scfq_debug_stages: returns the length, writes when it fits). */
+ * "fq_scan_tiles<false, 0, 2, true, false> tiles_per_range=100/50/25/12": the range size of every segment of the launch, one number
+ * for a uniform launch (same contract as scfq_debug_stages: returns the length, writes when it fits). */
 int64_t scfq_debug_last_scan_kernel(char* buf, uint64_t cap);
+/* Host only, no device needed: the ranges a scan launch over `n` bytes would use when its first byte lies `ptr_offset` (0..4095) bytes
+ * past a 4 KiB boundary, on a device of n_cu compute units (0: 256), under the SCFQ_* flags of the scan and the SCFQ_TILES_PER_RANGE /
+ * SCFQ_TAPER_WAVES of the environment.  Range r of segment s covers the 4 KiB tiles first_tile[s] + (r - first_range[s]) *
+ * tiles_per_range[s] up to + tiles_per_range[s], clipped to the next segment's first tile (n_tiles for the last).  Set struct_size. */
+typedef struct scfq_scan_geometry {
+  uint32_t struct_size;
+  uint32_t n_segments;          /* 1..6; 1 = uniform ranges */
+  uint64_t n_tiles, n_ranges;
+  uint64_t first_range[6], first_tile[6], tiles_per_range[6];
+} scfq_scan_geometry;
+int scfq_debug_scan_geometry(uint64_t n, uint32_t ptr_offset, uint32_t flags, int n_cu, scfq_scan_geometry* out);
 /* Stage times of the calling thread's last scfq_read_stats_buffer / scfq_read_stats_file, in milliseconds:
  * ms[0] line index (host clock around the synchronous index call), ms[1] R1 with its border pass, ms[2] R2 first pass
  * (sums and histograms), ms[3] R2 N50 / N90 (sort, scan, search; 0 when every read has the same length) — [1..3] are HIP-event

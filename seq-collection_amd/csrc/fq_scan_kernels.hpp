@@ -27,9 +27,15 @@
 #include <stdint.h>
 
 #include "scfq_hdrhash.hpp"
+#include "fq_scan_geometry.hpp"
 
 #ifndef SCFQ_ABLATE
 #define SCFQ_ABLATE 0   // diagnostic timing-only builds (make ablate): 1 = no classifier, 2 = no segment accounting, 3 = neither
+#endif
+#ifndef SCFQ_STAMPS
+#define SCFQ_STAMPS 0   // diagnostic build (make stamps): lane 0 of every wave of fq_scan_tiles / fq_stream_null writes wall_clock64() at its start
+                        // and before its partial's stores into a buffer of its own, [n_ranges][2] u64, that no kernel reads
+                        // (scripts/measure_scan_drain.py: residency against time).  No stamp exists in the normal build.
 #endif
 
 namespace scfq {
@@ -906,8 +912,8 @@ struct ScanArgs {
   const uint8_t* base;     // first byte of the range to scan (any alignment)
   uint64_t n;              // bytes
   int32_t prev_byte;       // byte before base[0]: 0..255, -1 = start of input, -2 = read base[-1]
-  uint32_t tiles_per_range;
-  uint64_t n_ranges;
+  ScanGeometry geo;        // which tiles are whose (fq_scan_geometry.hpp); the histogram forms and their guess pass get one segment
+  uint64_t n_ranges;       // == geo.n_ranges()
   uint64_t* partials;      // [n_ranges][kPartialWords]
   uint32_t* hist_partials; // [n_ranges][4][256] u32, HIST == 1 only
   const uint8_t* todo;     // HIST == 1, optional: scan only the ranges with todo[range] != 0 (redo pass of the fast form)
@@ -915,6 +921,9 @@ struct ScanArgs {
   uint32_t* hist_wg;       // HIST == 2: [n_workgroups][256] u32, quality-class histogram of the workgroup's ranges
   uint8_t* guess_out;      // GUESS: per range result
   uint32_t guess_cap_tiles;// GUESS: tiles a range may look at before giving up
+#if SCFQ_STAMPS
+  uint64_t* stamps;        // [n_ranges][2]: wall_clock64() at wave start / before the partial's stores
+#endif
 };
 
 // RING = LDS ring slots per wave (1 being consumed + RING-1 in flight); NT = non-temporal DMA loads
@@ -949,6 +958,9 @@ __global__ __launch_bounds__(HIST == 1 ? 64 * kHistWaves : HIST == 2 ? 64 * kQWa
     __syncthreads();
   }
   if (active) {
+#if SCFQ_STAMPS
+  if (!GUESS && lane == 0) a.stamps[range * 2] = wall_clock64();
+#endif
 
   // everything that steers the tile loop is wave-uniform: pin it in SGPRs so the per-tile bookkeeping runs on the
   // scalar unit instead of 64-bit VALU compares
@@ -957,9 +969,10 @@ __global__ __launch_bounds__(HIST == 1 ? 64 * kHistWaves : HIST == 2 ? 64 * kQWa
   const uint64_t B = (uint64_t)(uintptr_t)a.base, E = B + a.n;
   const uint64_t A0 = B & ~(uint64_t)(kTile - 1);
   const uint32_t n_tiles = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((E - A0 + kTile - 1) / kTile));
-  const uint32_t t_begin = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(range * a.tiles_per_range));
-  uint32_t t_end = t_begin + (GUESS ? a.guess_cap_tiles : a.tiles_per_range);   // a guess may look past its own range
-  if (t_end > n_tiles) t_end = n_tiles;
+  uint32_t t_begin, t_end;
+  scan_range_tiles(a.geo, (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)range), t_begin, t_end);
+  t_begin = (uint32_t)__builtin_amdgcn_readfirstlane((int)t_begin);
+  if (GUESS) t_end = (n_tiles - t_begin > a.guess_cap_tiles) ? t_begin + a.guess_cap_tiles : n_tiles;   // a guess may look past its own range
   t_end = (uint32_t)__builtin_amdgcn_readfirstlane((int)t_end);
   // tiles [full_lo, full_hi) lie entirely inside [B, E); at most the first and the last tile of an input do not
   const uint32_t full_lo = (uint32_t)__builtin_amdgcn_readfirstlane((A0 < B) ? 1 : 0);
@@ -1071,6 +1084,9 @@ __global__ __launch_bounds__(HIST == 1 ? 64 * kHistWaves : HIST == 2 ? 64 * kQWa
   }
 
   flush_pending(st);
+#if SCFQ_STAMPS
+  if (lane == 0) a.stamps[range * 2 + 1] = wall_clock64();
+#endif
   // ---- range partial: reduce the per-lane 16-bit fields across the wave, lane 0 stores --------
   uint64_t* out = a.partials + range * kPartialWords;
   auto sum4 = [&](const Acc16& acc) {
@@ -1386,19 +1402,25 @@ __global__ __launch_bounds__(256) void fq_fold_hist_wg(const uint32_t* hist_wg, 
 // non-temporal LDS-DMA ring, one ds_read per lane and tile, no classification or accounting.  Its time is the
 // practical ceiling the scan kernel is compared with on the same device (bench.py "stream_ceiling").
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void fq_stream_null(const uint8_t* base, uint32_t n_tiles, uint32_t tiles_per_range,
-                                                      uint32_t* sink) {
+__global__ __launch_bounds__(256) void fq_stream_null(const uint8_t* base, ScanGeometry geo, uint32_t* sink
+#if SCFQ_STAMPS
+                                                      , uint64_t* stamps
+#endif
+                                                      ) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int lane = threadIdx.x & 63;
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   uint8_t* ring = smem + wave * (2 * kTile);
   const uint32_t ring_lds = (uint32_t)(uintptr_t)ring;
   const uint32_t range = blockIdx.x * kWavesPerBlock + wave;
-  const uint32_t t0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(range * tiles_per_range));
-  uint32_t t1 = t0 + tiles_per_range;
-  if (t1 > n_tiles) t1 = n_tiles;
+  if (range >= geo.n_ranges()) return;
+#if SCFQ_STAMPS
+  if (lane == 0) stamps[(uint64_t)range * 2] = wall_clock64();
+#endif
+  uint32_t t0, t1;
+  scan_range_tiles(geo, (uint32_t)__builtin_amdgcn_readfirstlane((int)range), t0, t1);
+  t0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)t0);
   t1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)t1);
-  if (t0 >= n_tiles) return;
   uint32_t acc = 0, slot = 0;
   glds_tile<true>(base + (uint64_t)t0 * kTile + lane * 16, ring_lds);
   for (uint32_t t = t0; t < t1; ++t) {
@@ -1412,6 +1434,9 @@ __global__ __launch_bounds__(256) void fq_stream_null(const uint8_t* base, uint3
     acc += *reinterpret_cast<const uint32_t*>(ring + slot * kTile + lane * 64);
     slot ^= 1u;
   }
+#if SCFQ_STAMPS
+  if (lane == 0) stamps[(uint64_t)range * 2 + 1] = wall_clock64();
+#endif
   if (acc == 0x9E3779B9u) sink[0] = acc;   // keeps the reads alive
 }
 

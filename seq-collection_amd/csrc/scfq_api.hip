@@ -410,29 +410,69 @@ int ensure_staging(Ctx* c, uint64_t chunk, bool pinned) {
   return SCFQ_OK;
 }
 
-uint32_t pick_tiles_per_range(const Ctx* c, uint64_t n_tiles) {
+uint32_t pick_tiles_per_range(int n_cu, uint64_t n_tiles) {
   if (const char* e = std::getenv("SCFQ_TILES_PER_RANGE")) {
     long v = std::atol(e);
     if (v >= 1) return (uint32_t)std::min<long>(v, scfq::kMaxTilesPerRange);
   }
   // enough ranges that every CU sees many waves come and go (dynamic balance from block dispatch),
   // few enough that the ordered fold stays negligible
-  const uint64_t target_ranges = (uint64_t)c->n_cu * 12 * 8;
+  const uint64_t target_ranges = (uint64_t)n_cu * 12 * 8;
   uint64_t tpr = (n_tiles + target_ranges - 1) / target_ranges;
   tpr = std::max<uint64_t>(tpr, 16);
   tpr = std::min<uint64_t>(tpr, scfq::kMaxTilesPerRange);
   return (uint32_t)tpr;
+}
+uint32_t pick_tiles_per_range(const Ctx* c, uint64_t n_tiles) { return pick_tiles_per_range(c->n_cu, n_tiles); }
+
+// The ranges of a K1 launch over n_tiles tiles (fq_scan_geometry.hpp).  The non-histogram scans and the stream probe taper the range
+// size towards the end of the launch; the histogram forms, and the guess pass that shares their ranges, stay uniform.  The taper is
+// sized by the waves the device holds at once: 16 per CU — the stamps build shows a plateau of exactly 4 096 resident waves on 256 CUs,
+// four workgroups of 32 KiB of LDS per CU, not the five that 160 KiB would hold (profiles/scan_taper/drain.json).
+// SCFQ_TAPER_WAVES=N overrides that number, 0 switches the taper off; SCFQ_TILES_PER_RANGE is the base size either way.
+scfq::ScanGeometry scan_geometry(int n_cu, uint64_t n_tiles, bool hist) {
+  uint32_t waves = (uint32_t)n_cu * 16u;
+  if (const char* e = std::getenv("SCFQ_TAPER_WAVES")) {
+    long v = std::atol(e);
+    if (v >= 0) waves = (uint32_t)std::min<long>(v, 1l << 24);
+  }
+  return scfq::make_scan_geometry(n_tiles, pick_tiles_per_range(n_cu, n_tiles), hist ? 0u : waves);
+}
+
+// "100/50/25/12": the range size of every segment
+std::string geometry_sizes(const scfq::ScanGeometry& g) {
+  std::string s;
+  for (uint32_t k = 0; k < g.n_segments; ++k) s += (k ? "/" : "") + std::to_string(g.tpr[k]);
+  return s;
 }
 
 // the scan kernel instance and range geometry of this thread's last launch (scfq_debug_last_scan_kernel: bench.py attaches committed PMC
 // traffic only to a run of the very kernel that was profiled)
 thread_local char g_last_scan[128] = "";
 
+#if SCFQ_STAMPS
+// diagnostic build only: the stamps of the process's last K1 / stream-probe launch (scfq_debug_scan_stamps)
+uint64_t* g_stamps = nullptr;
+uint64_t g_stamps_cap = 0, g_stamps_n = 0;
+int ensure_stamps(uint64_t n_ranges) {
+  if (n_ranges > g_stamps_cap) {
+    HIPCHK(hipDeviceSynchronize());
+    if (g_stamps) HIPCHK(hipFree(g_stamps));
+    g_stamps = nullptr;
+    g_stamps_cap = 0;
+    HIPCHK(hipMalloc(&g_stamps, n_ranges * 2 * sizeof(uint64_t)));
+    g_stamps_cap = n_ranges;
+  }
+  g_stamps_n = n_ranges;
+  return SCFQ_OK;
+}
+#endif
+
 template <bool S, int H, int RING, bool NT, bool GUESS = false>
 void launch_scan(const scfq::ScanArgs& a, unsigned blocks, hipStream_t st) {
   if (!GUESS)
-    std::snprintf(g_last_scan, sizeof g_last_scan, "fq_scan_tiles<%s, %d, %d, %s, %s> tiles_per_range=%u", S ? "true" : "false", H, RING, NT ? "true" : "false",
-                  GUESS ? "true" : "false", a.tiles_per_range);
+    std::snprintf(g_last_scan, sizeof g_last_scan, "fq_scan_tiles<%s, %d, %d, %s, %s> tiles_per_range=%s", S ? "true" : "false", H, RING, NT ? "true" : "false",
+                  GUESS ? "true" : "false", geometry_sizes(a.geo).c_str());
   constexpr int waves = (H == 1) ? scfq::kHistWaves : (H == 2) ? scfq::kQWaves : scfq::kWavesPerBlock;
   unsigned lds = waves * RING * scfq::kTile;
   if (H == 1) lds += waves * scfq::kHistWords * sizeof(uint32_t);
@@ -455,15 +495,19 @@ int scan_async(Ctx* c, const uint8_t* dptr, uint64_t n, int prev_byte, uint32_t 
   const uint64_t B = (uint64_t)(uintptr_t)dptr, A0 = B & ~(uint64_t)(scfq::kTile - 1);
   const uint64_t NT = (B + n - A0 + scfq::kTile - 1) / scfq::kTile;
   if (NT >= (1ull << 32)) { std::snprintf(g_err, sizeof g_err, "a single scan launch covers at most 16 TiB"); return SCFQ_EARG; }
-  const uint32_t tpr = pick_tiles_per_range(c, NT);
-  const uint64_t n_ranges = (NT + tpr - 1) / tpr;
+  scfq::ScanArgs a;
+  a.geo = scan_geometry(c->n_cu, NT, hist);
+  const uint64_t n_ranges = a.geo.n_ranges();
   int rc = ensure_partials(c, n_ranges, hist);
   if (rc) return rc;
-  scfq::ScanArgs a;
+#if SCFQ_STAMPS
+  rc = ensure_stamps(n_ranges);
+  if (rc) return rc;
+  a.stamps = g_stamps;
+#endif
   a.base = dptr;
   a.n = n;
   a.prev_byte = prev_byte;
-  a.tiles_per_range = tpr;
   a.n_ranges = n_ranges;
   a.partials = c->d_partials;
   a.hist_partials = c->d_hist_partials;
@@ -1289,6 +1333,41 @@ int64_t scfq_debug_last_scan_kernel(char* buf, uint64_t cap) {
   if (buf && cap > n) std::memcpy(buf, g_last_scan, n + 1);
   return (int64_t)n;
 }
+int scfq_debug_scan_geometry(uint64_t n, uint32_t ptr_offset, uint32_t flags, int n_cu, scfq_scan_geometry* out) {
+  if (!out || out->struct_size != sizeof(scfq_scan_geometry) || ptr_offset >= (uint32_t)scfq::kTile || n == 0) return SCFQ_EARG;
+  const uint64_t n_tiles = ((uint64_t)ptr_offset + n + scfq::kTile - 1) / scfq::kTile;
+  if (n_tiles >= (1ull << 32)) return SCFQ_EARG;
+  const scfq::ScanGeometry g = scan_geometry(n_cu > 0 ? n_cu : 256, n_tiles, (flags & SCFQ_QUAL_HIST) != 0);
+  *out = scfq_scan_geometry{};
+  out->struct_size = sizeof(scfq_scan_geometry);
+  out->n_segments = g.n_segments;
+  out->n_tiles = g.n_tiles();
+  out->n_ranges = g.n_ranges();
+  for (uint32_t s = 0; s < g.n_segments; ++s) {
+    out->first_range[s] = g.first_range[s];
+    out->first_tile[s] = g.first_tile[s];
+    out->tiles_per_range[s] = g.tpr[s];
+  }
+  return SCFQ_OK;
+}
+#if SCFQ_STAMPS
+// diagnostic build only (make stamps): the [n_ranges][2] wall_clock64() stamps of the process's last K1 / stream-probe launch.  Returns
+// the number of ranges (nothing written when cap_ranges is smaller), negative on error.
+int64_t scfq_debug_scan_stamps(uint64_t* out, uint64_t cap_ranges) {
+  if (!g_stamps || !g_stamps_n) return 0;
+  if (out && cap_ranges >= g_stamps_n) {
+    if (hipDeviceSynchronize() != hipSuccess) return SCFQ_EHIP;
+    if (hipMemcpy(out, g_stamps, g_stamps_n * 2 * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return SCFQ_EHIP;
+  }
+  return (int64_t)g_stamps_n;
+}
+// ticks of wall_clock64() per millisecond on the current device; negative on error
+int64_t scfq_debug_wall_clock_khz(void) {
+  int dev = 0, khz = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess) return SCFQ_EHIP;
+  return khz;
+}
+#endif
 
 uint64_t scfq_device_bytes_high_water(void) { return g_dev_high.load(); }
 uint64_t scfq_device_bytes_now(void) { return g_dev_bytes.load(); }
@@ -1917,16 +1996,24 @@ double scfq_debug_stream_ms(const void* dptr, uint64_t n, int reps) {
   if (s.take() || !dptr || ((uintptr_t)dptr & 4095) || n < (uint64_t)scfq::kTile) return -1.0;
   Ctx* c = s.c;
   const uint32_t n_tiles = (uint32_t)std::min<uint64_t>(n / scfq::kTile, 0xFFFFFFFFull);
-  const uint32_t tpr = pick_tiles_per_range(c, n_tiles);
-  const unsigned ranges = (n_tiles + tpr - 1) / tpr, blocks = (ranges + scfq::kWavesPerBlock - 1) / scfq::kWavesPerBlock;
+  const scfq::ScanGeometry geo = scan_geometry(c->n_cu, n_tiles, false);      // the ranges a flags == 0 scan of these tiles gets
+  const unsigned ranges = geo.n_ranges(), blocks = (ranges + scfq::kWavesPerBlock - 1) / scfq::kWavesPerBlock;
   if (ensure_partials(c, 16, false)) return -1.0;
+#if SCFQ_STAMPS
+  if (ensure_stamps(ranges)) return -1.0;
+#endif
   hipEvent_t e0, e1;
   if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return -1.0;
   float best = -1.0f;
   for (int r = 0; r < std::max(1, reps) + 1; ++r) {
     (void)hipEventRecord(e0, c->compute);
+#if SCFQ_STAMPS
     hipLaunchKernelGGL(scfq::fq_stream_null, dim3(blocks), dim3(256), scfq::kWavesPerBlock * 2 * scfq::kTile, c->compute,
-                       static_cast<const uint8_t*>(dptr), n_tiles, tpr, reinterpret_cast<uint32_t*>(c->d_partials));
+                       static_cast<const uint8_t*>(dptr), geo, reinterpret_cast<uint32_t*>(c->d_partials), g_stamps);
+#else
+    hipLaunchKernelGGL(scfq::fq_stream_null, dim3(blocks), dim3(256), scfq::kWavesPerBlock * 2 * scfq::kTile, c->compute,
+                       static_cast<const uint8_t*>(dptr), geo, reinterpret_cast<uint32_t*>(c->d_partials));
+#endif
     (void)hipEventRecord(e1, c->compute);
     if (hipEventSynchronize(e1) != hipSuccess) { best = -1.0f; break; }
     float ms = 0;

@@ -44,7 +44,7 @@ EXPORTS = [
     "scfq_comm_unique_id", "scfq_comm_init_rank", "scfq_comm_init_rendezvous", "scfq_comm_init_all", "scfq_comm_world",
     "scfq_comm_rank", "scfq_comm_is_broken", "scfq_prepare", "scfq_comm_transport", "scfq_comm_exchange", "scfq_comm_exchange_start", "scfq_comm_exchange_finish",
     "scfq_comm_allgather_u64", "scfq_comm_destroy", "scfq_comm_error_detail", "scfq_debug_stages", "scfq_debug_stage_mark",
-    "scfq_debug_gz_member_boundary", "scfq_debug_gz_shard_fix", "scfq_debug_last_scan_kernel",
+    "scfq_debug_gz_member_boundary", "scfq_debug_gz_shard_fix", "scfq_debug_last_scan_kernel", "scfq_debug_scan_geometry",
     "scfq_read_stats_buffer", "scfq_read_stats_file", "scfq_format_read_stats_tsv", "scfq_read_stats_error_detail",
     "scfq_debug_read_stats_stages",
     "scfq_cycles_buffer", "scfq_cycles_file", "scfq_format_cycle_row_tsv", "scfq_cycles_error_detail", "scfq_debug_cycles_stages",
@@ -1447,13 +1447,35 @@ def debug_stream_ms(dev_ptr, n, reps=5):
 
 def debug_last_scan_kernel():
     """diagnostic: the scan kernel instance + range geometry of this thread's last launch, e.g.
-    'fq_scan_tiles<false, 0, 2, true, false> tiles_per_range=100'"""
+    'fq_scan_tiles<false, 0, 2, true, false> tiles_per_range=100/50/25/12': the range size of every segment of the launch
+    (big ranges first, small ranges last), a single number for a uniform launch (histogram forms, small inputs, SCFQ_TAPER_WAVES=0)"""
     L = lib()
     L.scfq_debug_last_scan_kernel.restype = ctypes.c_int64
     L.scfq_debug_last_scan_kernel.argtypes = [ctypes.c_char_p, ctypes.c_uint64]
     buf = ctypes.create_string_buffer(256)
     L.scfq_debug_last_scan_kernel(buf, 256)
     return buf.value.decode()
+
+
+class ScanGeometry(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("n_segments", ctypes.c_uint32), ("n_tiles", ctypes.c_uint64), ("n_ranges", ctypes.c_uint64),
+                ("first_range", ctypes.c_uint64 * 6), ("first_tile", ctypes.c_uint64 * 6), ("tiles_per_range", ctypes.c_uint64 * 6)]
+
+    def segments(self):
+        """[(first_range, first_tile, tiles_per_range)] of the segments in force"""
+        return [(int(self.first_range[s]), int(self.first_tile[s]), int(self.tiles_per_range[s])) for s in range(self.n_segments)]
+
+
+def debug_scan_geometry(n, ptr_offset=0, flags=0, n_cu=0):
+    """diagnostic, no device needed: the ranges a scan launch over n bytes starting ptr_offset bytes past a 4 KiB boundary would use
+    (SCFQ_TILES_PER_RANGE and SCFQ_TAPER_WAVES of the environment apply)"""
+    L = lib()
+    L.scfq_debug_scan_geometry.restype = ctypes.c_int
+    L.scfq_debug_scan_geometry.argtypes = [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ScanGeometry)]
+    g = ScanGeometry()
+    g.struct_size = ctypes.sizeof(ScanGeometry)
+    _check(L.scfq_debug_scan_geometry(n, ptr_offset, flags, n_cu, ctypes.byref(g)), "scfq_debug_scan_geometry")
+    return g
 
 
 def combine(acc, b, hist_acc=None, hist_b=None):
