@@ -874,6 +874,135 @@ int scfq_screen_files(const scfq_screen_index* index, const char* path1, const c
 int scfq_format_screen_row_tsv(const scfq_screen_stats* s, const scfq_screen_index* index, uint32_t r, char* buf, uint64_t cap);
 const char* scfq_screen_error_detail(void);      /* static, thread-local */
 
+/* ---- `sc fq-demux` (addition, not in the reference): split reads by sample barcode ---------------------------------------
+ * Inputs and units are fq-trim's: one FASTQ (a unit is a read), two FASTQs (unit i is record i of each, pairs =
+ * min(reads1, reads2), the surplus is counted in `unpaired` and goes nowhere) or, with SCFQ_DEMUX_INTERLEAVED, one
+ * interleaved FASTQ (records 2i and 2i+1). Lines, records and texts are those of fq-readstats above; a line the input does
+ * not have is empty. There is no length limit on reads or headers.
+ * Sheet. N = 1 .. SCFQ_DEMUX_MAX_SAMPLES samples, sample s with a name and one or two barcodes b1, b2 of 1 ..
+ *  SCFQ_DEMUX_MAX_BARCODE letters, each exactly 'A', 'C', 'G' or 'T'; either every sample has a second barcode (a dual
+ *  sheet) or none has. A name is 1 .. 63 bytes of [A-Za-z0-9._-], does not start with '.' and is not "undetermined". Two
+ *  samples may share neither their name nor their (b1, b2) pair.
+ * Where the barcode is read. Inline (the default): X1 is the sequence text S of the read, or of mate 1, X2 is S of mate 2;
+ *  a dual sheet with single-end input is SCFQ_EARG. With SCFQ_DEMUX_HEADER: H is the header text of the read, or of mate 1
+ *  (mate 2 is not consulted). Without a ':' in H both X1 and X2 are empty. Otherwise the tail is H behind its last ':'; if
+ *  the tail holds a '+', X1 is the tail before its first '+' and X2 the tail behind it, if not, X1 is the tail and X2 is
+ *  empty (CASAVA 1.8: "@... 1:N:0:ACGTACGT+TGCATGCA").
+ * Assignment, in integers. m1 = |b1|, m2 = |b2| (0 on a single-index sheet). Sample s is ELIGIBLE iff |X1| >= m1 and
+ *  |X2| >= m2; mmk(s) is the number of i < mk with Xk[i] != bk[i], byte for byte ('N' and lower case are mismatches); s
+ *  MATCHES iff it is eligible and mm1 <= M and mm2 <= M, M = mismatches (0 .. 3, default 1); t(s) = mm1 + mm2. The unit
+ *  goes to the matching sample with the smallest t and, among equal t, the larger m1 + m2 ("ACGTAA" wins over "ACGT").
+ *  Two or more matching samples that share the best (t, m1 + m2): the unit is AMBIGUOUS. No eligible sample: NO_BARCODE.
+ *  Eligible samples but no matching one: UNMATCHED. These three kinds are UNDETERMINED, which is destination N.
+ * Records. Every written record has four lines, as fq-trim's: the header text, '\n', the sequence, '\n', the text of the
+ *  separator line, '\n', the quality, '\n' ("\r\n" comes out as '\n', a last line without a newline gains one). Inline
+ *  mode without SCFQ_DEMUX_KEEP_BARCODE: mate k (k = 1, 2) of a unit assigned to s, with mk > 0, is written with
+ *  S[mk, L) and Q[min(LQ, mk), LQ) — L = mk gives an empty sequence line. Everything else is written unclipped:
+ *  undetermined units, header mode, mate 2 under a single-index sheet.
+ * Layout. out1 (and out2 for two inputs) holds the records of destination 0, then 1, .., N - 1, then the undetermined
+ *  ones; each destination in input order. Interleaved input gives one output, mate 1 then mate 2 of each pair. The mates
+ *  of unit u have the same rank within the same destination of out1 and out2.
+ * All values are integers and exact. Device pipeline over the HBM-resident inputs: line index (K5) of each, X1 — a lane
+ *  per unit: the candidate's first 32 bytes as 2-bit codes and a plane of bytes that are not A C G T, every sample of the
+ *  sheet against them by XOR, fold and population count; 8 bytes and a sort key per unit —, a stable radix sort of (key,
+ *  unit) over the key's bits, X2 — a thread per sorted position: record lengths per group of 32 and the rows —, one
+ *  exclusive scan per output, X3 — a wave per group gathers the records from where they lie in the input and writes them
+ *  one behind the other. */
+#define SCFQ_DEMUX_MAX_SAMPLES   1024
+#define SCFQ_DEMUX_MAX_BARCODE   32
+#define SCFQ_DEMUX_INTERLEAVED   0x1u
+#define SCFQ_DEMUX_HEADER        0x2u
+#define SCFQ_DEMUX_KEEP_BARCODE  0x4u
+#define SCFQ_DEMUX_ASSIGNED      0
+#define SCFQ_DEMUX_UNMATCHED     1
+#define SCFQ_DEMUX_AMBIGUOUS     2
+#define SCFQ_DEMUX_NO_BARCODE    3
+typedef struct scfq_demux_sheet scfq_demux_sheet;   /* opaque, host memory only: names, barcodes and their packed form */
+typedef struct scfq_demux_sample {
+  const char* name;        /* NUL-terminated */
+  const char* barcode1;    /* NUL-terminated */
+  const char* barcode2;    /* NUL-terminated, or NULL: no second barcode */
+} scfq_demux_sample;
+typedef struct scfq_demux_opts {       /* 24 bytes */
+  uint64_t struct_size;   /* sizeof(scfq_demux_opts) */
+  uint32_t flags;         /* SCFQ_DEMUX_INTERLEAVED | SCFQ_DEMUX_HEADER | SCFQ_DEMUX_KEEP_BARCODE */
+  uint32_t mismatches;    /* M: 0 .. 3 (opts = NULL: 1) */
+  uint32_t reserved[2];   /* 0 */
+} scfq_demux_opts;
+typedef struct scfq_demux_row {        /* one destination: 64 bytes; entry N is the undetermined one */
+  uint64_t units;
+  uint64_t perfect;       /* units with t = 0; 0 for the undetermined row */
+  uint64_t mismatched;    /* units with t > 0: units = perfect + mismatched for a sample */
+  uint64_t bases_out;     /* sequence bytes written, both mates */
+  uint64_t bytes1, bytes2;   /* the destination's bytes in out1 and out2 */
+  uint64_t off1, off2;    /* where they begin: destination d is out1[off1, off1 + bytes1) and out2[off2, off2 + bytes2) */
+} scfq_demux_row;
+typedef struct scfq_demux_rec {        /* the per-unit table: 8 bytes per unit */
+  uint16_t sample;        /* 0xFFFF when undetermined */
+  uint8_t mm1, mm2;       /* of that sample; 0xFF when undetermined */
+  uint8_t state;          /* SCFQ_DEMUX_ASSIGNED, _UNMATCHED, _AMBIGUOUS or _NO_BARCODE */
+  uint8_t reserved[3];    /* 0 */
+} scfq_demux_rec;
+typedef struct scfq_demux_stats {      /* 29 x 8 bytes */
+  uint64_t struct_size;   /* caller sets to sizeof(scfq_demux_stats) before the call */
+  uint64_t abi_version;   /* library writes SCFQ_ABI_VERSION */
+  uint64_t reads1, reads2;             /* as scfq_trim_stats, down to `unpaired` */
+  uint64_t lines1, lines2;
+  uint64_t input_bytes1, input_bytes2;
+  uint64_t pairs, unpaired;
+  uint64_t units_in;                   /* reads1, or pairs: units_in = assigned + undetermined */
+  uint64_t assigned, undetermined;
+  uint64_t no_barcode, unmatched, ambiguous;   /* sum = undetermined */
+  uint64_t perfect, mismatched;        /* sum = assigned */
+  uint64_t reads_in, reads_out;        /* reads1, or 2 * pairs; equal: nothing is dropped */
+  uint64_t bases_in, bases_out, bases_clipped;   /* sums of L over reads_in; bases_in = bases_out + bases_clipped */
+  uint64_t out1_bytes, out2_bytes;     /* sizes of the outputs, written or not */
+  uint64_t flags, mismatches, n_samples, dual;   /* the parameters as used */
+} scfq_demux_stats;
+
+/* The sheet of n samples. SCFQ_EARG with text in scfq_demux_error_detail(), all decided on the host: n outside 1 ..
+ * SCFQ_DEMUX_MAX_SAMPLES, a NULL, empty, too long, reserved or repeated name or one with another byte, a NULL, empty or too
+ * long barcode1, a barcode byte that is not A C G T, a second barcode on some samples only, a repeated (barcode1, barcode2)
+ * pair. SCFQ_EARG without text for a NULL out. *out is NULL after every failure. No device is touched. */
+int scfq_demux_sheet_new(const scfq_demux_sample* samples, uint32_t n, scfq_demux_sheet** out);
+void scfq_demux_sheet_free(scfq_demux_sheet* sheet);   /* NULL is fine */
+uint32_t scfq_demux_sheet_samples(const scfq_demux_sheet* sheet);   /* N; 0 for a NULL sheet */
+/* the name of sample s, owned by the sheet; "undetermined" for s = N; NULL for a NULL sheet or s > N */
+const char* scfq_demux_sheet_name(const scfq_demux_sheet* sheet, uint32_t s);
+/* r1 / r2, the outputs, the sizing call (both outputs NULL), a too-small output (SCFQ_EARG naming it, stats and rows
+ * complete, NO byte written to ANY output: the host compares the scanned totals with the capacities before X3 is launched)
+ * and the device-pointer rules are those of scfq_trim_buffers. rows_host: HOST memory for row_cap entries, N + 1 of which are
+ * written; row_cap < N + 1 is SCFQ_EARG with text before any launch. recs_device: NULL, or DEVICE memory for rec_cap entries
+ * of the per-unit table; fewer than units_in is SCFQ_EARG with text and nothing is written. SCFQ_EARG with text, before any
+ * device call: a NULL sheet, unknown flag bits, mismatches above 3, reserved not 0, out2 without a second input, a second
+ * buffer with SCFQ_DEMUX_INTERLEAVED, a dual sheet with single-end input in inline mode. opts = NULL: the defaults. One
+ * device, inputs and outputs whole and resident, fewer than 2^31 records per input; there is no CPU fallback (SCFQ_EHIP
+ * without a device). */
+int scfq_demux_buffers(const scfq_demux_sheet* sheet, const void* r1, uint64_t n1, const void* r2, uint64_t n2, int is_device,
+                       const scfq_demux_opts* opts, scfq_demux_rec* recs_device, uint64_t rec_cap, scfq_demux_row* rows_host,
+                       uint64_t row_cap, void* out1, uint64_t cap1, void* out2, uint64_t cap2, int out_is_device,
+                       scfq_demux_stats* stats);
+/* path2 = NULL: path1 is single-end or, with SCFQ_DEMUX_INTERLEAVED in dopts, interleaved (the flag with a path2 is
+ * SCFQ_EARG). Stages the whole (inflated) inputs with scfq_stage_file, ".gz" and BGZF by suffix as everywhere else.
+ * out_dir = NULL: report only. Otherwise the directory has to exist, and every destination gets a file in it, created or
+ * truncated, empty for a destination without a unit: <out_dir>/<name>.fq for one input, <out_dir>/<name>_R1.fq and
+ * <out_dir>/<name>_R2.fq for two, the undetermined units under the name "undetermined". One descriptor is open at a time
+ * (2050 files are more than a common `ulimit -n`). A file that cannot be created is SCFQ_EIO with text; a failing write is
+ * SCFQ_EPIPE / SCFQ_EIO as scfq_merge_files; stats and rows are complete then. recs_host: NULL, or HOST memory for rec_cap
+ * entries of the per-unit table. */
+int scfq_demux_files(const scfq_demux_sheet* sheet, const char* path1, const char* path2, const scfq_opts* opts,
+                     const scfq_demux_opts* dopts, const char* out_dir, scfq_demux_rec* recs_host, uint64_t rec_cap,
+                     scfq_demux_row* rows_host, uint64_t row_cap, scfq_demux_stats* stats);
+/* One report row, without trailing newline, of destination d = 0 .. N with its row of the call that filled s:
+ * "<sample>\t<barcode>\t<units>\t<pct_units>\t<perfect>\t<mismatched>\t<bases_out>\t<bytes1>\t<bytes2>". <barcode> is
+ * barcode1, or barcode1 + '+' + barcode2; the row of d = N is named "undetermined" with the barcode "-". pct_units = 10000 *
+ * units / units_in in integers (0 for units_in = 0), printed with two decimals, as fq-screen's. Returns the number of bytes
+ * needed (excluding NUL); writes at most cap bytes incl. NUL. SCFQ_EARG for a NULL argument, d > N, or stats of another
+ * sheet (n_samples differs). */
+int scfq_format_demux_row_tsv(const scfq_demux_stats* s, const scfq_demux_sheet* sheet, uint32_t d, const scfq_demux_row* row,
+                              char* buf, uint64_t cap);
+const char* scfq_demux_error_detail(void);       /* static, thread-local */
+
 /* ---- `sc fa-gc` (FASTA group): src/fa_gc.nim, docs/fa-gc.md, sc.nim:84-96 --------------------------------------------
  * GC content of the windows [pos - w, pos + w] around 1-based positions of a FASTA. The contract:
  *   Lines.   A header line is a line whose first byte is '>' (a line that starts at byte 0 of the input included); every

@@ -107,6 +107,10 @@ int scfq_debug_trim_stages(double* ms, uint32_t cap);
 int scfq_debug_screen_stages(double* ms, uint32_t cap);
 /* S1, the build kernel of that index, in milliseconds by HIP events; 0 for a NULL index. */
 double scfq_debug_screen_build_ms(const scfq_screen_index* index);
+/* Stage times of the calling thread's last scfq_demux_buffers / scfq_demux_files, in milliseconds: ms[0] X1, the assignment
+ * kernel, ms[1] the radix sort, ms[2] X2 with its scans, ms[3] X3, the gather-write kernel — HIP-event times, taken only while
+ * SCFQ_DEMUX_TIMING=1 is in the environment (zeros otherwise). Writes min(cap, 4) values, returns 4. */
+int scfq_debug_demux_stages(double* ms, uint32_t cap);
 /* Stage times of the calling thread's last scfq_fa_index_buffer / scfq_fa_index_file, in milliseconds: ms[0] F1, the tile scan,
  * ms[1] F2, the scan over the tile records, ms[2] F3, the contig table's kernel, ms[3] unused (0) — HIP-event times, taken only
  * while SCFQ_FA_TIMING=1 is in the environment (zeros otherwise). Writes min(cap, 4) values, returns 4. */

@@ -712,6 +712,144 @@ static int cmd_fq_screen(const std::vector<std::string>& params) {
   return 0;
 }
 
+// command "fq-demux" (addition, not in the reference): --sheet=PATH or --sample=NAME:BC1[+BC2] (up to 1024 times), then IN.fq, R1.fq R2.fq
+// or --interleaved IN.fq; the report goes to stdout, a row per sample and a last row "undetermined"; reads only where --out-dir=DIR
+// says (a file per sample and mate); --barcodes=inline|header, --mismatches=N, --keep-barcode, --per-read=PATH, -t/--header,
+// -b/--basename, -a/--absolute
+static const char* kDemuxHeader = "sample\tbarcode\tunits\tpct_units\tperfect\tmismatched\tbases_out\tbytes1\tbytes2";
+static int cmd_fq_demux(const std::vector<std::string>& params) {
+  static const char* const help =
+      "Split the reads of a pooled run by sample barcode; pairs stay in step\n\nUsage:\n"
+      "  fq-demux [options] (--sheet=PATH | --sample=NAME:BC1[+BC2] ...) [--out-dir=DIR] IN.fq\n"
+      "  fq-demux [options] (--sheet=PATH | --sample=...) [--out-dir=DIR] R1.fq R2.fq\n"
+      "  fq-demux [options] (--sheet=PATH | --sample=...) --interleaved [--out-dir=DIR] IN.fq\n\n"
+      "Arguments:\n  IN.fq            One FASTQ: single-end reads, or pairs with --interleaved\n"
+      "  R1.fq R2.fq      Two FASTQs: record i of each is pair i\n\nOptions:\n"
+      "      --sheet=PATH           The samples, one per line: name<TAB>barcode1[<TAB>barcode2]; '#' lines and blank lines are skipped\n"
+      "      --sample=NAME:BC1[+BC2]  One sample; up to 1024, instead of --sheet\n"
+      "      --out-dir=DIR          An existing directory: NAME.fq per sample and undetermined.fq, or NAME_R1.fq and NAME_R2.fq\n"
+      "                             with R1.fq R2.fq. Without it only the report is made\n"
+      "      --barcodes=inline|header  Where the barcode is read: the first bases of the read (mate 2 for the second barcode), or\n"
+      "                             the header behind its last ':' (BC1+BC2) (default: inline)\n"
+      "      --mismatches=N         Mismatches allowed per barcode (default: 1, 0 .. 3)\n"
+      "      --keep-barcode         Inline barcodes stay in the written reads\n"
+      "      --interleaved          The one argument is an interleaved FASTQ: records 2i and 2i+1 are pair i\n"
+      "      --per-read=PATH        One row per read, or pair, to PATH: unit sample mm1 mm2 state\n"
+      "  -t, --header               Output the header\n  -b, --basename             Add a column with the basename of the first FASTQ\n"
+      "  -a, --absolute             Add a column with the absolute path of the first FASTQ\n"
+      "  -h, --help                 Show this help\n";
+  Columns cols;
+  scfq_demux_opts dopts = fresh<scfq_demux_opts>();
+  dopts.mismatches = 1;
+  std::vector<std::string> files, names, bc1, bc2;
+  std::vector<char> has2;
+  std::string sheet_path, out_dir, per_read;
+  const std::vector<Opt> table = cols.options({
+      opt_text("sheet", &sheet_path),
+      opt_custom("sample", [&](std::string& v) {
+        const size_t colon = v.find(':');
+        if (colon == std::string::npos || colon == 0 || colon + 1 == v.size() || names.size() >= SCFQ_DEMUX_MAX_SAMPLES) return Reject::bad_value;
+        const std::string bc = v.substr(colon + 1);
+        const size_t plus = bc.find('+');
+        names.push_back(v.substr(0, colon));
+        bc1.push_back(bc.substr(0, plus));
+        bc2.push_back(plus == std::string::npos ? "" : bc.substr(plus + 1));
+        has2.push_back(plus != std::string::npos);
+        return Reject::none;
+      }),
+      opt_text("out-dir", &out_dir),
+      opt_custom("barcodes", [&](std::string& v) {
+        if (v == "header") dopts.flags |= SCFQ_DEMUX_HEADER;
+        else if (v == "inline") dopts.flags &= ~SCFQ_DEMUX_HEADER;
+        else return Reject::bad_value;
+        return Reject::none;
+      }),
+      opt_number("mismatches", 1, 0, 3, &dopts.mismatches),
+      opt_bits("keep-barcode", &dopts.flags, SCFQ_DEMUX_KEEP_BARCODE),
+      opt_bits("interleaved", &dopts.flags, SCFQ_DEMUX_INTERLEAVED),
+      opt_text("per-read", &per_read),
+  });
+  if (!parse_options(params, help, table, &files)) return 0;
+  const bool interleaved = dopts.flags & SCFQ_DEMUX_INTERLEAVED;
+  if (sheet_path.empty() == names.empty()) usage_error(help, "fq-demux needs its samples: --sheet=PATH, or --sample=NAME:BC1[+BC2] once per sample");
+  if (files.empty()) quit_no_fastq();
+  if (files.size() > 2 || (interleaved && files.size() != 1)) usage_error(help, "fq-demux takes one FASTQ, R1.fq and R2.fq, or one FASTQ with --interleaved");
+  const bool two = files.size() == 2;
+  for (const std::string& f : files) require_suffix_room(f);
+  // the inputs, the sheet and the directory are looked at before an output file is made
+  for (const std::string& f : files)
+    if (access(f.c_str(), R_OK) != 0) quit_unable_to_open(f);
+  if (!sheet_path.empty()) {
+    FILE* f = std::fopen(sheet_path.c_str(), "r");
+    if (!f) quit_unable_to_open(sheet_path, 2);
+    std::string line;
+    size_t line_no = 0;
+    for (int c = 0; c != EOF;) {
+      line.clear();
+      while ((c = std::fgetc(f)) != EOF && c != '\n') line += (char)c;
+      ++line_no;
+      if (!line.empty() && line.back() == '\r') line.pop_back();
+      if (line.empty() || line[0] == '#') continue;
+      std::vector<std::string> cell(1);
+      for (char ch : line) { if (ch == '\t') cell.emplace_back(); else cell.back() += ch; }
+      if (cell.size() < 2 || cell.size() > 3 || names.size() >= SCFQ_DEMUX_MAX_SAMPLES) {
+        std::fclose(f);
+        quit_error(sheet_path + ": line " + std::to_string(line_no) + " is not name<TAB>barcode1[<TAB>barcode2], or is sample " +
+                   std::to_string(SCFQ_DEMUX_MAX_SAMPLES + 1), 1);
+      }
+      names.push_back(cell[0]);
+      bc1.push_back(cell[1]);
+      bc2.push_back(cell.size() == 3 ? cell[2] : "");
+      has2.push_back(cell.size() == 3);
+    }
+    std::fclose(f);
+    if (names.empty()) quit_error(sheet_path + ": no sample", 1);
+  }
+  std::vector<scfq_demux_sample> samples(names.size());
+  for (size_t s = 0; s < names.size(); ++s) samples[s] = scfq_demux_sample{names[s].c_str(), bc1[s].c_str(), has2[s] ? bc2[s].c_str() : nullptr};
+  scfq_demux_sheet* sheet = nullptr;
+  int rc = scfq_demux_sheet_new(samples.data(), (uint32_t)samples.size(), &sheet);
+  if (rc != SCFQ_OK) quit_error(library_error(rc, scfq_demux_error_detail()), 1);
+  if (!out_dir.empty()) {
+    struct stat sb;
+    if (stat(out_dir.c_str(), &sb) != 0 || !S_ISDIR(sb.st_mode)) quit_error("Not a directory: " + out_dir, 1);
+  }
+  const char* path2 = two ? files[1].c_str() : nullptr;
+  const char* dir = out_dir.empty() ? nullptr : out_dir.c_str();
+  std::vector<scfq_demux_row> rows(samples.size() + 1);
+  scfq_demux_stats st = fresh<scfq_demux_stats>();
+  std::vector<scfq_demux_rec> recs;
+  if (!per_read.empty()) {
+    // the table's length is the number of units: a call without outputs tells it (the assignment runs twice with --per-read)
+    rc = scfq_demux_files(sheet, files[0].c_str(), path2, nullptr, &dopts, nullptr, nullptr, 0, rows.data(), rows.size(), &st);
+    if (rc == SCFQ_OK) recs.assign((size_t)st.units_in, scfq_demux_rec());
+    st = fresh<scfq_demux_stats>();
+  }
+  if (rc == SCFQ_OK)
+    rc = scfq_demux_files(sheet, files[0].c_str(), path2, nullptr, &dopts, dir, recs.empty() ? nullptr : recs.data(), recs.size(), rows.data(), rows.size(), &st);
+  if (rc == SCFQ_EOPEN) quit_unable_to_open(first_unopenable(files[0], two ? &files[1] : nullptr));
+  if (rc != SCFQ_OK) quit_error(library_error(rc, scfq_demux_error_detail()), 1);
+  if (!per_read.empty()) {
+    static const char* const kState[4] = {"assigned", "unmatched", "ambiguous", "no_barcode"};
+    FILE* f = std::fopen(per_read.c_str(), "w");
+    if (!f) quit_error("Unable to create file: " + per_read, 1);
+    for (size_t u = 0; u < recs.size(); ++u) {
+      const bool assigned = recs[u].state == SCFQ_DEMUX_ASSIGNED;
+      if (assigned) std::fprintf(f, "%zu\t%s\t%u\t%u\t%s\n", u, scfq_demux_sheet_name(sheet, recs[u].sample), (unsigned)recs[u].mm1, (unsigned)recs[u].mm2, kState[0]);
+      else std::fprintf(f, "%zu\t-\t-\t-\t%s\n", u, kState[recs[u].state & 3u]);
+    }
+    if (std::fclose(f) != 0) quit_error("Unable to write file: " + per_read, 1);
+  }
+  if (cols.header) std::printf("%s\n", output_header(kDemuxHeader, cols.basename, cols.absolute).c_str());
+  for (uint32_t d = 0; d <= samples.size(); ++d) {
+    char row[1024];
+    scfq_format_demux_row_tsv(&st, sheet, d, &rows[d], row, sizeof row);
+    cols.emit_row(row, files[0]);
+  }
+  scfq_demux_sheet_free(sheet);
+  return 0;
+}
+
 // command "fq-kmers" (addition, not in the reference): -t/--header, -b/--basename, -a/--absolute as fq-count, --k=N, --canonical, --top=N,
 // --totals, [fastq ...]
 static const char* kKmersHeader = "kmer\tcount";
@@ -1214,7 +1352,8 @@ int main(int argc, char** argv) {
       {"fq-count", cmd_fq_count},       {"fq-dedup", cmd_fq_dedup},       {"fq-meta", cmd_fq_meta},
       {"fq-readstats", cmd_fq_readstats}, {"fq-cycles", cmd_fq_cycles},   {"fq-kmers", cmd_fq_kmers},
       {"fq-adapters", cmd_fq_adapters}, {"fq-insert-size", cmd_fq_insert_size}, {"fq-merge", cmd_fq_merge},
-      {"fq-trim", cmd_fq_trim},         {"fq-screen", cmd_fq_screen},     {"fa-gc", cmd_fa_gc}};
+      {"fq-trim", cmd_fq_trim},         {"fq-screen", cmd_fq_screen},     {"fq-demux", cmd_fq_demux},
+      {"fa-gc", cmd_fa_gc}};
   for (const auto& c : commands)
     if (params[0] == c.name) return c.run(params);
   help_top(stdout);

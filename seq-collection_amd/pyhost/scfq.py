@@ -58,6 +58,8 @@ EXPORTS = [
     "scfq_screen_index_buffers", "scfq_screen_index_files", "scfq_screen_index_free", "scfq_screen_index_summary", "scfq_screen_ref_name",
     "scfq_screen_buffers", "scfq_screen_files", "scfq_format_screen_row_tsv", "scfq_screen_error_detail", "scfq_debug_screen_stages",
     "scfq_debug_screen_build_ms",
+    "scfq_demux_sheet_new", "scfq_demux_sheet_free", "scfq_demux_sheet_samples", "scfq_demux_sheet_name", "scfq_demux_buffers", "scfq_demux_files",
+    "scfq_format_demux_row_tsv", "scfq_demux_error_detail", "scfq_debug_demux_stages",
     "scfq_fa_index_buffer", "scfq_fa_index_file", "scfq_fa_contig_at", "scfq_fa_contig_find", "scfq_fa_count_intervals",
     "scfq_fa_index_free", "scfq_fa_error_detail", "scfq_fa_parse_window", "scfq_fa_gc_interval", "scfq_format_fa_gc_value",
     "scfq_debug_fa_stages",
@@ -268,6 +270,40 @@ class ScreenStats(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64 * 16 if n in SCREEN_PER_REF_FIELDS else ctypes.c_uint64) for n in SCREEN_STATS_FIELDS]
 
 
+SCFQ_DEMUX_INTERLEAVED, SCFQ_DEMUX_HEADER, SCFQ_DEMUX_KEEP_BARCODE = 0x1, 0x2, 0x4
+SCFQ_DEMUX_ASSIGNED, SCFQ_DEMUX_UNMATCHED, SCFQ_DEMUX_AMBIGUOUS, SCFQ_DEMUX_NO_BARCODE = 0, 1, 2, 3
+DEMUX_MAX_SAMPLES, DEMUX_MAX_BARCODE = 1024, 32
+DEMUX_ROW_FIELDS = ("units", "perfect", "mismatched", "bases_out", "bytes1", "bytes2", "off1", "off2")
+DEMUX_STATS_FIELDS = ("struct_size", "abi_version", "reads1", "reads2", "lines1", "lines2", "input_bytes1", "input_bytes2", "pairs", "unpaired",
+                      "units_in", "assigned", "undetermined", "no_barcode", "unmatched", "ambiguous", "perfect", "mismatched", "reads_in", "reads_out",
+                      "bases_in", "bases_out", "bases_clipped", "out1_bytes", "out2_bytes", "flags", "mismatches", "n_samples", "dual")
+
+
+class DemuxSample(ctypes.Structure):
+    """scfq_demux_sample"""
+    _fields_ = [("name", ctypes.c_char_p), ("barcode1", ctypes.c_char_p), ("barcode2", ctypes.c_char_p)]
+
+
+class DemuxOpts(ctypes.Structure):
+    """scfq_demux_opts (24 bytes)"""
+    _fields_ = [("struct_size", ctypes.c_uint64), ("flags", ctypes.c_uint32), ("mismatches", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 2)]
+
+
+class DemuxRow(ctypes.Structure):
+    """scfq_demux_row (eight uint64): one destination"""
+    _fields_ = [(n, ctypes.c_uint64) for n in DEMUX_ROW_FIELDS]
+
+
+class DemuxRec(ctypes.Structure):
+    """scfq_demux_rec (8 bytes): one unit"""
+    _fields_ = [("sample", ctypes.c_uint16), ("mm1", ctypes.c_uint8), ("mm2", ctypes.c_uint8), ("state", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 3)]
+
+
+class DemuxStats(ctypes.Structure):
+    """scfq_demux_stats (29 uint64)"""
+    _fields_ = [(n, ctypes.c_uint64) for n in DEMUX_STATS_FIELDS]
+
+
 FA_SUMMARY_FIELDS = ("struct_size", "abi_version", "input_bytes", "tiles", "contigs", "bases", "gc_bases", "acgt_bases", "orphan_bases")
 
 
@@ -447,6 +483,21 @@ def lib():
         L.scfq_debug_screen_stages.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]
         L.scfq_debug_screen_build_ms.argtypes = [vp]
         L.scfq_debug_screen_build_ms.restype = ctypes.c_double
+        L.scfq_demux_sheet_new.argtypes = [ctypes.POINTER(DemuxSample), ctypes.c_uint32, pvp]
+        L.scfq_demux_sheet_free.argtypes = [vp]
+        L.scfq_demux_sheet_free.restype = None
+        L.scfq_demux_sheet_samples.argtypes = [vp]
+        L.scfq_demux_sheet_samples.restype = ctypes.c_uint32
+        L.scfq_demux_sheet_name.argtypes = [vp, ctypes.c_uint32]
+        L.scfq_demux_sheet_name.restype = ctypes.c_char_p
+        L.scfq_demux_buffers.argtypes = [vp, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(DemuxOpts),
+                                         ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                         ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(DemuxStats)]
+        L.scfq_demux_files.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_void_p, ctypes.POINTER(DemuxOpts), ctypes.c_char_p, ctypes.c_void_p,
+                                       ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(DemuxStats)]
+        L.scfq_format_demux_row_tsv.argtypes = [ctypes.POINTER(DemuxStats), vp, ctypes.c_uint32, ctypes.POINTER(DemuxRow), ctypes.c_char_p, ctypes.c_uint64]
+        L.scfq_demux_error_detail.restype = ctypes.c_char_p
+        L.scfq_debug_demux_stages.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]
         L.scfq_fa_index_buffer.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, pvp, ctypes.POINTER(FaSummary)]
         L.scfq_fa_index_file.argtypes = [ctypes.c_char_p, ctypes.c_void_p, pvp, ctypes.POINTER(FaSummary)]
         L.scfq_fa_contig_at.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(FaContig)]
@@ -1279,6 +1330,127 @@ def screen_stages():
     last three are HIP-event times and zeros unless SCFQ_SCREEN_TIMING=1 is in the environment"""
     ms = (ctypes.c_double * 4)()
     lib().scfq_debug_screen_stages(ms, 4)
+    return list(ms)
+
+
+def _demux_error(rc, what):
+    return ScfqError(rc, what, lib().scfq_demux_error_detail().decode() or lib().scfq_last_error_detail().decode())
+
+
+class DemuxSheet:
+    """scfq_demux_sheet: the samples of a run, host memory only.  `names` has N + 1 entries, the last one "undetermined"; `samples` the
+    (name, barcode1, barcode2 or None) triples as given.  close() (or the end of a `with`) frees it."""
+
+    def __init__(self, handle, samples):
+        self._h, self.samples = handle, samples
+        self.n = int(lib().scfq_demux_sheet_samples(handle))
+        self.names = [lib().scfq_demux_sheet_name(handle, s).decode("latin-1") for s in range(self.n + 1)]
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if self._h:
+            lib().scfq_demux_sheet_free(self._h)
+        self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def demux_sheet(samples):
+    """samples: a list of (name, barcode1) or (name, barcode1, barcode2), each bytes or str (None stays NULL)"""
+    raw = lambda x: None if x is None else (x.encode("latin-1") if isinstance(x, str) else bytes(x))
+    triples = [(raw(t[0]), raw(t[1]), raw(t[2]) if len(t) > 2 else None) for t in samples]
+    arr = (DemuxSample * max(len(triples), 1))()
+    for i, t in enumerate(triples):
+        arr[i] = DemuxSample(*t)
+    h = ctypes.c_void_p()
+    rc = lib().scfq_demux_sheet_new(arr, len(triples), ctypes.byref(h))
+    if rc != 0:
+        raise _demux_error(rc, "scfq_demux_sheet_new")
+    return DemuxSheet(h, triples)
+
+
+def demux_opts(interleaved=False, header=False, keep_barcode=False, mismatches=1, flags=None, reserved=(0, 0)):
+    o = DemuxOpts()
+    o.struct_size = ctypes.sizeof(DemuxOpts)
+    o.flags = flags if flags is not None else (SCFQ_DEMUX_INTERLEAVED if interleaved else 0) | (SCFQ_DEMUX_HEADER if header else 0) | \
+        (SCFQ_DEMUX_KEEP_BARCODE if keep_barcode else 0)
+    o.mismatches = mismatches
+    o.reserved[0], o.reserved[1] = reserved
+    return o
+
+
+def _demux_call(fn, what, sheet, opts, head, mid, tail, row_cap=None):
+    """Returns (DemuxStats, rows): rows is a list of N + 1 DemuxRow.  An ScfqError carries both as `stats` and `rows` (complete when an
+    output was too small).  row_cap: the capacity told to the library, None: N + 1."""
+    s = DemuxStats()
+    s.struct_size = ctypes.sizeof(DemuxStats)
+    n = sheet.n if isinstance(sheet, DemuxSheet) else 0
+    rows = (DemuxRow * (n + 1))()
+    handle = sheet.handle if isinstance(sheet, DemuxSheet) else sheet
+    rc = fn(handle, *head, ctypes.byref(opts) if opts is not None else None, *mid, ctypes.cast(rows, ctypes.c_void_p), n + 1 if row_cap is None else row_cap,
+            *tail, ctypes.byref(s))
+    if rc != 0:
+        e = _demux_error(rc, what)
+        e.stats, e.rows = s, list(rows)
+        raise e
+    return s, list(rows)
+
+
+def demux_device(sheet, ptr1, n1, ptr2=None, n2=0, opts=None, out1=None, out2=None, recs=None, row_cap=None):
+    """fq-demux of device-resident FASTQs (the pointer rules of trim_device).  out1 / out2: (device address, capacity) or None; recs:
+    (device address, entries) of the per-unit table or None.  Returns (DemuxStats, rows)."""
+    return _demux_call(lib().scfq_demux_buffers, "scfq_demux_buffers", sheet, opts,
+                       [ctypes.c_void_p(ptr1), n1, ctypes.c_void_p(ptr2) if ptr2 is not None else None, n2, 1],
+                       [ctypes.c_void_p(recs[0]) if recs else None, recs[1] if recs else 0], _trim_outputs((out1, out2)) + [1], row_cap)
+
+
+def demux_host(sheet, data1, data2=None, opts=None, caps=None):
+    """fq-demux of host buffers; caps as trim_host's.  Returns (DemuxStats, rows, out1, out2), the outputs as bytes or None."""
+    a1, n1, keep1 = _host_ptr(data1)
+    a2, n2, keep2 = _host_ptr(data2) if data2 is not None else (None, 0, None)
+    head = [a1, n1, a2, n2, 0]
+    fn = lib().scfq_demux_buffers
+    if caps is None:
+        s, rows = _demux_call(fn, "scfq_demux_buffers", sheet, opts, head, [None, 0], [None, 0, None, 0, 0])
+        caps = (s.out1_bytes, s.out2_bytes if data2 is not None else None)
+    bufs = [None if c is None else ctypes.create_string_buffer(max(int(c), 1)) for c in caps]
+    outs = [None if b is None else (ctypes.addressof(b), int(c)) for b, c in zip(bufs, caps)]
+    s, rows = _demux_call(fn, "scfq_demux_buffers", sheet, opts, head, [None, 0], _trim_outputs(outs) + [0])
+    sizes = (s.out1_bytes, s.out2_bytes)
+    return (s, rows) + tuple(None if b is None else b.raw[:int(k)] for b, k in zip(bufs, sizes))
+
+
+def demux_file(sheet, path1, path2=None, opts=None, out_dir=None, recs=None):
+    """out_dir: None (report only) or an existing directory that receives a file per destination and mate.  recs: None, or a ctypes
+    array of DemuxRec that receives the per-unit table.  Returns (DemuxStats, rows)."""
+    return _demux_call(lib().scfq_demux_files, "scfq_demux_files", sheet, opts,
+                       [os.fsencode(path1), os.fsencode(path2) if path2 is not None else None, None],
+                       [os.fsencode(out_dir) if out_dir is not None else None, ctypes.cast(recs, ctypes.c_void_p) if recs is not None else None,
+                        len(recs) if recs is not None else 0], [])
+
+
+def format_demux_row_tsv(s, sheet, d, row):
+    buf = ctypes.create_string_buffer(1024)
+    n = lib().scfq_format_demux_row_tsv(ctypes.byref(s), sheet.handle, d, ctypes.byref(row), buf, 1024)
+    if n < 0:
+        raise ScfqError(n, "scfq_format_demux_row_tsv")
+    return buf.value.decode("latin-1")
+
+
+def demux_stages():
+    """(assignment kernel, radix sort, lengths and scans, gather-write kernel) milliseconds of this thread's last demux call: HIP-event
+    times, zeros unless SCFQ_DEMUX_TIMING=1 is in the environment"""
+    ms = (ctypes.c_double * 4)()
+    lib().scfq_debug_demux_stages(ms, 4)
     return list(ms)
 
 
