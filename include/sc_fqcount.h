@@ -1003,6 +1003,93 @@ int scfq_format_demux_row_tsv(const scfq_demux_stats* s, const scfq_demux_sheet*
                               char* buf, uint64_t cap);
 const char* scfq_demux_error_detail(void);       /* static, thread-local */
 
+/* ---- `sc fq-kcount` (addition; not in the reference): k-mer counts for k = 13 .. 32 in a hash table on the device -----
+ * Lines, records, windows, k-mers, skipped and short_lines are exactly those of fq-kmers above; so is the key (codes A = 0,
+ * C = 1, G = 2, T = 3, first base most significant, here in 64 bits) and the canonical mode (a k-mer is counted at
+ * min(key, rc(key)); a palindrome once per occurrence). Where fq-kmers holds 4^k counters, this one holds the keys that
+ * occur: an open-addressing table of (key, count) slots, linear probing, a power of two of slots. Every value is an
+ * integer and exact; counts are 64 bits.
+ *   Inputs.  One input (r2 = NULL, n2 = 0) or two, which are counted into ONE table: reads, lines, windows and the rest are
+ *            the sums over both. The two are not paired and their lengths may differ.
+ *   Sizing.  opts->table_bits = 0: the table starts at the power of two >= 2 * (n1 + n2) slots (at least 2^10, at most
+ *            2^30; SCFQ_KCOUNT_START_BITS in the environment lowers it) and grows fourfold per failed pass while it fits
+ *            into half of the free device memory. table_bits = 10 .. 32: that size and no growth. A pass fails when a key
+ *            found no slot within the probe bound (512 slots with automatic sizing, min(slots, 4096) with table_bits;
+ *            SCFQ_KCOUNT_MAX_PROBE overrides both); a failed pass is thrown away whole and the input, which is resident,
+ *            is counted again: no count is ever applied twice. SCFQ_EFULL: the table named by table_bits could not hold
+ *            the keys (or could not be allocated), or growth ran out of device memory; the detail names the slot count.
+ *   Summary. Every field but slots and passes is independent of table_bits. kmers is the sum of the counts in the table,
+ *            windows and skipped are counted by the lanes that see the windows: windows = kmers + skipped compares two
+ *            counts made in different ways. slots and passes are diagnostics: the size of the table of the last pass
+ *            and the number of passes over the input (one with a table that is large enough). */
+#define SCFQ_KCOUNT_MIN_K     13
+#define SCFQ_KCOUNT_MAX_K     32
+#define SCFQ_KCOUNT_CANONICAL 0x1u
+#define SCFQ_EFULL   (-10) /* fq-kcount: the hash table could not hold the keys (see Sizing above) */
+typedef struct scfq_kcount scfq_kcount;          /* opaque: the table on the device */
+typedef struct scfq_kcount_opts {
+  uint64_t struct_size;   /* caller sets to sizeof(scfq_kcount_opts) */
+  uint32_t k;             /* SCFQ_KCOUNT_MIN_K .. SCFQ_KCOUNT_MAX_K */
+  uint32_t flags;         /* SCFQ_KCOUNT_CANONICAL */
+  uint32_t table_bits;    /* 0: automatic; 10 .. 32: 2^table_bits slots, no growth */
+  uint32_t reserved;      /* 0 */
+} scfq_kcount_opts;
+typedef struct scfq_kcount_summary {
+  uint64_t struct_size;   /* caller sets to sizeof(scfq_kcount_summary) before the call */
+  uint64_t abi_version;   /* library writes SCFQ_ABI_VERSION */
+  uint64_t reads;         /* (lines + 3) / 4 per input, summed */
+  uint64_t lines;
+  uint64_t input_bytes;
+  uint64_t k;
+  uint64_t flags;
+  uint64_t windows;       /* kmers + skipped */
+  uint64_t kmers;         /* the sum of the counts in the table */
+  uint64_t skipped;       /* windows with a byte that is not A C G T */
+  uint64_t short_lines;   /* sequence lines with fewer than k text bytes */
+  uint64_t distinct;      /* keys in the table */
+  uint64_t unique;        /* keys whose count is 1 */
+  uint64_t max_count;
+  uint64_t slots;         /* diagnostic: slots of the table of the last pass */
+  uint64_t passes;        /* diagnostic: passes over the input */
+} scfq_kcount_summary;
+typedef struct scfq_kmer_count { uint64_t key, count; } scfq_kmer_count;
+
+/* Counts the k-mers of one or two inputs in host (is_device = 0) or device memory. out: receives the table, to be freed
+ * with scfq_kcount_free, or NULL for the summary only; sum: the whole summary either way, or NULL. At least one of the two
+ * is given. *out is NULL after every failure. SCFQ_EARG with text in scfq_kcount_error_detail(), found before any HIP call:
+ * k outside 13 .. 32, unknown flag bits, table_bits not 0 and outside 10 .. 32, a non-zero reserved, a wrong struct_size
+ * (opts' or sum's), a NULL opts, a NULL input with n > 0, a second input without a first. Device pointers follow the
+ * scfq_set_wait_stream contract of scfq_index_lines and may have any alignment. One device, the whole input resident,
+ * fewer than 2^31 records per input; there is no CPU fallback (SCFQ_EHIP without a device). */
+int scfq_kcount_buffers(const void* r1, uint64_t n1, const void* r2, uint64_t n2, int is_device, const scfq_kcount_opts* opts,
+                        scfq_kcount** out, scfq_kcount_summary* sum);
+/* The same from files (path2 may be NULL): the whole (inflated) inputs are staged with scfq_stage_file, ".gz" and BGZF by
+ * suffix as everywhere else; SCFQ_EOPEN for a file that cannot be opened. */
+int scfq_kcount_files(const char* path1, const char* path2, const scfq_opts* opts, const scfq_kcount_opts* kopts,
+                      scfq_kcount** out, scfq_kcount_summary* sum);
+/* The multiplicity histogram, 2 <= bins <= 2^20 entries of HOST memory: hist[0] = 0, hist[c] for 1 <= c <= bins - 2 is the
+ * number of keys with count c, hist[bins - 1] the number of keys with count >= bins - 1: the sum is `distinct`. SCFQ_EARG
+ * for a NULL argument or bins out of range. hist, dump and query work in device memory that belongs to the table (8 MiB
+ * behind its slots, allocated with it; they take none of their own), so the calls on one table run one after the other:
+ * a second thread's call waits. Calls on different tables do not wait for each other. */
+int scfq_kcount_hist(const scfq_kcount* t, uint64_t* hist_host, uint64_t bins);
+/* The keys with min_count <= count (and count <= max_count unless that is 0) in ascending key order, sorted on the host
+ * (the table is read in pieces of 2^19 slots, each piece's rows copied behind the last one's).
+ * *total is always the number of keys that qualify; with cap < *total nothing is written and the call still returns 0 (as
+ * snprintf sizes); entries behind *total are not touched. out_host may be NULL with cap = 0. */
+int scfq_kcount_dump(const scfq_kcount* t, uint64_t min_count, uint64_t max_count, scfq_kmer_count* out_host, uint64_t cap,
+                     uint64_t* total);
+/* counts_host[i] = the count of keys_host[i], 0 for a key that is absent. The keys are plain indices; in canonical mode the
+ * library takes the minimum with the reverse complement itself. A key >= 4^k: SCFQ_EARG, the text names it, nothing is
+ * written. n = 0 is valid. */
+int scfq_kcount_query(const scfq_kcount* t, const uint64_t* keys_host, uint64_t n, uint64_t* counts_host);
+void scfq_kcount_free(scfq_kcount* t);           /* NULL is fine */
+/* "<kmer>\t<count>" without trailing newline: the k letters of `key`, first base first. Returns the number of bytes needed
+ * (excluding NUL); writes at most cap bytes incl. NUL, as scfq_format_kmer_tsv. SCFQ_EARG for k outside 13 .. 32 or
+ * key >= 4^k. */
+int scfq_format_kcount_tsv(uint32_t k, uint64_t key, uint64_t count, char* buf, uint64_t cap);
+const char* scfq_kcount_error_detail(void);      /* static, thread-local */
+
 /* ---- `sc fa-gc` (FASTA group): src/fa_gc.nim, docs/fa-gc.md, sc.nim:84-96 --------------------------------------------
  * GC content of the windows [pos - w, pos + w] around 1-based positions of a FASTA. The contract:
  *   Lines.   A header line is a line whose first byte is '>' (a line that starts at byte 0 of the input included); every

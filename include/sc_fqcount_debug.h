@@ -111,6 +111,12 @@ double scfq_debug_screen_build_ms(const scfq_screen_index* index);
  * kernel, ms[1] the radix sort, ms[2] X2 with its scans, ms[3] X3, the gather-write kernel — HIP-event times, taken only while
  * SCFQ_DEMUX_TIMING=1 is in the environment (zeros otherwise). Writes min(cap, 4) values, returns 4. */
 int scfq_debug_demux_stages(double* ms, uint32_t cap);
+/* Stage times of the calling thread's last fq-kcount calls, in milliseconds: ms[0] the line indexes of scfq_kcount_buffers /
+ * scfq_kcount_files (host clock around the synchronous index calls), ms[1] H1, the counting kernel over every input in the
+ * LAST pass (the clear of the table not included), ms[2] H2, the finish, ms[3] H3 of the last scfq_kcount_hist — [1..3] are
+ * HIP-event times, taken only while SCFQ_KCOUNT_TIMING=1 is in the environment (zeros otherwise). Writes min(cap, 4) values,
+ * returns 4. */
+int scfq_debug_kcount_stages(double* ms, uint32_t cap);
 /* Stage times of the calling thread's last scfq_fa_index_buffer / scfq_fa_index_file, in milliseconds: ms[0] F1, the tile scan,
  * ms[1] F2, the scan over the tile records, ms[2] F3, the contig table's kernel, ms[3] unused (0) — HIP-event times, taken only
  * while SCFQ_FA_TIMING=1 is in the environment (zeros otherwise). Writes min(cap, 4) values, returns 4. */

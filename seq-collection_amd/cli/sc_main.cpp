@@ -914,6 +914,119 @@ static int cmd_fq_kmers(const std::vector<std::string>& params) {
   return 0;
 }
 
+// command "fq-kcount" (addition, not in the reference): -t/--header, -b/--basename, -a/--absolute as fq-count, --k=N, --canonical,
+// --table-bits=N, --high=N, --totals, --dump [--min-count=C] [--max-count=C], --top=N, IN.fq [IN2.fq]
+static const char* kKcountHistHeader = "count\tkmers";
+static const char* kKcountTotalsHeader = "k\twindows\tkmers\tskipped\tshort_lines\tdistinct\tunique\tmax_count";
+static int cmd_fq_kcount(const std::vector<std::string>& params) {
+  static const char* const help =
+      "K-mer counts of the sequence lines of one or two FASTQ, k = 13 .. 32, in a hash table on the device\n\n"
+      "Usage:\n  fq-kcount [options] IN.fq [IN2.fq]\n\nArguments:\n"
+      "  IN.fq [IN2.fq]   Input FASTQ; two files are counted together into one table\n\nOptions:\n"
+      "  -t, --header               Output the header\n"
+      "  -b, --basename             Add basename column (of IN.fq)\n  -a, --absolute             Add column for absolute path (of IN.fq)\n"
+      "      --k=N                  Length of the k-mers, 13 .. 32 (default: 21); only windows of A C G T count\n"
+      "      --canonical            Count a k-mer and its reverse complement as the smaller of the two\n"
+      "      --table-bits=N         A table of 2^N slots, 10 .. 32, that does not grow (default: sized by the input, and\n"
+      "                             grown fourfold when it turns out too small)\n"
+      "      --high=N               The default output, the histogram of the counts: a row \"count kmers\" for every count\n"
+      "                             from 1 to min(largest count, N), zeros included, and a row N + 1 that holds everything\n"
+      "                             above when there is any (default: 10000, at most 1048574)\n"
+      "      --totals               One row instead: k windows kmers skipped short_lines distinct unique max_count\n"
+      "      --dump                 The k-mers and their counts instead, in k-mer order\n"
+      "      --min-count=C          With --dump: only k-mers that occur at least C times (default: 1)\n"
+      "      --max-count=C          With --dump: only k-mers that occur at most C times\n"
+      "      --top=N                The N most frequent k-mers instead, ties in k-mer order\n"
+      "  -h, --help                 Show this help\n";
+  const uint64_t kNone = ~0ull, kTopCandidates = 1ull << 24;
+  Columns cols;
+  bool totals = false, dump = false;
+  uint32_t k = 21, flags = 0, table_bits = 0;
+  uint64_t high = 10000, top = kNone, min_count = kNone, max_count = kNone;
+  std::vector<std::string> files;
+  const std::vector<Opt> options = cols.options({
+      opt_number("k", 18, SCFQ_KCOUNT_MIN_K, SCFQ_KCOUNT_MAX_K, &k),
+      opt_bits("canonical", &flags, SCFQ_KCOUNT_CANONICAL),
+      opt_number("table-bits", 18, 10, 32, &table_bits),
+      opt_number("high", 18, 1, (1ull << 20) - 2, &high),
+      opt_flag("totals", 0, &totals),
+      opt_flag("dump", 0, &dump),
+      opt_number("min-count", 18, 1, ~0ull, &min_count),
+      opt_number("max-count", 18, 1, ~0ull, &max_count),
+      opt_number("top", 18, 0, kNone - 1, &top),      // (18 digits cannot say kNone)
+  });
+  if (!parse_options(params, help, options, &files)) return 0;
+  if ((int)totals + (int)dump + (int)(top != kNone) > 1) usage_error(help, "--totals, --dump and --top exclude each other");
+  if (!dump && (min_count != kNone || max_count != kNone)) usage_error(help, "--min-count and --max-count go with --dump");
+  if (min_count != kNone && max_count != kNone && max_count < min_count) usage_error(help, "--max-count is below --min-count");
+  if (files.size() > 2) usage_error(help, "at most two FASTQ are counted together");
+  cols.header_or_no_input(totals ? kKcountTotalsHeader : (dump || top != kNone) ? kKmersHeader : kKcountHistHeader, files.empty());
+  if (files.empty()) return 0;
+  for (const auto& f : files) require_suffix_room(f);
+  const std::string* second = files.size() > 1 ? &files[1] : nullptr;
+  scfq_kcount_opts ko = fresh<scfq_kcount_opts>();
+  ko.k = k;
+  ko.flags = flags;
+  ko.table_bits = table_bits;
+  scfq_kcount_summary s = fresh<scfq_kcount_summary>();
+  scfq_kcount* table = nullptr;
+  int rc = scfq_kcount_files(files[0].c_str(), second ? second->c_str() : nullptr, nullptr, &ko, totals ? nullptr : &table, &s);
+  if (rc == SCFQ_EOPEN) quit_unable_to_open(first_unopenable(files[0], second));
+  if (rc != SCFQ_OK) quit_error(library_error(rc, scfq_kcount_error_detail()), 1);
+  auto must = [&](int code) { if (code != SCFQ_OK) quit_error(library_error(code, scfq_kcount_error_detail()), 1); };
+  char row[96];
+  if (totals) {
+    cols.emit_row(std::to_string(s.k) + "\t" + std::to_string(s.windows) + "\t" + std::to_string(s.kmers) + "\t" + std::to_string(s.skipped) + "\t" +
+                      std::to_string(s.short_lines) + "\t" + std::to_string(s.distinct) + "\t" + std::to_string(s.unique) + "\t" +
+                      std::to_string(s.max_count),
+                  files[0]);
+  } else if (dump) {
+    std::vector<scfq_kmer_count> rows;
+    uint64_t total = 0;
+    const uint64_t lo = min_count == kNone ? 1 : min_count, hi = max_count == kNone ? 0 : max_count;
+    must(scfq_kcount_dump(table, lo, hi, nullptr, 0, &total));
+    rows.resize((size_t)total);
+    if (total) must(scfq_kcount_dump(table, lo, hi, rows.data(), total, &total));
+    for (const auto& r : rows) {
+      scfq_format_kcount_tsv(k, r.key, r.count, row, sizeof row);
+      cols.emit_row(row, files[0]);
+    }
+  } else if (top != kNone) {
+    // the count of the last place is read off the histogram; the k-mers with that count or more are the candidates
+    const uint64_t bins = std::min<uint64_t>(s.max_count + 2, 1ull << 20);
+    std::vector<uint64_t> hist((size_t)bins);
+    must(scfq_kcount_hist(table, hist.data(), bins));
+    uint64_t threshold = bins - 1, above = 0;
+    for (; threshold > 1 && above + hist[threshold] < top; --threshold) above += hist[threshold];
+    std::vector<scfq_kmer_count> rows;
+    uint64_t total = 0;
+    if (top) must(scfq_kcount_dump(table, threshold, 0, nullptr, 0, &total));
+    if (total > kTopCandidates)
+      usage_error(help, "--top=" + std::to_string(top) + ": " + std::to_string(total) + " k-mers occur " + std::to_string(threshold) +
+                            " times or more, which are more than " + std::to_string(kTopCandidates) + " candidates; use --dump --min-count=C");
+    rows.resize((size_t)total);
+    if (total) must(scfq_kcount_dump(table, threshold, 0, rows.data(), total, &total));
+    const size_t keep = (size_t)std::min<uint64_t>(top, rows.size());
+    std::partial_sort(rows.begin(), rows.begin() + keep, rows.end(), [](const scfq_kmer_count& a, const scfq_kmer_count& b) {
+      return a.count != b.count ? a.count > b.count : a.key < b.key;
+    });
+    rows.resize(keep);
+    for (const auto& r : rows) {
+      scfq_format_kcount_tsv(k, r.key, r.count, row, sizeof row);
+      cols.emit_row(row, files[0]);
+    }
+  } else {
+    const uint64_t bins = high + 2;
+    std::vector<uint64_t> hist((size_t)bins);
+    must(scfq_kcount_hist(table, hist.data(), bins));
+    for (uint64_t c = 1; c <= std::min<uint64_t>(s.max_count, high); ++c) cols.emit_row(std::to_string(c) + "\t" + std::to_string(hist[c]), files[0]);
+    if (hist[high + 1]) cols.emit_row(std::to_string(high + 1) + "\t" + std::to_string(hist[high + 1]), files[0]);
+  }
+  scfq_kcount_free(table);
+  std::fflush(stdout);
+  return 0;
+}
+
 // command "fq-adapters" (addition, not in the reference): -t/--header, -b/--basename, -a/--absolute as fq-count, --adapter=NAME:SEQ,
 // --max-positions=N, --counts, --totals, [fastq ...]
 static const char* kAdaptersTotalsHeader = "adapter\tsequence\treads\treads_with\tpercent\thits";
@@ -1353,7 +1466,7 @@ int main(int argc, char** argv) {
       {"fq-readstats", cmd_fq_readstats}, {"fq-cycles", cmd_fq_cycles},   {"fq-kmers", cmd_fq_kmers},
       {"fq-adapters", cmd_fq_adapters}, {"fq-insert-size", cmd_fq_insert_size}, {"fq-merge", cmd_fq_merge},
       {"fq-trim", cmd_fq_trim},         {"fq-screen", cmd_fq_screen},     {"fq-demux", cmd_fq_demux},
-      {"fa-gc", cmd_fa_gc}};
+      {"fq-kcount", cmd_fq_kcount},     {"fa-gc", cmd_fa_gc}};
   for (const auto& c : commands)
     if (params[0] == c.name) return c.run(params);
   help_top(stdout);

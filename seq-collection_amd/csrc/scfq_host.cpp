@@ -238,6 +238,7 @@ const char* scfq_strerror(int rc) {
     case SCFQ_EPIPE: return "broken pipe on the output descriptor";
     case SCFQ_ENOMEM: return "out of host memory";
     case SCFQ_ESPEC: return "speculative quality histogram did not verify across shards (retry with SCFQ_HIST_EXACT)";
+    case SCFQ_EFULL: return "the k-mer table is full";
     default: return "unknown error";
   }
 }

@@ -60,6 +60,8 @@ EXPORTS = [
     "scfq_debug_screen_build_ms",
     "scfq_demux_sheet_new", "scfq_demux_sheet_free", "scfq_demux_sheet_samples", "scfq_demux_sheet_name", "scfq_demux_buffers", "scfq_demux_files",
     "scfq_format_demux_row_tsv", "scfq_demux_error_detail", "scfq_debug_demux_stages",
+    "scfq_kcount_buffers", "scfq_kcount_files", "scfq_kcount_hist", "scfq_kcount_dump", "scfq_kcount_query", "scfq_kcount_free",
+    "scfq_format_kcount_tsv", "scfq_kcount_error_detail", "scfq_debug_kcount_stages",
     "scfq_fa_index_buffer", "scfq_fa_index_file", "scfq_fa_contig_at", "scfq_fa_contig_find", "scfq_fa_count_intervals",
     "scfq_fa_index_free", "scfq_fa_error_detail", "scfq_fa_parse_window", "scfq_fa_gc_interval", "scfq_format_fa_gc_value",
     "scfq_debug_fa_stages",
@@ -304,6 +306,28 @@ class DemuxStats(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in DEMUX_STATS_FIELDS]
 
 
+SCFQ_EFULL = -10
+SCFQ_KCOUNT_MIN_K, SCFQ_KCOUNT_MAX_K, SCFQ_KCOUNT_CANONICAL = 13, 32, 0x1
+KCOUNT_SUMMARY_FIELDS = ("struct_size", "abi_version", "reads", "lines", "input_bytes", "k", "flags", "windows", "kmers", "skipped",
+                         "short_lines", "distinct", "unique", "max_count", "slots", "passes")
+
+
+class KcountOpts(ctypes.Structure):
+    """scfq_kcount_opts (24 bytes)"""
+    _fields_ = [("struct_size", ctypes.c_uint64), ("k", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("table_bits", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+class KcountSummary(ctypes.Structure):
+    """scfq_kcount_summary (sixteen uint64)"""
+    _fields_ = [(n, ctypes.c_uint64) for n in KCOUNT_SUMMARY_FIELDS]
+
+
+class KmerCount(ctypes.Structure):
+    """scfq_kmer_count"""
+    _fields_ = [("key", ctypes.c_uint64), ("count", ctypes.c_uint64)]
+
+
 FA_SUMMARY_FIELDS = ("struct_size", "abi_version", "input_bytes", "tiles", "contigs", "bases", "gc_bases", "acgt_bases", "orphan_bases")
 
 
@@ -498,6 +522,16 @@ def lib():
         L.scfq_format_demux_row_tsv.argtypes = [ctypes.POINTER(DemuxStats), vp, ctypes.c_uint32, ctypes.POINTER(DemuxRow), ctypes.c_char_p, ctypes.c_uint64]
         L.scfq_demux_error_detail.restype = ctypes.c_char_p
         L.scfq_debug_demux_stages.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]
+        L.scfq_kcount_buffers.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_int, vp, pvp, vp]
+        L.scfq_kcount_files.argtypes = [ctypes.c_char_p, ctypes.c_char_p, vp, vp, pvp, vp]
+        L.scfq_kcount_hist.argtypes = [vp, vp, ctypes.c_uint64]
+        L.scfq_kcount_dump.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+        L.scfq_kcount_query.argtypes = [vp, vp, ctypes.c_uint64, vp]
+        L.scfq_kcount_free.argtypes = [vp]
+        L.scfq_kcount_free.restype = None
+        L.scfq_format_kcount_tsv.argtypes = [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_uint64]
+        L.scfq_kcount_error_detail.restype = ctypes.c_char_p
+        L.scfq_debug_kcount_stages.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]
         L.scfq_fa_index_buffer.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, pvp, ctypes.POINTER(FaSummary)]
         L.scfq_fa_index_file.argtypes = [ctypes.c_char_p, ctypes.c_void_p, pvp, ctypes.POINTER(FaSummary)]
         L.scfq_fa_contig_at.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(FaContig)]
@@ -1451,6 +1485,130 @@ def demux_stages():
     times, zeros unless SCFQ_DEMUX_TIMING=1 is in the environment"""
     ms = (ctypes.c_double * 4)()
     lib().scfq_debug_demux_stages(ms, 4)
+    return list(ms)
+
+
+def _kcount_error(rc, what):
+    return ScfqError(rc, what, lib().scfq_kcount_error_detail().decode() or lib().scfq_last_error_detail().decode())
+
+
+class KcountTable:
+    """scfq_kcount: the table of one fq-kcount call, on the device.  close() (or the end of a `with`) frees it."""
+
+    def __init__(self, handle, k, flags):
+        self._h, self.k, self.flags = handle, k, flags
+
+    @property
+    def handle(self):
+        return self._h
+
+    def hist(self, bins):
+        """numpy uint64 array of `bins` entries: [c] keys with count c, the last one keys with count >= bins - 1"""
+        import numpy as np
+        out = np.zeros(max(int(bins), 1), dtype=np.uint64)
+        rc = lib().scfq_kcount_hist(self._h, out.ctypes.data, bins)
+        if rc != 0:
+            raise _kcount_error(rc, "scfq_kcount_hist")
+        return out
+
+    def dump_into(self, out, cap, min_count=1, max_count=0):
+        """the raw call: out is a numpy uint64 array of shape (rows, 2) or None; returns total"""
+        total = ctypes.c_uint64(0)
+        rc = lib().scfq_kcount_dump(self._h, min_count, max_count, out.ctypes.data if out is not None else None, cap, ctypes.byref(total))
+        if rc != 0:
+            raise _kcount_error(rc, "scfq_kcount_dump")
+        return int(total.value)
+
+    def dump(self, min_count=1, max_count=0):
+        """numpy uint64 array of shape (total, 2): (key, count) in ascending key order"""
+        import numpy as np
+        total = self.dump_into(None, 0, min_count, max_count)
+        out = np.zeros((total, 2), dtype=np.uint64)
+        if total:
+            assert self.dump_into(out, total, min_count, max_count) == total
+        return out
+
+    def query(self, keys):
+        """numpy uint64 array: the count of every key (plain indices), 0 when absent"""
+        import numpy as np
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        out = np.zeros(keys.size, dtype=np.uint64)
+        rc = lib().scfq_kcount_query(self._h, keys.ctypes.data if keys.size else None, keys.size, out.ctypes.data if keys.size else None)
+        if rc != 0:
+            raise _kcount_error(rc, "scfq_kcount_query")
+        return out
+
+    def close(self):
+        if self._h:
+            lib().scfq_kcount_free(self._h)
+        self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def kcount_opts(k=21, flags=0, table_bits=0, reserved=0):
+    o = KcountOpts()
+    o.struct_size = ctypes.sizeof(KcountOpts)
+    o.k, o.flags, o.table_bits, o.reserved = k, flags, table_bits, reserved
+    return o
+
+
+def _new_kcount_summary():
+    s = KcountSummary()
+    s.struct_size = ctypes.sizeof(KcountSummary)
+    return s
+
+
+def _kcount_call(fn, what, head, k, flags, table_bits, table):
+    """Returns (KcountSummary, KcountTable), the table None with table=False"""
+    s = _new_kcount_summary()
+    o = kcount_opts(k, flags, table_bits)
+    h = ctypes.c_void_p()
+    rc = fn(*head, ctypes.byref(o), ctypes.byref(h) if table else None, ctypes.byref(s))
+    if rc != 0:
+        e = _kcount_error(rc, what)
+        e.handle = h.value
+        raise e
+    return s, (KcountTable(h, k, flags) if table else None)
+
+
+def kcount_device(ptr1, n1, ptr2=None, n2=0, k=21, flags=0, table_bits=0, table=True):
+    """fq-kcount of one or two device-resident FASTQs (counted into one table)"""
+    return _kcount_call(lib().scfq_kcount_buffers, "scfq_kcount_buffers",
+                        [ctypes.c_void_p(ptr1), n1, ctypes.c_void_p(ptr2) if ptr2 is not None else None, n2, 1], k, flags, table_bits, table)
+
+
+def kcount_host(data1, data2=None, k=21, flags=0, table_bits=0, table=True):
+    """fq-kcount of one or two host buffers (bytes / numpy uint8)"""
+    a1, n1, keep1 = _host_ptr(data1)
+    a2, n2, keep2 = _host_ptr(data2) if data2 is not None else (None, 0, None)
+    return _kcount_call(lib().scfq_kcount_buffers, "scfq_kcount_buffers", [a1, n1, a2, n2, 0], k, flags, table_bits, table)
+
+
+def kcount_files(path1, path2=None, k=21, flags=0, table_bits=0, table=True):
+    return _kcount_call(lib().scfq_kcount_files, "scfq_kcount_files",
+                        [os.fsencode(path1), os.fsencode(path2) if path2 is not None else None, None], k, flags, table_bits, table)
+
+
+def format_kcount_tsv(k, key, count):
+    buf = ctypes.create_string_buffer(96)
+    n = lib().scfq_format_kcount_tsv(k, key, count, buf, 96)
+    if n < 0:
+        raise ScfqError(n, "scfq_format_kcount_tsv")
+    return buf.value.decode()
+
+
+def kcount_stages():
+    """(line indexes, H1 of the last pass, H2, H3 of the last hist) milliseconds of this thread's last kcount calls; the last three
+    are HIP-event times, zeros unless SCFQ_KCOUNT_TIMING=1 is in the environment"""
+    ms = (ctypes.c_double * 4)()
+    lib().scfq_debug_kcount_stages(ms, 4)
     return list(ms)
 
 
