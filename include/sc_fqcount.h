@@ -1090,6 +1090,111 @@ void scfq_kcount_free(scfq_kcount* t);           /* NULL is fine */
 int scfq_format_kcount_tsv(uint32_t k, uint64_t key, uint64_t count, char* buf, uint64_t cap);
 const char* scfq_kcount_error_detail(void);      /* static, thread-local */
 
+/* ---- `sc fq-normalize` (addition; not in the reference): k-mer depth normalization of reads against an fq-kcount table ----
+ * For every read, how often its k-mers occur in a table of scfq_kcount; reads of over-covered regions are thinned to a target
+ * depth, reads whose k-mers are almost all rare are dropped (BBNorm, khmer's normalize-by-median, in one pass over resident
+ * input). Every value is an integer and exact.
+ *   Taken over. Lines, records, texts, read forms and pairing are fq-trim's / fq-screen's: one FASTQ (a unit is a read); two
+ *            (unit p is record p of each, pairs = min(reads1, reads2), the rest `unpaired`, counted nowhere else); one
+ *            interleaved FASTQ with SCFQ_NORM_INTERLEAVED (records 2p and 2p + 1). Windows, k-mers (every byte EXACTLY
+ *            A C G T), skipped, the 64-bit key and the canonical mode are fq-kcount's. k and plain / canonical are the
+ *            table's own: the handle carries them.
+ *   Count.   c(w) is the table's count of the window's key, 0 when the key is absent; the key of 32 x 'T' in plain mode has
+ *            the counter of its own that fq-kcount keeps for it. c(w) is saturated at SCFQ_NORM_MAX_DEPTH = 2^32 - 2 (2^32 - 1
+ *            is the kernels' marker for "no k-mer here"). The lookup is scfq_kcount_query's: 16-byte loads, linear probing, at
+ *            most the table's probe bound of slots, ending at the key or at an empty slot; every key that was inserted lies
+ *            within that bound of its home slot, so the bound loses nothing.
+ *   Per read (scfq_norm_rec, 16 bytes; paired input: mate m of pair p is entry 2p + m). kmers: the read's number of k-mers;
+ *            depth: the LOWER MEDIAN of their counts, sorted[(kmers - 1) / 2], 0 when kmers = 0; min_count: the smallest
+ *            count, 0 when kmers = 0; weak: the k-mers with c < weak_below (0: none are counted).
+ *   Per unit, u its 0-based number in input order. D = the smaller depth among the mates with kmers > 0 ("use the lower
+ *            depth"). A unit without such a mate is `no_kmers`: dropped, or kept with SCFQ_NORM_KEEP_NO_KMERS. Otherwise it is
+ *            dropped as `low` iff D < min_depth. Otherwise, with target > 0 and D > target, it is dropped as `high` iff
+ *            ((r * D) >> 32) >= target, r = mix64(seed ^ (u * 0x9E3779B97F4A7C15 mod 2^64)) >> 32 and mix64 MurmurHash3's
+ *            64-bit finalizer (r and D are below 2^32: the product fits 64 bits). Otherwise it is kept. target = 0 switches
+ *            the thinning off. The decision depends on u, the seed and the counts only — not on launch geometry, on
+ *            SCFQ_NORM_LDS_WINDOWS or on host vs device input.
+ *   Outputs. out1 / out2 receive the kept units' records in input order, echoed as fq-screen echoes them, pairs in step;
+ *            interleaved input sends both mates to out1. The sizing call, a too-small output (SCFQ_EARG naming it, statistics
+ *            complete, NO byte written to ANY output) and a too-small rec_cap (SCFQ_EARG with text before any write) are
+ *            scfq_screen_buffers'. hist_host: NULL (bins = 0), or 2 * bins words of HOST memory, 2 <= bins <= 2^20:
+ *            hist[2d] = units with D = d, hist[2d + 1] = those of them that are kept; the last bin gathers D >= bins - 1;
+ *            no_kmers units are in neither column.
+ *   Two-pass form. table = NULL: the library counts the SAME inputs first (opts->k, opts->table_flags, opts->table_bits; growth
+ *            and SCFQ_EFULL are fq-kcount's), normalizes against that table and frees it; one staging and one line index per
+ *            input serve both passes. With a table given opts->k is 0 or the table's k and table_flags / table_bits are not
+ *            looked at.
+ *   Limits.  One device, everything resident, fewer than 2^31 records per input, L < 2^32. The two-pass form needs fq-kcount's
+ *            table next to the inputs: 32 bytes per input byte at automatic sizing (2 slots of 16 bytes per byte).
+ *   Device pipeline. K5 line index per input; N1 — a wave per read, four per block, persistent blocks: the read through LDS
+ *            as 2-bit codes and an invalid-bit plane in chunks of 512 window starts, lane l the windows l, l + 64, ..., each
+ *            valid one probes the table, its saturated count (or the marker) goes to the wave's array of 2048 words in LDS,
+ *            minimum, weak, kmers and the maximum are wave reductions, the median a radix select (a ballot and a population
+ *            count per 64 entries and bit, from the maximum's top bit down); a read with more windows than the array keeps its
+ *            counts in device memory (4 bytes per window of such reads, sized by a pass over the line index before N1) and
+ *            selects from there; SCFQ_NORM_LDS_WINDOWS = 64 .. 2048 in the environment lowers the threshold and changes no
+ *            result — N2, a thread per unit: the rule, output lengths per group of 32, statistics, histogram columns — one
+ *            exclusive scan per output — N3, a wave per group echoes the kept records. Every loop is bounded: probes by the
+ *            probe bound, select rounds by 32, chunk loops by the line's length. There is no CPU fallback. */
+#define SCFQ_NORM_MAX_DEPTH      0xFFFFFFFEu
+#define SCFQ_NORM_INTERLEAVED    0x1u
+#define SCFQ_NORM_KEEP_NO_KMERS  0x2u
+#define SCFQ_NORM_MAX_BINS       (1ull << 20)
+typedef struct scfq_norm_opts {        /* 48 bytes */
+  uint64_t struct_size;   /* sizeof(scfq_norm_opts) */
+  uint32_t flags;         /* SCFQ_NORM_INTERLEAVED | SCFQ_NORM_KEEP_NO_KMERS */
+  uint32_t k;             /* table = NULL: 13 .. 32; otherwise 0 or the table's k */
+  uint32_t table_flags;   /* table = NULL: SCFQ_KCOUNT_CANONICAL or 0 */
+  uint32_t table_bits;    /* table = NULL: scfq_kcount_opts.table_bits */
+  uint32_t target;        /* 0: no thinning */
+  uint32_t min_depth;
+  uint32_t weak_below;    /* 0: count none */
+  uint32_t reserved;      /* 0 */
+  uint64_t seed;
+} scfq_norm_opts;
+typedef struct scfq_norm_rec { uint32_t kmers, depth, min_count, weak; } scfq_norm_rec;
+typedef struct scfq_norm_stats {       /* 37 x 8 bytes */
+  uint64_t struct_size;   /* caller sets to sizeof(scfq_norm_stats) before the call */
+  uint64_t abi_version;   /* library writes SCFQ_ABI_VERSION */
+  uint64_t reads1, reads2;             /* as scfq_screen_stats, down to `unpaired` */
+  uint64_t lines1, lines2;
+  uint64_t input_bytes1, input_bytes2;
+  uint64_t pairs, unpaired;
+  uint64_t units_in, units_out;        /* units_in = units_out + dropped_no_kmers + dropped_low + dropped_high */
+  uint64_t reads_in, reads_out;        /* reads_in: reads1, or 2 * pairs */
+  uint64_t dropped_no_kmers, dropped_low, dropped_high;   /* units */
+  uint64_t short_reads;                /* L < k */
+  uint64_t bases_in, bases_out;        /* sums of L */
+  uint64_t windows, kmers, skipped;    /* windows = kmers + skipped */
+  uint64_t weak_kmers;                 /* c < weak_below */
+  uint64_t absent_kmers;               /* c = 0: only a table made from other data has any */
+  uint64_t out1_bytes, out2_bytes;     /* sizes of the outputs, written or not */
+  uint64_t flags, k, table_flags, target, min_depth, weak_below, seed;   /* the parameters as used */
+  uint64_t distinct, slots, passes;    /* the table's */
+} scfq_norm_stats;
+
+/* r1 / r2, the outputs and the device-pointer rules are those of scfq_screen_buffers. opts = NULL: the defaults (no flags,
+ * target 0, min_depth 0, weak_below 2, seed 0), which need a table. recs_device: NULL, or DEVICE memory for rec_cap entries.
+ * SCFQ_EARG with text in scfq_norm_error_detail(), decided before any HIP call: unknown flag bits, a non-zero reserved, a wrong
+ * struct_size (opts' or stats'), bins outside 2 .. 2^20 with a histogram (or not 0 without one), out2 without a second input
+ * or with interleaved input, a second input without a first or with interleaved input, a k that is not the table's, and with
+ * table = NULL whatever scfq_kcount_buffers refuses in k, table_flags and table_bits. */
+int scfq_norm_buffers(const scfq_kcount* table, const void* r1, uint64_t n1, const void* r2, uint64_t n2, int is_device,
+                      const scfq_norm_opts* opts, scfq_norm_rec* recs_device, uint64_t rec_cap, void* out1, uint64_t cap1,
+                      void* out2, uint64_t cap2, int out_is_device, uint64_t* hist_host, uint64_t bins, scfq_norm_stats* stats);
+/* As scfq_screen_files: staged inputs, descriptors below 0 are not produced, out1 then out2, SCFQ_EPIPE / SCFQ_EIO.
+ * recs_host: NULL, or HOST memory for rec_cap entries of the per-read table. */
+int scfq_norm_files(const scfq_kcount* table, const char* path1, const char* path2, const scfq_opts* opts,
+                    const scfq_norm_opts* nopts, int out1_fd, int out2_fd, scfq_norm_rec* recs_host, uint64_t rec_cap,
+                    uint64_t* hist_host, uint64_t bins, scfq_norm_stats* stats);
+/* The one-row report without trailing newline; header != 0: the names of its columns instead. The columns: units_in units_out
+ * reads_in reads_out dropped_no_kmers dropped_low dropped_high bases_in bases_out kmers skipped weak_kmers absent_kmers k target
+ * min_depth. Returns the number of bytes needed (excluding NUL); writes at most cap bytes incl. NUL. */
+int scfq_format_norm_row_tsv(const scfq_norm_stats* s, int header, char* buf, uint64_t cap);
+/* "<depth>\t<units_in>\t<units_out>" of one bin, without trailing newline; the same return rule. */
+int scfq_format_norm_hist_tsv(uint64_t depth, uint64_t units_in, uint64_t units_out, char* buf, uint64_t cap);
+const char* scfq_norm_error_detail(void);        /* static, thread-local */
+
 /* ---- `sc fa-gc` (FASTA group): src/fa_gc.nim, docs/fa-gc.md, sc.nim:84-96 --------------------------------------------
  * GC content of the windows [pos - w, pos + w] around 1-based positions of a FASTA. The contract:
  *   Lines.   A header line is a line whose first byte is '>' (a line that starts at byte 0 of the input included); every

@@ -914,6 +914,168 @@ static int cmd_fq_kmers(const std::vector<std::string>& params) {
   return 0;
 }
 
+// command "fq-normalize" (addition, not in the reference): IN.fq (the kept reads to stdout, or to --out=PATH), R1.fq R2.fq with
+// --out1=PATH --out2=PATH (or neither: the report only), or --interleaved IN.fq; --k=N, --plain, --target=N, --min-depth=N, --weak-below=N,
+// --seed=N, --keep-no-kmers, --table-bits=N, --stats, --hist[=BINS], --per-read=PATH, -t/--header, -b/--basename, -a/--absolute.  The
+// report goes to stdout, or to stderr while stdout carries the reads.
+static const char* kNormHistHeader = "depth\tunits_in\tunits_out";
+static int cmd_fq_normalize(const std::vector<std::string>& params) {
+  static const char* const help =
+      "Normalize reads by the depth of their k-mers: thin over-covered regions to a target depth, drop reads of rare k-mers; pairs stay in step\n\n"
+      "Usage:\n  fq-normalize [options] IN.fq > out.fq\n  fq-normalize [options] --out1=PATH --out2=PATH R1.fq R2.fq\n"
+      "  fq-normalize [options] --interleaved [--out=PATH] IN.fq\n\n"
+      "Arguments:\n  IN.fq            One FASTQ: single-end reads, or pairs with --interleaved; the kept reads go to stdout or to --out=PATH\n"
+      "  R1.fq R2.fq      Two FASTQs: record i of each is pair i; without --out1 and --out2 only the report is produced\n\nOptions:\n"
+      "      --k=N                  Length of the k-mers, 13 .. 32 (default: 21); the inputs are counted first, then normalized\n"
+      "      --plain                Count a k-mer and its reverse complement apart (default: as the smaller of the two)\n"
+      "      --target=N             Thin units whose depth D is above N to about N (default: 0 = off)\n"
+      "      --min-depth=N          Drop units with D below N (default: 0)\n"
+      "      --weak-below=N         Count k-mers that occur fewer than N times as weak (default: 2, 0 = none)\n"
+      "      --seed=N               Seed of the thinning (default: 0)\n"
+      "      --keep-no-kmers        Keep the units that have no k-mer at all\n"
+      "      --table-bits=N         A table of 2^N slots, 10 .. 32, that does not grow (default: sized by the input)\n"
+      "      --interleaved          The one argument is an interleaved FASTQ: records 2i and 2i+1 are pair i\n"
+      "      --out=PATH             With one FASTQ: the kept reads, or pairs, go to PATH and the report to stdout\n"
+      "      --out1=PATH            With R1.fq R2.fq: mate 1 of the kept pairs goes to PATH\n"
+      "      --out2=PATH            With R1.fq R2.fq: mate 2 of the kept pairs goes to PATH\n"
+      "      --stats                While stdout carries the reads: the report row to stderr\n"
+      "      --hist[=BINS]          Instead of the report row the table \"depth units_in units_out\", the last bin gathering\n"
+      "                             D >= BINS - 1 (default: 1002, 2 .. 1048576)\n"
+      "      --per-read=PATH        One row per read to PATH: read_index kmers depth min_count weak\n"
+      "  -t, --header               Output the header\n  -b, --basename             Add a column with the basename of the first FASTQ\n"
+      "  -a, --absolute             Add a column with the absolute path of the first FASTQ\n"
+      "  -h, --help                 Show this help\n";
+  Columns cols;
+  scfq_norm_opts no = fresh<scfq_norm_opts>();
+  no.k = 21;
+  no.weak_below = 2;
+  uint32_t plain = 0;
+  bool stats = false, hist = false;
+  uint64_t bins = 1002;
+  std::vector<std::string> files;
+  std::string out, out1, out2, per_read;
+  const std::vector<Opt> table = cols.options({
+      opt_number("k", 6, SCFQ_KCOUNT_MIN_K, SCFQ_KCOUNT_MAX_K, &no.k),
+      opt_bits("plain", &plain, 1u),
+      opt_number("target", 10, 0, SCFQ_NORM_MAX_DEPTH, &no.target),
+      opt_number("min-depth", 10, 0, SCFQ_NORM_MAX_DEPTH, &no.min_depth),
+      opt_number("weak-below", 10, 0, SCFQ_NORM_MAX_DEPTH, &no.weak_below),
+      opt_custom("seed", [&](std::string& v) {             // all of 64 bits: twenty digits may be too many
+        if (v.empty() || v.size() > 20 || v.find_first_not_of("0123456789") != std::string::npos) return Reject::bad_value;
+        uint64_t n = 0;
+        for (const char c : v) {
+          if (n > (~0ull - (uint64_t)(c - '0')) / 10) return Reject::bad_value;
+          n = 10 * n + (uint64_t)(c - '0');
+        }
+        no.seed = n;
+        return Reject::none;
+      }),
+      opt_bits("keep-no-kmers", &no.flags, SCFQ_NORM_KEEP_NO_KMERS),
+      opt_number("table-bits", 6, 10, 32, &no.table_bits),
+      opt_bits("interleaved", &no.flags, SCFQ_NORM_INTERLEAVED),
+      opt_text("out", &out),
+      opt_text("out1", &out1),
+      opt_text("out2", &out2),
+      opt_flag("stats", 0, &stats),
+      opt_flag("hist", 0, &hist),
+      opt_custom("hist", [&](std::string& v) {
+        hist = true;
+        return bounded_number(v, 7, 2, SCFQ_NORM_MAX_BINS, &bins) ? Reject::none : Reject::bad_value;
+      }),
+      opt_text("per-read", &per_read),
+  });
+  if (!parse_options(params, help, table, &files)) return 0;
+  no.table_flags = plain ? 0u : (uint32_t)SCFQ_KCOUNT_CANONICAL;
+  const bool interleaved = no.flags & SCFQ_NORM_INTERLEAVED;
+  if (files.empty()) quit_no_fastq();
+  if (files.size() > 2 || (interleaved && files.size() != 1)) usage_error(help, "fq-normalize takes one FASTQ, R1.fq and R2.fq, or one FASTQ with --interleaved");
+  const bool two = files.size() == 2;
+  if (two && !out.empty()) usage_error(help, "R1.fq R2.fq write to --out1=PATH and --out2=PATH");
+  if (two && out1.empty() != out2.empty()) usage_error(help, "--out1=PATH and --out2=PATH go together");
+  if (!two && (!out1.empty() || !out2.empty())) usage_error(help, "--out1=PATH and --out2=PATH go with R1.fq R2.fq; one input is written to stdout or to --out=PATH");
+  for (const std::string& f : files) require_suffix_room(f);
+  // the inputs are looked at before an output file is made
+  for (const std::string& f : files)
+    if (access(f.c_str(), R_OK) != 0) quit_unable_to_open(f);
+  const bool to_stdout = !two && out.empty();          // stdout carries the reads: the report goes to stderr
+  const std::string p1 = two ? out1 : out;
+  int fd1 = to_stdout ? 1 : -1, fd2 = -1;
+  // a call that fails leaves no output file behind: what this process created goes again (fq-trim's rule)
+  auto discard = [&]() {
+    auto drop = [](int fd, const std::string& p) {
+      struct stat st;
+      const bool regular = fstat(fd, &st) == 0 && S_ISREG(st.st_mode);
+      close(fd);
+      if (regular) unlink(p.c_str());
+    };
+    if (!to_stdout && fd1 >= 0) drop(fd1, p1);
+    if (fd2 >= 0) drop(fd2, out2);
+    fd1 = fd2 = -1;
+  };
+  auto create = [&](const std::string& p) -> int {
+    const int fd = open(p.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
+    if (fd < 0) { discard(); quit_error("Unable to create file: " + p, 1); }
+    return fd;
+  };
+  if (!p1.empty()) fd1 = create(p1);
+  if (two && !out2.empty()) fd2 = create(out2);
+  scfq_norm_stats st = fresh<scfq_norm_stats>();
+  const char* path2 = two ? files[1].c_str() : nullptr;
+  std::vector<scfq_norm_rec> recs;
+  std::vector<uint64_t> bin_words(hist ? 2 * bins : 0);
+  scfq_kcount* kc = nullptr;
+  int rc = SCFQ_OK;
+  bool counting = false;
+  if (!per_read.empty()) {
+    // the per-read table's length is the number of reads: the inputs are counted into a table that stays, and a call without outputs
+    // tells the length
+    scfq_kcount_opts ko = fresh<scfq_kcount_opts>();
+    ko.k = no.k; ko.flags = no.table_flags; ko.table_bits = no.table_bits;
+    counting = true;
+    rc = scfq_kcount_files(files[0].c_str(), path2, nullptr, &ko, &kc, nullptr);
+    if (rc == SCFQ_OK) {
+      counting = false;
+      rc = scfq_norm_files(kc, files[0].c_str(), path2, nullptr, &no, -1, -1, nullptr, 0, nullptr, 0, &st);
+    }
+    if (rc == SCFQ_OK) recs.assign((size_t)st.reads_in, scfq_norm_rec());
+    st = fresh<scfq_norm_stats>();
+  }
+  std::fflush(stdout);
+  if (rc == SCFQ_OK)
+    rc = scfq_norm_files(kc, files[0].c_str(), path2, nullptr, &no, fd1, fd2, recs.empty() ? nullptr : recs.data(), recs.size(), hist ? bin_words.data() : nullptr,
+                         hist ? bins : 0, &st);
+  const std::string detail = counting ? scfq_kcount_error_detail() : scfq_norm_error_detail();
+  scfq_kcount_free(kc);
+  if (rc != SCFQ_OK && rc != SCFQ_EPIPE) discard();
+  else { if (!to_stdout && fd1 >= 0) close(fd1); if (fd2 >= 0) close(fd2); }
+  if (rc == SCFQ_EOPEN) quit_unable_to_open(first_unopenable(files[0], two ? &files[1] : nullptr));
+  if (rc == SCFQ_EPIPE) return 0;              // a reader of stdout that went away: quiet, as `sc fq-dedup | head`
+  if (rc != SCFQ_OK) quit_error(library_error(rc, detail.c_str()), 1);
+  if (!per_read.empty()) {
+    FILE* f = std::fopen(per_read.c_str(), "w");
+    if (!f) quit_error("Unable to create file: " + per_read, 1);
+    for (size_t i = 0; i < recs.size(); ++i) std::fprintf(f, "%zu\t%u\t%u\t%u\t%u\n", i, recs[i].kmers, recs[i].depth, recs[i].min_count, recs[i].weak);
+    if (std::fclose(f) != 0) quit_error("Unable to write file: " + per_read, 1);
+  }
+  FILE* report = to_stdout ? stderr : stdout;
+  if (to_stdout && !stats && !hist) return 0;
+  char row[1024];
+  if (cols.header) {
+    scfq_format_norm_row_tsv(nullptr, 1, row, sizeof row);
+    std::fprintf(report, "%s\n", output_header(hist ? kNormHistHeader : row, cols.basename, cols.absolute).c_str());
+  }
+  if (hist) {
+    for (uint64_t d = 0; d < bins; ++d) {
+      scfq_format_norm_hist_tsv(d, bin_words[2 * d], bin_words[2 * d + 1], row, sizeof row);
+      std::fprintf(report, "%s\n", cols.row(row, files[0]).c_str());
+    }
+  } else {
+    scfq_format_norm_row_tsv(&st, 0, row, sizeof row);
+    std::fprintf(report, "%s\n", cols.row(row, files[0]).c_str());
+  }
+  return 0;
+}
+
 // command "fq-kcount" (addition, not in the reference): -t/--header, -b/--basename, -a/--absolute as fq-count, --k=N, --canonical,
 // --table-bits=N, --high=N, --totals, --dump [--min-count=C] [--max-count=C], --top=N, IN.fq [IN2.fq]
 static const char* kKcountHistHeader = "count\tkmers";
@@ -1466,7 +1628,7 @@ int main(int argc, char** argv) {
       {"fq-readstats", cmd_fq_readstats}, {"fq-cycles", cmd_fq_cycles},   {"fq-kmers", cmd_fq_kmers},
       {"fq-adapters", cmd_fq_adapters}, {"fq-insert-size", cmd_fq_insert_size}, {"fq-merge", cmd_fq_merge},
       {"fq-trim", cmd_fq_trim},         {"fq-screen", cmd_fq_screen},     {"fq-demux", cmd_fq_demux},
-      {"fq-kcount", cmd_fq_kcount},     {"fa-gc", cmd_fa_gc}};
+      {"fq-kcount", cmd_fq_kcount},     {"fq-normalize", cmd_fq_normalize}, {"fa-gc", cmd_fa_gc}};
   for (const auto& c : commands)
     if (params[0] == c.name) return c.run(params);
   help_top(stdout);

@@ -34,6 +34,7 @@
 #include <hip/hip_runtime.h>
 
 #include "scfq_kcount_host.hpp"
+#include "scfq_kcount_internal.hpp"
 #include "scfq_record_device.hpp"
 #include "scfq_scratch.hpp"
 
@@ -52,6 +53,7 @@ struct scfq_kcount {
   mutable std::mutex mu;           // one reader (hist, dump, query) at a time: they share the scratch
   uint64_t slots = 0;
   uint64_t ones = 0;               // count of the key that equals kEmpty
+  uint64_t distinct = 0, passes = 0;      // of the summary, for the readers of scfq_kcount_internal.hpp
   uint32_t k = 0, flags = 0, max_probe = 0;
 };
 
@@ -397,7 +399,8 @@ __global__ __launch_bounds__(256) void kc_query(const KcSlot* table, uint64_t sl
 
 unsigned grid_for(uint64_t items) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((items + 255) / 256, 2048)); }
 
-struct Input { const uint8_t* d = nullptr; uint64_t n = 0, lines = 0; bool has_cr = true; DevBuf line_off; };
+// off: the line index; the caller's (lines and has_cr with it), or nullptr: it is built here, into line_off
+struct Input { const uint8_t* d = nullptr; uint64_t n = 0, lines = 0; bool has_cr = true; const uint64_t* off = nullptr; DevBuf line_off; };
 
 int full_error(uint64_t slots, const char* why) {
   std::snprintf(g_cerr, sizeof g_cerr, "a table of %llu slots %s", (unsigned long long)slots, why);
@@ -417,7 +420,10 @@ int kcount_device(Input* in, int n_in, const scfq_kcount_opts& o, scfq_kcount** 
   {
     const auto t_a = std::chrono::steady_clock::now();
     for (int i = 0; i < n_in; ++i) {
-      if ((rc = scfq_scratch::build_line_index(in[i].d, in[i].n, stream, g_cerr, in[i].line_off, &in[i].lines, &in[i].has_cr))) return rc;
+      if (!in[i].off) {
+        if ((rc = scfq_scratch::build_line_index(in[i].d, in[i].n, stream, g_cerr, in[i].line_off, &in[i].lines, &in[i].has_cr))) return rc;
+        in[i].off = in[i].line_off.as<uint64_t>();
+      }
       const uint64_t reads = (in[i].lines + 3) / 4;
       if (reads >= (1ull << 31)) { std::snprintf(g_cerr, sizeof g_cerr, "more than 2^31 records in one input"); return SCFQ_EARG; }
       s.reads += reads;
@@ -465,10 +471,10 @@ int kcount_device(Input* in, int n_in, const scfq_kcount_opts& o, scfq_kcount** 
       const uint64_t spb = (steps + kKcMaxBlocks - 1) / kKcMaxBlocks;
       const unsigned blocks = (unsigned)((steps + spb - 1) / spb);
       if (canonical)
-        hipLaunchKernelGGL(kc_count<true>, dim3(blocks), dim3(kKcThreads), 0, stream, in[i].d, in[i].n, in[i].line_off.as<uint64_t>(), in[i].lines,
+        hipLaunchKernelGGL(kc_count<true>, dim3(blocks), dim3(kKcThreads), 0, stream, in[i].d, in[i].n, in[i].off, in[i].lines,
                            shift, in[i].has_cr, o.k, merge, chunks, spb, static_cast<KcSlot*>(table.p), slots - 1, max_probe, d_failed, d_stats);
       else
-        hipLaunchKernelGGL(kc_count<false>, dim3(blocks), dim3(kKcThreads), 0, stream, in[i].d, in[i].n, in[i].line_off.as<uint64_t>(), in[i].lines,
+        hipLaunchKernelGGL(kc_count<false>, dim3(blocks), dim3(kKcThreads), 0, stream, in[i].d, in[i].n, in[i].off, in[i].lines,
                            shift, in[i].has_cr, o.k, merge, chunks, spb, static_cast<KcSlot*>(table.p), slots - 1, max_probe, d_failed, d_stats);
       SCFQ_SCRATCH_CHK(g_cerr, hipGetLastError());
     }
@@ -488,6 +494,8 @@ int kcount_device(Input* in, int n_in, const scfq_kcount_opts& o, scfq_kcount** 
         table.p = nullptr;
         t->slots = slots;
         t->ones = h[kStOnes];
+        t->distinct = h[kStDistinct];
+        t->passes = s.passes;
         t->k = o.k;
         t->flags = o.flags;
         t->max_probe = max_probe;
@@ -545,6 +553,33 @@ struct HandleCall {
 };
 
 }  // namespace
+
+namespace scfq_kcount_internal {
+
+bool view(const scfq_kcount* t, View* out) {
+  if (!t || !out) return false;
+  out->slots = t->slots_dev;
+  out->n_slots = t->slots;
+  out->ones = t->ones;
+  out->distinct = t->distinct;
+  out->passes = t->passes;
+  out->k = t->k;
+  out->flags = t->flags;
+  out->max_probe = t->max_probe;
+  return true;
+}
+
+int count_resident(const Resident* r, int n_in, const scfq_kcount_opts& o, scfq_kcount** out, scfq_kcount_summary* sum, hipStream_t stream) {
+  g_cerr[0] = '\0';
+  if (out) *out = nullptr;
+  Input in[2];
+  for (int i = 0; i < n_in && i < 2; ++i) {
+    in[i].d = r[i].d; in[i].n = r[i].n; in[i].off = r[i].line_off; in[i].lines = r[i].lines; in[i].has_cr = r[i].has_cr;
+  }
+  return kcount_device(in, n_in < 2 ? n_in : 2, o, out, sum, stream);
+}
+
+}  // namespace scfq_kcount_internal
 
 extern "C" {
 

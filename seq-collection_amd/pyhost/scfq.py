@@ -62,6 +62,8 @@ EXPORTS = [
     "scfq_format_demux_row_tsv", "scfq_demux_error_detail", "scfq_debug_demux_stages",
     "scfq_kcount_buffers", "scfq_kcount_files", "scfq_kcount_hist", "scfq_kcount_dump", "scfq_kcount_query", "scfq_kcount_free",
     "scfq_format_kcount_tsv", "scfq_kcount_error_detail", "scfq_debug_kcount_stages",
+    "scfq_norm_buffers", "scfq_norm_files", "scfq_format_norm_row_tsv", "scfq_format_norm_hist_tsv", "scfq_norm_error_detail",
+    "scfq_debug_norm_stages",
     "scfq_fa_index_buffer", "scfq_fa_index_file", "scfq_fa_contig_at", "scfq_fa_contig_find", "scfq_fa_count_intervals",
     "scfq_fa_index_free", "scfq_fa_error_detail", "scfq_fa_parse_window", "scfq_fa_gc_interval", "scfq_format_fa_gc_value",
     "scfq_debug_fa_stages",
@@ -328,6 +330,33 @@ class KmerCount(ctypes.Structure):
     _fields_ = [("key", ctypes.c_uint64), ("count", ctypes.c_uint64)]
 
 
+SCFQ_NORM_MAX_DEPTH = 0xFFFFFFFE
+SCFQ_NORM_INTERLEAVED, SCFQ_NORM_KEEP_NO_KMERS = 0x1, 0x2
+NORM_MAX_BINS = 1 << 20
+NORM_REC_FIELDS = ("kmers", "depth", "min_count", "weak")
+NORM_STATS_FIELDS = ("struct_size", "abi_version", "reads1", "reads2", "lines1", "lines2", "input_bytes1", "input_bytes2", "pairs", "unpaired",
+                     "units_in", "units_out", "reads_in", "reads_out", "dropped_no_kmers", "dropped_low", "dropped_high", "short_reads",
+                     "bases_in", "bases_out", "windows", "kmers", "skipped", "weak_kmers", "absent_kmers", "out1_bytes", "out2_bytes",
+                     "flags", "k", "table_flags", "target", "min_depth", "weak_below", "seed", "distinct", "slots", "passes")
+
+
+class NormOpts(ctypes.Structure):
+    """scfq_norm_opts (48 bytes)"""
+    _fields_ = [("struct_size", ctypes.c_uint64)] + \
+               [(n, ctypes.c_uint32) for n in ("flags", "k", "table_flags", "table_bits", "target", "min_depth", "weak_below", "reserved")] + \
+               [("seed", ctypes.c_uint64)]
+
+
+class NormRec(ctypes.Structure):
+    """scfq_norm_rec (16 bytes)"""
+    _fields_ = [(n, ctypes.c_uint32) for n in NORM_REC_FIELDS]
+
+
+class NormStats(ctypes.Structure):
+    """scfq_norm_stats (37 uint64)"""
+    _fields_ = [(n, ctypes.c_uint64) for n in NORM_STATS_FIELDS]
+
+
 FA_SUMMARY_FIELDS = ("struct_size", "abi_version", "input_bytes", "tiles", "contigs", "bases", "gc_bases", "acgt_bases", "orphan_bases")
 
 
@@ -532,6 +561,13 @@ def lib():
         L.scfq_format_kcount_tsv.argtypes = [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_uint64]
         L.scfq_kcount_error_detail.restype = ctypes.c_char_p
         L.scfq_debug_kcount_stages.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]
+        L.scfq_norm_buffers.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_int, vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp,
+                                        ctypes.c_uint64, ctypes.c_int, vp, ctypes.c_uint64, vp]
+        L.scfq_norm_files.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, vp, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp]
+        L.scfq_format_norm_row_tsv.argtypes = [vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_uint64]
+        L.scfq_format_norm_hist_tsv.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_uint64]
+        L.scfq_norm_error_detail.restype = ctypes.c_char_p
+        L.scfq_debug_norm_stages.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]
         L.scfq_fa_index_buffer.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, pvp, ctypes.POINTER(FaSummary)]
         L.scfq_fa_index_file.argtypes = [ctypes.c_char_p, ctypes.c_void_p, pvp, ctypes.POINTER(FaSummary)]
         L.scfq_fa_contig_at.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(FaContig)]
@@ -1609,6 +1645,90 @@ def kcount_stages():
     are HIP-event times, zeros unless SCFQ_KCOUNT_TIMING=1 is in the environment"""
     ms = (ctypes.c_double * 4)()
     lib().scfq_debug_kcount_stages(ms, 4)
+    return list(ms)
+
+
+def _norm_error(rc, what):
+    return ScfqError(rc, what, lib().scfq_norm_error_detail().decode() or lib().scfq_last_error_detail().decode())
+
+
+def norm_opts(interleaved=False, keep_no_kmers=False, k=0, canonical=False, table_bits=0, target=0, min_depth=0, weak_below=2, seed=0,
+              flags=None, table_flags=None, reserved=0):
+    """scfq_norm_opts.  k, canonical and table_bits matter without a table only (the two-pass form)"""
+    o = NormOpts()
+    o.struct_size = ctypes.sizeof(NormOpts)
+    o.flags = flags if flags is not None else (SCFQ_NORM_INTERLEAVED if interleaved else 0) | (SCFQ_NORM_KEEP_NO_KMERS if keep_no_kmers else 0)
+    o.table_flags = table_flags if table_flags is not None else (SCFQ_KCOUNT_CANONICAL if canonical else 0)
+    o.k, o.table_bits, o.target, o.min_depth, o.weak_below, o.reserved, o.seed = k, table_bits, target, min_depth, weak_below, reserved, seed
+    return o
+
+
+def _norm_call(fn, what, table, opts, head, tail, bins):
+    """Returns (NormStats, hist): hist a numpy uint64 array of shape (bins, 2) with the columns (units in, units kept), or None with
+    bins = 0.  An ScfqError carries the stats as `stats` (complete when an output was too small)."""
+    import numpy as np
+    s = NormStats()
+    s.struct_size = ctypes.sizeof(NormStats)
+    hist = np.zeros((bins, 2), dtype=np.uint64) if bins else None
+    handle = table.handle if isinstance(table, KcountTable) else table
+    rc = fn(handle, *head, ctypes.byref(opts) if opts is not None else None, *tail, hist.ctypes.data if bins else None, bins, ctypes.byref(s))
+    if rc != 0:
+        e = _norm_error(rc, what)
+        e.stats = s
+        raise e
+    return s, hist
+
+
+def norm_device(table, ptr1, n1, ptr2=None, n2=0, opts=None, out1=None, out2=None, recs=None, bins=0):
+    """fq-normalize of device-resident FASTQs against a KcountTable (None: the two-pass form; the pointer rules of trim_device).
+    out1 / out2: (device address, capacity) or None; recs: (device address, entries) of the per-read table or None."""
+    return _norm_call(lib().scfq_norm_buffers, "scfq_norm_buffers", table, opts,
+                      [ctypes.c_void_p(ptr1), n1, ctypes.c_void_p(ptr2) if ptr2 is not None else None, n2, 1],
+                      [ctypes.c_void_p(recs[0]) if recs else None, recs[1] if recs else 0] + _trim_outputs((out1, out2)) + [1], bins)
+
+
+def norm_host(table, data1, data2=None, opts=None, caps=None, bins=0):
+    """fq-normalize of host buffers; caps as trim_host's.  Returns (NormStats, hist, out1, out2), the outputs as bytes or None."""
+    a1, n1, keep1 = _host_ptr(data1)
+    a2, n2, keep2 = _host_ptr(data2) if data2 is not None else (None, 0, None)
+    head = [a1, n1, a2, n2, 0]
+    fn = lib().scfq_norm_buffers
+    if caps is None:
+        s, _ = _norm_call(fn, "scfq_norm_buffers", table, opts, head, [None, 0, None, 0, None, 0, 0], 0)
+        caps = (s.out1_bytes, s.out2_bytes if data2 is not None else None)
+    bufs = [None if c is None else ctypes.create_string_buffer(max(int(c), 1)) for c in caps]
+    outs = [None if b is None else (ctypes.addressof(b), int(c)) for b, c in zip(bufs, caps)]
+    s, hist = _norm_call(fn, "scfq_norm_buffers", table, opts, head, [None, 0] + _trim_outputs(outs) + [0], bins)
+    sizes = (s.out1_bytes, s.out2_bytes)
+    return (s, hist) + tuple(None if b is None else b.raw[:int(k)] for b, k in zip(bufs, sizes))
+
+
+def norm_file(table, path1, path2=None, opts=None, out1_fd=-1, out2_fd=-1, recs=None, bins=0):
+    """recs: None, or a ctypes array of NormRec that receives the per-read table.  Returns (NormStats, hist)"""
+    return _norm_call(lib().scfq_norm_files, "scfq_norm_files", table, opts,
+                      [os.fsencode(path1) if path1 is not None else None, os.fsencode(path2) if path2 is not None else None, None],
+                      [out1_fd, out2_fd, ctypes.cast(recs, ctypes.c_void_p) if recs is not None else None, len(recs) if recs is not None else 0], bins)
+
+
+def format_norm_row_tsv(s, header=False):
+    buf = ctypes.create_string_buffer(1024)
+    n = lib().scfq_format_norm_row_tsv(ctypes.byref(s) if s is not None else None, 1 if header else 0, buf, 1024)
+    if n < 0:
+        raise ScfqError(n, "scfq_format_norm_row_tsv")
+    return buf.value.decode()
+
+
+def format_norm_hist_tsv(depth, units_in, units_out):
+    buf = ctypes.create_string_buffer(96)
+    lib().scfq_format_norm_hist_tsv(depth, units_in, units_out, buf, 96)
+    return buf.value.decode()
+
+
+def norm_stages():
+    """(line indexes, N1, N2 with its scans, N3) milliseconds of this thread's last normalize call; the last three are HIP-event times,
+    zeros unless SCFQ_NORM_TIMING=1 is in the environment"""
+    ms = (ctypes.c_double * 4)()
+    lib().scfq_debug_norm_stages(ms, 4)
     return list(ms)
 
 
