@@ -9,13 +9,19 @@ beyond 2^32.
 The expectation is never computed on the whole input: it is the checker's result on the block and on the tail, composed.  Counters,
 histograms and tables add up (R * block + tail); per-record rows and outputs are the block's R times, then the tail's (`Tiled`);
 what a checker derives at its end (N50, the median insert, ...) is derived again from the composed rows by the checker's own code.
+A k-mer table is merged key by key; fq-demux's outputs are tiled destination by destination; under fq-normalize's sampled rule the
+class of a unit depends on its number in the whole input and is computed again for all of them (compose_normalize_sampled).
 tests/test_big_offset_cases_host.py proves every composition against the checker on block x 3 + tail."""
 import numpy as np
 
 from _adapters_check import adapters_of_np
 from _cycles_check import table_of_np
 from _insert_size_check import DEFAULTS as INSERT_DEFAULTS, _finish as insert_finish, insert_of_np, planted, paired_block, random_dna, revcomp
+from _demux_check import demux_of as demux_check_of
+from _kcount_check import Want as KcountWant, kcount_of_np
 from _kmers_check import kmers_of_np
+from _normalize_check import GOLDEN as NORM_GOLDEN, HIGH as NORM_HIGH, KEPT as NORM_KEPT, LOW as NORM_LOW, NO_KMERS as NORM_NO_KMERS, \
+    normalize_of as normalize_check_of
 from _merge_check import merge_of_np, with_random_qualities
 from _readstats_check import line_spans_np, per_read_np
 from _screen_check import PARAM_FIELDS as SCREEN_PARAMS, PER_REF, screen_of_np
@@ -28,6 +34,9 @@ LONG_ADAPTER = b"AGATCGGAAGAGCACACGTCTGAACTCCAGTCACGATCTCGTATGCCGTCTTCTGCTTG"  #
 TRIM_ALL = dict(poly_g=5, window_quality=20)                                  # every step on (test_gpu_trim.py's ALL)
 SCREEN_KW = dict(min_hits=3)
 FIELD = 8                                                                      # hex digits of the repetition number in a header
+DEMUX_SAMPLES = (("s0", "ACGTACGT", "TTGACCAG"), ("s1", "GGATCCTA", "CATGGTCA"), ("s2", "TCAGGACT", "AGCTTGTC"), ("s3", "CTTCAGAC", "GTCAAGGT"),
+                 ("s4", "TAGCTTGA", "CCATGACT"))          # dual barcodes of 8 + 8 letters, any two at least 4 letters apart in either
+DEMUX_KW = dict(mismatches=1)
 
 
 def layout(B, tail_len, R=None):
@@ -261,6 +270,186 @@ def compose_screen(block, tail, R):
     return compose(block, tail, R, same=SCREEN_PARAMS, tiled=("out1", "out2", "recs"))
 
 
+KCOUNT_SUMS = ("windows", "kmers", "skipped", "short_lines", "lines", "reads", "input_bytes")
+
+
+def kcount_of(a1, a2, k, canonical):
+    w = kcount_of_np([as_u8(a1)] + ([as_u8(a2)] if a2 is not None else []), k, canonical)
+    return dict({f: getattr(w, f) for f in KCOUNT_SUMS}, table=w.table)
+
+
+def compose_kcount(block, tail, R):
+    """the table is merged key by key (R * the block's count + the tail's), the sums add up.  (distinct, unique and max_count are read
+    off the merged table by _kcount_check.Want: see kcount_want)"""
+    table = {key: R * c for key, c in block["table"].items()}
+    for key, c in tail["table"].items():
+        table[key] = table.get(key, 0) + c
+    return dict({f: R * block[f] + tail[f] for f in KCOUNT_SUMS}, table=table)
+
+
+def kcount_want(w):
+    """a (composed) dict as the _kcount_check.Want that assert_summary, dump_of and hist_of take"""
+    return KcountWant(w["table"], *[w[f] for f in KCOUNT_SUMS])
+
+
+def _record_bytes(a):
+    """the byte length of every record of an input of whole records"""
+    a = as_u8(a)
+    off = index_of(a)["off"]
+    assert (off.size - 1) % 4 == 0 and (a.size == 0 or a[-1] == 10)
+    return np.diff(off[::4])
+
+
+def _unit_sums(per_read1, per_read2, units, two):
+    """per-unit sums of a per-read quantity, for out1 and out2: both mates of an interleaved unit go to out1"""
+    if two:
+        return per_read1[:units], per_read2[:units]
+    return per_read1[0:2 * units:2] + per_read1[1:2 * units:2], np.zeros(units, np.int64)
+
+
+DEMUX_SAME = ("flags", "mismatches", "n_samples", "dual")
+DEMUX_ROW_SUMS = ("units", "perfect", "mismatched", "bases_out", "bytes1", "bytes2")
+
+
+def demux_of(a1, a2=None, samples=DEMUX_SAMPLES, **kw):
+    w = demux_check_of(as_u8(a1).tobytes(), None if a2 is None else as_u8(a2).tobytes(), list(samples), **kw)
+    w["recs"] = np.array(w["recs"], np.int64).reshape(-1, 4)
+    return w
+
+
+def _dest_slice(w, which, d):
+    row = w["rows"][d]
+    return w["out" + which][row["off" + which]:row["off" + which] + row["bytes" + which]]
+
+
+def compose_demux(block, tail, R):
+    """counters and the rows' counts add up, off1 / off2 are the running sums of the composed bytes, the per-unit table is tiled.  An
+    output is ordered by destination: out1 / out2 come back as one Tiled per destination — the block's slice R times, then the tail's —
+    and are never written out here"""
+    assert block["unpaired"] == 0 and set(block) == set(tail)
+    out = {}
+    for k, b in block.items():
+        if k in DEMUX_SAME:
+            assert b == tail[k], (k, b, tail[k])
+            out[k] = b
+        elif k not in ("rows", "recs", "out1", "out2"):
+            out[k] = R * b + tail[k]
+    rows, off1, off2 = [], 0, 0
+    for rb, rt in zip(block["rows"], tail["rows"]):
+        row = {f: R * rb[f] + rt[f] for f in DEMUX_ROW_SUMS}
+        row["off1"], row["off2"] = off1, off2
+        off1, off2 = off1 + row["bytes1"], off2 + row["bytes2"]
+        rows.append(row)
+    assert (off1, off2) == (out["out1_bytes"], out["out2_bytes"])
+    out["rows"], out["recs"] = rows, Tiled(block["recs"], R, tail["recs"])
+    for which in "12":
+        out["out" + which] = [Tiled(_dest_slice(block, which, d), R, _dest_slice(tail, which, d)) for d in range(len(rows))]
+    return out
+
+
+def demux_R(block):
+    """the repetitions after which the block's last destination (undetermined) starts beyond LIMIT in every output it has"""
+    last = block["rows"][-1]
+    return -(-LIMIT // min(last["off" + w] for w in "12" if block["out%s_bytes" % w]))
+
+
+NORM_SAME = ("flags", "k", "table_flags", "target", "min_depth", "weak_below", "seed", "distinct")
+NORM_TILED = ("recs", "out1", "out2", "classes", "len1", "len2", "bases")
+NORM_RULE = ("units_out", "reads_out", "dropped_no_kmers", "dropped_low", "dropped_high", "bases_out", "out1_bytes", "out2_bytes")
+NORM_SAMPLED = dict(target=3, min_depth=2, seed=77)
+
+
+def normalize_of(table, k, canonical, a1, a2=None, **kw):
+    """normalize_of's dict with recs as an int64 array of shape (reads, 4), classes and hist as arrays, and per unit the bytes it has in
+    out1 and out2 when kept (len1, len2) and its bases: inputs of whole pairs, and no '\\r'"""
+    a1, a2 = as_u8(a1), None if a2 is None else as_u8(a2)
+    w = normalize_check_of(table, k, canonical, a1.tobytes(), None if a2 is None else a2.tobytes(), **kw)
+    w["recs"] = np.array(w["recs"], np.int64).reshape(-1, 4)
+    w["classes"] = np.array(w["classes"], np.uint8)
+    w["hist"] = np.array(w["hist"], np.int64).reshape(-1, 2)
+    two, units = a2 is not None, w["units_in"]
+    assert w["unpaired"] == 0 and w["reads_in"] == 2 * units and 13 not in a1
+    second = a2 if two else np.zeros(0, np.uint8)
+    w["len1"], w["len2"] = _unit_sums(_record_bytes(a1), _record_bytes(second), units, two)
+    s1, s2 = _unit_sums(_seq_lengths(a1, w["reads1"]), _seq_lengths(second, w["reads2"]), units, two)
+    w["bases"] = s1 + s2
+    return w
+
+
+def compose_normalize(block, tail, R):
+    """a rule that does not hash the unit number (target = 0), for a fixed table: counters and the histogram add up"""
+    assert block["target"] == 0
+    return compose(block, tail, R, same=NORM_SAME, tiled=NORM_TILED)
+
+
+def mix64_np(x):
+    """_normalize_check.mix64 over a uint64 array (products wrap)"""
+    x = x ^ (x >> np.uint64(33))
+    x = x * np.uint64(0xFF51AFD7ED558CCD)
+    x = x ^ (x >> np.uint64(33))
+    x = x * np.uint64(0xC4CEB9FE1A85EC53)
+    return x ^ (x >> np.uint64(33))
+
+
+def classify_np(kmers1, depth1, kmers2, depth2, u, target=0, min_depth=0, seed=0):
+    """_normalize_check.classify for arrays of units of two mates with the numbers u: (class, D)"""
+    u = np.asarray(u).astype(np.uint64)
+    has1, has2 = np.asarray(kmers1) > 0, np.asarray(kmers2) > 0
+    none = ~(has1 | has2)
+    far = np.int64(2 ** 62)
+    D = np.minimum(np.where(has1, np.asarray(depth1, np.int64), far), np.where(has2, np.asarray(depth2, np.int64), far))
+    D[none] = 0
+    cls = np.full(u.shape, NORM_KEPT, np.uint8)
+    low = ~none & (D < min_depth)
+    cls[low] = NORM_LOW
+    cls[none] = NORM_NO_KMERS
+    if target > 0:
+        r = mix64_np(np.full(u.shape, seed, np.uint64) ^ (u * np.uint64(NORM_GOLDEN))) >> np.uint64(32)
+        high = ~none & ~low & (D > target) & (((r * D.astype(np.uint64)) >> np.uint64(32)) >= np.uint64(target))
+        cls[high] = NORM_HIGH
+    return cls, D
+
+
+def compose_normalize_sampled(block, tail, R, target, min_depth, seed, keep_no_kmers=False, u=None):
+    """a rule that hashes the unit number (target > 0), for a fixed table; block and tail are normalize_of's dicts under any rule.  What a
+    read is (recs, the counters of the reads) is tiled or adds up; the class of every unit is found again for its number in the whole
+    input — r * U_block + i in the filler, R * U_block + j in the tail (u: other numbers, to show that they matter) —, and the kept
+    units give the other counters, the histogram and the output sizes.  The outputs are described: `kept` (uint8, per unit) and the
+    bytes a kept unit has in them (len1, len2)"""
+    assert set(block) == set(tail)
+    Ub, Ut = len(block["classes"]), len(tail["classes"])
+    units = R * Ub + Ut
+    out = {}
+    for k, b in block.items():
+        if k in ("k", "table_flags", "weak_below", "distinct"):
+            assert b == tail[k], (k, b, tail[k])
+            out[k] = b
+        elif k not in NORM_SAME + NORM_TILED + NORM_RULE + ("hist",):
+            out[k] = R * b + tail[k]
+    assert out["units_in"] == units
+
+    def per_unit(f):
+        return np.concatenate([np.tile(f(block), R), f(tail)])
+
+    mates = [per_unit(lambda w, m=m, j=j: w["recs"][m::2, j]) for m in (0, 1) for j in (0, 1)]
+    cls, D = classify_np(*mates, np.arange(units, dtype=np.uint64) if u is None else u, target, min_depth, seed)
+    kept = (cls == NORM_KEPT) | ((cls == NORM_NO_KMERS) & bool(keep_no_kmers))
+    rows = {f: Tiled(block[f], R, tail[f]) for f in ("recs", "len1", "len2", "bases")}
+    len1, len2, bases = (rows[f].whole() for f in ("len1", "len2", "bases"))
+    out.update(units_out=int(kept.sum()), reads_out=2 * int(kept.sum()), dropped_no_kmers=int(((cls == NORM_NO_KMERS) & ~kept).sum()),
+               dropped_low=int((cls == NORM_LOW).sum()), dropped_high=int((cls == NORM_HIGH).sum()), bases_out=int(bases[kept].sum()),
+               out1_bytes=int(len1[kept].sum()), out2_bytes=int(len2[kept].sum()), target=target, min_depth=min_depth, seed=seed,
+               flags=(block["flags"] & 1) | (2 if keep_no_kmers else 0))
+    bins = block["hist"].shape[0]
+    hist = np.zeros((bins, 2), np.int64)
+    if bins:
+        seen = cls != NORM_NO_KMERS
+        hist[:, 0] = np.bincount(np.minimum(D[seen], bins - 1), minlength=bins)
+        hist[:, 1] = np.bincount(np.minimum(D[seen & kept], bins - 1), minlength=bins)
+    out.update(rows, hist=hist, classes=cls, kept=kept.astype(np.uint8))
+    return out
+
+
 def cut_of(checker, composer, block, n, **kw):
     """what is owed for the first n bytes of block x R: n // B whole repetitions, then the checker on the block cut at n % B"""
     block = as_u8(block)
@@ -373,17 +562,15 @@ def _ref_reads(rng, refs, ln):
     return text[at:at + ln]
 
 
-def paired_blocks(rng, refs, pairs=1900, la=150, lb=140):
-    """(r1, r2, interleaved): paired_block's pairs with random qualities and the planted cases of test_gpu_trim.py — adapters in mate 1,
-    G tails in mate 2, quality that stays high —, and every 10th pair drawn from the screen's references.  Three blocks of
-    different lengths"""
+def _paired_rows(rng, refs, pairs, la, lb):
+    """paired_blocks' records as two arrays of `pairs` rows: "@p\n" S "\n+\n" Q "\n", one length per file"""
     r1, r2 = paired_block(rng, pairs, la, lb)
     r1, r2 = with_random_qualities(rng, r1, 33 + 22, 33 + 40), with_random_qualities(rng, r2, 33 + 22, 33 + 40)
     for a, ln in ((r1.reshape(pairs, -1), la), (r2.reshape(pairs, -1), lb)):     # quality that falls at a random place in every fifth read
         for k in range(2, pairs, 5):
             at = int(rng.integers(0, ln))
             a[k, 6 + ln + at:6 + 2 * ln] = rng.integers(33 + 2, 33 + 13, ln - at, dtype=np.uint8)
-    a1, a2 = r1.reshape(pairs, -1), r2.reshape(pairs, -1)          # records of one length each: "@p\n" S "\n+\n" Q "\n"
+    a1, a2 = r1.reshape(pairs, -1), r2.reshape(pairs, -1)
     for k in range(0, pairs, 7):
         at = int(rng.integers(20, la))
         a1[k, 3 + at:3 + la] = np.frombuffer((LONG_ADAPTER + b"A" * la)[:la - at], np.uint8)
@@ -397,17 +584,28 @@ def paired_blocks(rng, refs, pairs=1900, la=150, lb=140):
         frag = _ref_reads(rng, refs, la + 60)
         a1[k, 3:3 + la] = np.frombuffer(frag[:la], np.uint8)
         a2[k, 3:3 + lb] = np.frombuffer(revcomp(frag)[:lb], np.uint8)
+    return a1, a2
+
+
+def _three_blocks(a1, a2):
     il = np.concatenate([a1, a2], axis=1).reshape(-1)
     return lengthen(a1.reshape(-1), 2)[0], lengthen(a2.reshape(-1), 2)[0], lengthen(il, 2)[0]
 
 
-def paired_tails(rng, refs):
-    """(r1, r2, interleaved): pairs of many lengths — fragments shorter than, as long as and longer than the reads, mates too long for
-    the overlap search, empty ones, reads of the references, adapters behind short fragments"""
-    lengths = (0, 1, 29, 30, 31, 63, 64, 65, 100, 127, 128, 129, 250, 511, 512, 513)
+def paired_blocks(rng, refs, pairs=1900, la=150, lb=140):
+    """(r1, r2, interleaved): paired_block's pairs with random qualities and the planted cases of test_gpu_trim.py — adapters in mate 1,
+    G tails in mate 2, quality that stays high —, and every 10th pair drawn from the screen's references.  Three blocks of
+    different lengths"""
+    return _three_blocks(*_paired_rows(rng, refs, pairs, la, lb))
+
+
+TAIL_LENGTHS = (0, 1, 29, 30, 31, 63, 64, 65, 100, 127, 128, 129, 250, 511, 512, 513)
+
+
+def _tail_mates(rng, refs):
     m1, m2 = [], []
-    for la in lengths:
-        for lb in lengths:
+    for la in TAIL_LENGTHS:
+        for lb in TAIL_LENGTHS:
             ins = (max(la, lb) + 20, min(la, lb) - 7, 40)[(la + lb) % 3]
             if la and lb and 0 < ins < la + lb and la <= 512 and lb <= 512:
                 a, b = planted(rng, la, lb, ins)
@@ -421,7 +619,10 @@ def paired_tails(rng, refs):
         if ln > len(frag):                                    # a fragment shorter than the reads: both run into the adapter
             a, b = (frag + LONG_ADAPTER)[:ln], (revcomp(frag) + LONG_ADAPTER)[:ln]
         m1.append(a), m2.append(b)
+    return m1, m2
 
+
+def _tail_files(rng, m1, m2):
     def fq(mates, tag):
         return b"".join(b"@t%d/%s\n" % (i, tag) + s + b"\n+\n" + (rng.integers(15, 41, len(s)) + 33).astype(np.uint8).tobytes() + b"\n"
                         for i, s in enumerate(mates))
@@ -434,6 +635,76 @@ def paired_tails(rng, refs):
 
     il = b"".join(x for pair in zip(records(r1), records(r2)) for x in pair)
     return as_u8(r1), as_u8(r2), as_u8(il)
+
+
+def paired_tails(rng, refs):
+    """(r1, r2, interleaved): pairs of many lengths — fragments shorter than, as long as and longer than the reads, mates too long for
+    the overlap search, empty ones, reads of the references, adapters behind short fragments"""
+    return _tail_files(rng, *_tail_mates(rng, refs))
+
+
+def _barcode(rng, samples, s1, s2):
+    """the barcodes of a random sample over the first letters of both mates (mutable, at least as long as the barcodes): one pair in 8
+    keeps its letters, about one in 10 of the others gets one substituted letter, one in 20 an N"""
+    if rng.random() < 1 / 8:
+        return
+    _, b1, b2 = samples[int(rng.integers(len(samples)))]
+    codes = [bytearray(b1.encode()), bytearray(b2.encode())]
+    y = rng.random()
+    if y < 0.15:
+        c = codes[int(rng.integers(2))]
+        at = int(rng.integers(len(c)))
+        c[at] = ord("N") if y >= 0.10 else [x for x in b"ACGT" if x != c[at]][int(rng.integers(3))]
+    s1[:len(codes[0])] = list(codes[0])
+    s2[:len(codes[1])] = list(codes[1])
+
+
+def barcoded_blocks(rng, refs, samples=DEMUX_SAMPLES, pairs=1900, la=147, lb=145):
+    """(r1, r2, interleaved): paired_blocks' three blocks, of other lengths, with the samples' barcodes written over the first letters of
+    both mates: roughly equal shares for the samples, one pair in 8 undetermined"""
+    a1, a2 = _paired_rows(rng, refs, pairs, la, lb)
+    for u in range(pairs):
+        _barcode(rng, samples, a1[u, 3:3 + la], a2[u, 3:3 + lb])
+    return _three_blocks(a1, a2)
+
+
+def barcoded_tails(rng, refs, samples=DEMUX_SAMPLES):
+    """(r1, r2, interleaved): paired_tails' pairs, barcodes over those whose mates are both long enough; the lengths 0 and 1 stay
+    shorter than every barcode"""
+    m1, m2 = _tail_mates(rng, refs)
+    need1, need2 = max(len(s[1]) for s in samples), max(len(s[2]) for s in samples)
+    for i, (a, b) in enumerate(zip(m1, m2)):
+        if len(a) >= need1 and len(b) >= need2:
+            a, b = bytearray(a), bytearray(b)
+            _barcode(rng, samples, a, b)
+            m1[i], m2[i] = bytes(a), bytes(b)
+    return _tail_files(rng, m1, m2)
+
+
+TABLES_PAIR_SEED, BARCODED_SEED = 20261023, 20261024
+
+
+def tables_pair_data(refs):
+    """(blocks, tails) of the paired input that tests/test_gpu_big_offsets_tables.py gives fq-kcount and fq-normalize"""
+    rng = np.random.default_rng(TABLES_PAIR_SEED)
+    return paired_blocks(rng, refs), paired_tails(rng, refs)
+
+
+def barcoded_data(refs):
+    """(blocks, tails) of the input that tests/test_gpu_big_offsets_tables.py gives fq-demux"""
+    rng = np.random.default_rng(BARCODED_SEED)
+    return barcoded_blocks(rng, refs), barcoded_tails(rng, refs)
+
+
+def normalize_counted(b1, b2, t1, t2):
+    """the input whose k-mers fq-normalize's given table counts: the records of both blocks once, those of every 4th pair three more
+    times, those of every 9th pair eight more times, then both tails.  Depths 1, 4, 9 and 12 where the mates do not overlap"""
+    parts = []
+    for b in (b1, b2):
+        off = index_of(b)["off"]
+        recs = [b[off[4 * i]:off[4 * i + 4]] for i in range((off.size - 1) // 4)]
+        parts += recs + recs[::4] * 3 + recs[::9] * 8
+    return np.concatenate(parts + [as_u8(t1), as_u8(t2)])
 
 
 FA_ALPHABET = np.frombuffer(b"ACGTACGTACGTACGTACGT", np.uint8)

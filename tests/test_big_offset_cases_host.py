@@ -55,7 +55,21 @@ def test_layout_facts(probes, refs):
     b1, b2, bi = C.paired_blocks(rng, texts)
     fa, _, _ = C.fasta_block(rng)
     assert len({block.size, b1.size, b2.size, bi.size, fa.size}) == 5
-    for B, given in ((block.size, None), (b1.size, None), (bi.size, None), (fa.size, None), (max(b1.size, b2.size), -(-C.LIMIT // min(b1.size, b2.size)))):
+    # the inputs of fq-kcount / fq-normalize (other pairs of the same lengths) and of fq-demux: new lengths, and repeated more often
+    (k1, k2, ki), _ = C.tables_pair_data(texts)
+    (x1, x2, xi), _ = C.barcoded_data(texts)
+    assert len({block.size, b1.size, b2.size, bi.size, fa.size, x1.size, x2.size, xi.size}) == 8 and len({k1.size, k2.size, ki.size}) == 3
+    more = C.demux_R(C.demux_of(x1, x2, **C.DEMUX_KW))
+    assert more > -(-C.LIMIT // min(x1.size, x2.size))
+    for blk in (k1, k2, ki, x1, x2, xi):
+        off = C.index_of(blk)["off"]
+        assert blk[-1] == 10 and (off.size - 1) % 4 == 0
+        for m in C.MARKS:                                        # strictly inside a record: no record of any repetition starts there
+            assert m % blk.size not in off[::4] and (m + 1) % blk.size not in off[::4]
+    pairs = ((b1.size, None), (bi.size, None), (max(b1.size, b2.size), -(-C.LIMIT // min(b1.size, b2.size))),
+             (k1.size, None), (ki.size, None), (max(k1.size, k2.size), -(-C.LIMIT // min(k1.size, k2.size))),
+             (x1.size, more), (x2.size, more), (xi.size, C.demux_R(C.demux_of(xi, interleaved=True, **C.DEMUX_KW))))
+    for B, given in ((block.size, None), (fa.size, None)) + pairs:
         assert 400_000 < B < 1_300_000
         L = C.layout(B, 12345, given)
         assert B % 2 == 1 and B % 3 != 0
@@ -189,3 +203,150 @@ def test_fasta():
     q = C.fasta_intervals(rng, mt, R * cb)
     assert (whole.count_many(q) == mt.count_many([(c - R * cb, lo, hi) for c, lo, hi in q])).all()
     assert mb.gc_bases != mb.acgt_bases and mb.acgt_bases != mb.bases
+
+
+# ---- fq-kcount, fq-demux, fq-normalize ------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def texts(refs):
+    from _screen_check import contigs_of
+    return [c for r in refs for c in contigs_of(r) if len(c) > 400]
+
+
+@pytest.fixture(scope="module")
+def barcoded(texts):
+    rng = np.random.default_rng(20261005)
+    blocks = C.barcoded_blocks(rng, texts, pairs=60)
+    tails = C.barcoded_tails(rng, texts)
+    return blocks, tails, [np.concatenate([np.tile(b, R), t]) for b, t in zip(blocks, tails)]
+
+
+@pytest.mark.parametrize("k,canonical", [(13, False), (21, True), (32, False)])
+def test_kcount(paired, k, canonical):
+    (b1, b2, _), (t1, t2, _), (d1, d2, _) = paired
+    for blocks, tails, data in (((b1, None), (t1, None), (d1, None)), ((b1, b2), (t1, t2), (d1, d2))):
+        block, tail = C.kcount_of(*blocks, k, canonical), C.kcount_of(*tails, k, canonical)
+        want, direct = C.compose_kcount(block, tail, R), C.kcount_of(*data, k, canonical)
+        same(want, direct)
+        assert C.kcount_want(want) == C.kcount_want(direct) and C.kcount_want(want).distinct == len(direct["table"])
+        assert set(tail["table"]) - set(block["table"]), "a key that only the tail has"
+        assert set(tail["table"]) & set(block["table"]), "a key whose count is R * the block's + the tail's"
+    if k == 13:
+        for c in (5, b1.size // 3, b1.size - 1):
+            cut = np.tile(b1, R)[:2 * b1.size + c]
+            same(C.cut_of(lambda a: C.kcount_of(a, None, k, canonical), C.compose_kcount, b1, cut.size), C.kcount_of(cut, None, k, canonical))
+
+
+def written_demux(w):
+    out = C.whole(w)
+    for which in ("out1", "out2"):
+        out[which] = b"".join(t.whole() for t in w[which])
+    return out
+
+
+@pytest.mark.parametrize("keep_barcode", [False, True])
+def test_demux(barcoded, keep_barcode):
+    (b1, b2, bi), (t1, t2, ti), (d1, d2, di) = barcoded
+    kw = dict(C.DEMUX_KW, keep_barcode=keep_barcode)
+    for blocks, tails, data, more in (((b1, b2), (t1, t2), (d1, d2), {}), ((bi,), (ti,), (di,), dict(interleaved=True))):
+        block, tail = C.demux_of(*blocks, **kw, **more), C.demux_of(*tails, **kw, **more)
+        want, direct = C.compose_demux(block, tail, R), C.demux_of(*data, **kw, **more)
+        bad = C.equal(written_demux(want), direct)
+        assert not bad, bad
+        assert [len(t) for t in want["out1"]] == [r["bytes1"] for r in direct["rows"]]
+        assert min(block["perfect"], block["mismatched"], block["unmatched"]) > 0 and block["no_barcode"] == 0 and tail["no_barcode"] > 0
+        assert (direct["bases_clipped"] > 0) != keep_barcode
+
+
+def test_demux_barcodes_and_shares(texts):
+    """the sheet's barcodes are far enough apart for one mismatch, and the block the GPU module repeats gives every sample and
+    "undetermined" at least 8 % of its units"""
+    for j in (1, 2):
+        codes = [s[j] for s in C.DEMUX_SAMPLES]
+        assert all(len(c) == 8 for c in codes)
+        assert min(sum(x != y for x, y in zip(p, q)) for i, p in enumerate(codes) for q in codes[:i]) >= 4
+    (b1, b2, bi), (t1, t2, ti) = C.barcoded_data(texts)
+    for blocks, tails, more in (((b1, b2), (t1, t2), {}), ((bi,), (ti,), dict(interleaved=True))):
+        block, tail = C.demux_of(*blocks, **C.DEMUX_KW, **more), C.demux_of(*tails, **C.DEMUX_KW, **more)
+        assert len(block["rows"]) == 6 and all(r["units"] >= 0.08 * block["units_in"] for r in block["rows"])
+        assert min(block["perfect"], block["mismatched"], block["unmatched"]) > 0 and tail["no_barcode"] > 0
+
+
+def test_classify_np():
+    from _normalize_check import classify
+    rng = np.random.default_rng(20261006)
+    n = 10_000
+    u = rng.integers(0, 2 ** 33, n).astype(np.uint64)
+    u[:6] = (0, 2 ** 31 - 1, 2 ** 31, 2 ** 32 - 1, 2 ** 32, 2 ** 32 + 1)
+    for target, min_depth, seed in ((3, 2, 77), (0, 2, 5), (20, 0, 2 ** 64 - 1), (7, 7, 0)):
+        mates = [rng.integers(0, 3, n), rng.integers(max(0, target - 3), target + 12, n), rng.integers(0, 3, n), rng.integers(0, 2 * target + 40, n)]
+        mates[1][:6], mates[3][:6], mates[0][:6], mates[2][:6] = target + 5, target + 9, 1, 1
+        cls, D = C.classify_np(*mates, u, target, min_depth, seed)
+        want = [classify([(int(mates[0][i]), int(mates[1][i])), (int(mates[2][i]), int(mates[3][i]))], int(u[i]), target, min_depth, seed) for i in range(n)]
+        assert list(zip(cls.tolist(), D.tolist())) == want
+        assert set(cls.tolist()) == {0, 1} | ({2} if min_depth else set()) | ({3} if target else set())
+    # the number of the unit matters past 32 bits: among units above 2^32 some change class when the number is cut
+    big = u[u >= 2 ** 32]
+    deep = np.full(big.size, 9)
+    a, _ = C.classify_np(deep, deep, deep, deep, big, 3, 2, 77)
+    b, _ = C.classify_np(deep, deep, deep, deep, big & np.uint64(2 ** 32 - 1), 3, 2, 77)
+    assert (a != b).any()
+
+
+def kept_bytes(data, lens, kept):
+    at = np.cumsum(lens) - lens
+    return b"".join(data[a:a + n].tobytes() for a, n, k in zip(at.tolist(), lens.tolist(), kept.tolist()) if k)
+
+
+NORM_FIELDS = ("reads1", "reads2", "lines1", "lines2", "input_bytes1", "input_bytes2", "pairs", "unpaired", "units_in", "units_out", "reads_in",
+               "reads_out", "dropped_no_kmers", "dropped_low", "dropped_high", "short_reads", "bases_in", "bases_out", "windows", "kmers", "skipped",
+               "weak_kmers", "absent_kmers", "out1_bytes", "out2_bytes", "flags", "k", "table_flags", "target", "min_depth", "weak_below", "seed",
+               "distinct", "hist", "classes", "recs")
+
+
+def test_normalize(paired):
+    from _normalize_check import FIELDS
+    assert set(FIELDS) <= set(NORM_FIELDS)
+    (b1, b2, bi), (t1, t2, ti), (d1, d2, di) = paired
+    table = C.kcount_of(C.normalize_counted(b1, b2, t1, t2), None, 21, True)["table"]
+    for blocks, tails, data, more in (((b1, b2), (t1, t2), (d1, d2), {}), ((bi,), (ti,), (di,), dict(interleaved=True))):
+        # a rule without the hash
+        rule = dict(more, target=0, min_depth=2, bins=12)
+        block, tail = C.normalize_of(table, 21, True, *blocks, **rule), C.normalize_of(table, 21, True, *tails, **rule)
+        direct = C.normalize_of(table, 21, True, *data, **rule)
+        same(C.compose_normalize(block, tail, R), direct)
+        assert 0 < direct["dropped_low"] and 0 < direct["units_out"] and tail["dropped_no_kmers"] > 0
+        # the sampled rule: the statistics and the histogram, then the outputs from the kept mask and the lengths
+        for keep in (False, True):
+            want = C.compose_normalize_sampled(block, tail, R, keep_no_kmers=keep, **C.NORM_SAMPLED)
+            direct = C.normalize_of(table, 21, True, *data, bins=12, keep_no_kmers=keep, **more, **C.NORM_SAMPLED)
+            bad = C.equal({k: v for k, v in C.whole(want).items() if k in NORM_FIELDS}, {k: direct[k] for k in NORM_FIELDS})
+            assert not bad, bad
+            kept = want["kept"]
+            assert kept.size == direct["units_in"] and kept_bytes(data[0], want["len1"].whole(), kept) == direct["out1"]
+            if more:
+                assert direct["out2"] == b"" and want["out2_bytes"] == 0
+            else:
+                assert kept_bytes(data[1], want["len2"].whole(), kept) == direct["out2"]
+            assert min(direct["dropped_high"], direct["dropped_low"], direct["units_out"]) > 0
+        # the law can fail: with the block's own numbering in every repetition other units are kept
+        Ub = len(block["classes"])
+        local = np.concatenate([np.tile(np.arange(Ub, dtype=np.uint64), R), R * Ub + np.arange(len(tail["classes"]), dtype=np.uint64)])
+        right = C.compose_normalize_sampled(block, tail, R, **C.NORM_SAMPLED)["kept"]
+        wrong = C.compose_normalize_sampled(block, tail, R, u=local, **C.NORM_SAMPLED)["kept"]
+        assert (wrong[:Ub] == right[:Ub]).all() and (wrong[Ub:R * Ub] != right[Ub:R * Ub]).any() and (wrong[R * Ub:] == right[R * Ub:]).all()
+
+
+def test_normalize_shares(texts):
+    """the block the GPU module repeats, against the table of its counted input and under its sampled rule: each of kept without the
+    hash, dropped_low, dropped_high and kept by the hash is at least 5 % of the units; the tail has units without k-mers"""
+    (b1, b2, _), (t1, t2, _) = C.tables_pair_data(texts)
+    table = C.kcount_of(C.normalize_counted(b1, b2, t1, t2), None, 21, True)["table"]
+    block = C.normalize_of(table, 21, True, b1, b2, **C.NORM_SAMPLED)
+    units, target = block["units_in"], C.NORM_SAMPLED["target"]
+    D = np.minimum(block["recs"][0::2, 1], block["recs"][1::2, 1])           # (every mate of the block has k-mers)
+    assert (block["recs"][:, 0] > 0).all()
+    kept = block["classes"] == 0
+    shares = dict(plain=int((kept & (D <= target)).sum()), low=block["dropped_low"], high=block["dropped_high"], hashed=int((kept & (D > target)).sum()))
+    assert sum(shares.values()) == units and all(20 * v >= units for v in shares.values()), (shares, units)
+    assert C.normalize_of(table, 21, True, t1, t2, **C.NORM_SAMPLED)["dropped_no_kmers"] > 0

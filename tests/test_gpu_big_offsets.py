@@ -33,17 +33,18 @@ SCREEN_REC = np.dtype([("kmers", "<u4"), ("hit_kmers", "<u4"), ("best_hits", "<u
 
 class Big:
     """block x R + tail in device memory between guard bytes 'G'; the filler is the block, repeated on the device into the buffer.
-    fields: where every header of the block holds FIELD hex digits, which get the repetition number."""
+    fields: where every header of the block holds FIELD hex digits, which get the repetition number.  at: its first byte sits that many
+    bytes past a 4 KiB boundary."""
 
-    def __init__(self, torch, block, tail, R=None, fields=None):
+    def __init__(self, torch, block, tail, R=None, fields=None, at=AT):
         self.torch, self.block, self.tail = torch, block, tail
         self.L = C.layout(block.size, tail.size, R)
         self.R, self.B, self.n, self.fields = self.L["R"], block.size, self.L["n"], fields
-        self.t = torch.full((PAD + AT + self.n + PAD + 4096,), 0x47, dtype=torch.uint8, device="cuda")
+        self.t = torch.full((PAD + at + self.n + PAD + 4096,), 0x47, dtype=torch.uint8, device="cuda")
         base = self.t.data_ptr()
-        self.start = ((base + PAD + 4095) // 4096) * 4096 - base + AT
+        self.start = ((base + PAD + 4095) // 4096) * 4096 - base + at
         self.ptr = base + self.start
-        assert self.ptr % 4096 == AT and self.start + self.n + PAD <= self.t.numel()
+        assert self.ptr % 4096 == at and self.start + self.n + PAD <= self.t.numel()
         filler = self.filler().view(self.R, self.B)
         filler.copy_(torch.from_numpy(block.copy()).cuda().expand(self.R, self.B))
         if fields is not None:                                  # one digit of all repetitions' numbers at a time
