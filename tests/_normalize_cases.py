@@ -3,6 +3,7 @@ SCFQ_NORM_LDS_WINDOWS and SCFQ_KCOUNT_START_BITS are read once per process.  Eve
 library returns with the checker of _normalize_check.py with == and returns the number of calls it compared."""
 import numpy as np
 
+from _every_k_cases import NORM_OPTS, OFFSETS, cases
 from _kcount_check import kcount_of, kcount_of_np
 from _normalize_check import assert_stats, normalize_of
 
@@ -293,4 +294,29 @@ def partition(torch, scfq):
     return calls
 
 
-CASES = {"lengths": lengths, "select": select, "special_keys": special_keys, "rule": rule, "partition": partition}
+# ---- 9. every k -----------------------------------------------------------------------------------------------------------------
+def every_k_one(torch, scfq, k, offsets=OFFSETS, two_pass_at=(OFFSETS[0], OFFSETS[-1])):
+    """the case set of _every_k_cases.py at one k, plain and canonical, against a table counted from the set itself: as a handle with the
+    device pointer at each of `offsets`, and in the two-pass form at each of `two_pass_at`"""
+    data = cases(k).fastq
+    calls = 0
+    for canonical in (False, True):
+        ctable = table_of(data, k, canonical, big=True)
+        want = normalize_of(ctable, k, canonical, data, bins=12, **NORM_OPTS)
+        assert set(want["classes"]) == {0, 1, 2, 3} and max(r[0] for r in want["recs"]) == 513
+        with device_table(scfq, data, k, canonical) as dtable:
+            for off in offsets:
+                check_device(torch, scfq, dtable, ctable, k, canonical, data, ctx=("every k", k, canonical, off), want=want, bins=12, offs=(off, 0), **NORM_OPTS)
+        for off in two_pass_at:
+            check_device(torch, scfq, None, ctable, k, canonical, data, ctx=("every k, two-pass", k, canonical, off), want=want, bins=12, offs=(off, 0),
+                         two_pass=dict(k=k, canonical=canonical), **NORM_OPTS)
+        calls += len(offsets) + len(two_pass_at)
+    return calls
+
+
+def every_k(torch, scfq, c=BUILT_IN_C):
+    """every k at one offset each: the run under SCFQ_NORM_LDS_WINDOWS=64, where the reads of 65 and more windows select from device memory"""
+    return sum(every_k_one(torch, scfq, k, offsets=OFFSETS[1:2], two_pass_at=OFFSETS[:1]) for k in range(13, 33))
+
+
+CASES = {"every_k": every_k, "lengths": lengths, "select": select, "special_keys": special_keys, "rule": rule, "partition": partition}
