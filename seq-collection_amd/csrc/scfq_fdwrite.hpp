@@ -58,7 +58,10 @@ struct Pinned {
       if (k + 1 < n_chunks) SCFQ_SCRATCH_CHK(errbuf, issue(k + 1));
       const uint64_t lo = k * kChunk, len = std::min(kChunk, nb - lo);
       const int rc = write_all(fd, pin[k & 1], len, errbuf);
-      if (rc) return rc;
+      if (rc) {      // chunk k+1 is on its way into the other buffer: it lands before the caller may free that buffer (~Pinned)
+        if (k + 1 < n_chunks) (void)hipEventSynchronize(ev[(k + 1) & 1]);
+        return rc;
+      }
     }
     return SCFQ_OK;
   }
