@@ -1195,6 +1195,98 @@ int scfq_format_norm_row_tsv(const scfq_norm_stats* s, int header, char* buf, ui
 int scfq_format_norm_hist_tsv(uint64_t depth, uint64_t units_in, uint64_t units_out, char* buf, uint64_t cap);
 const char* scfq_norm_error_detail(void);        /* static, thread-local */
 
+/* ---- `sc fq-complexity` (addition; not in the reference): symmetric DUST masking and filtering of low-complexity reads ----
+ * Inputs, lines, records, texts, pairing (`pairs`, `unpaired`), interleaving and too_long are fq-trim's, word for word. A read
+ * whose sequence text S has L > SCFQ_CPLX_MAX_LEN bytes is too long: nothing looks at it, it is never masked, never low, and
+ * its record is echoed as fq-trim echoes one.
+ * Triplets. Position i in [0, L-2) is VALID iff S[i], S[i+1], S[i+2] are each exactly 'A', 'C', 'G' or 'T' (byte-exact: lower
+ *  case and 'N' are no bases, as in fq-kmers); t(i) is its 6-bit code.
+ * Intervals. [i, j] with 0 <= i < j <= L-3 and l = j-i+1 <= window - 2; window is in bases, 8 .. 64, default 64 (sdust's W,
+ *  so l <= 62). c(i,j) is the number of pairs a < b in [i, j], both valid, with t(a) == t(b). The score of the interval is
+ *  the fraction c / (l-1); fractions are only ever compared by cross-multiplication (c <= 1891, l-1 <= 61).
+ * High. 10 * c > threshold * (l-1); threshold is 1 .. 310, default 20 (sdust's T). At 310 nothing is high; equality is not.
+ * Perfect. The interval is high and no sub-interval [i', j'], i <= i' < j' <= j, has a strictly larger score:
+ *  c(i',j') * (l-1) <= c(i,j) * (l'-1) for all of them (the symmetric DUST of Morgulis et al. 2006). Agreement with
+ *  dustmasker or sdust is not claimed: they restart the window at an 'N', here an invalid triplet simply matches nothing.
+ * Masked positions. The union of [i, j+2] over all perfect intervals.
+ * Per read. masked: the number of masked positions; intervals: the number of perfect intervals; first: the smallest masked
+ *  position, 0xFFFF without one; score: floor(10 * c / (l-1)) of the interval with the largest fraction over ALL intervals,
+ *  high or not, 0 for L < 4.
+ * Low read. L >= 1 and 100 * masked > max_masked_pct * L; max_masked_pct is 0 .. 100, default 100 (nothing is low). A low
+ *  single-end read is dropped; a pair is dropped when either mate is low.
+ * Output record of a kept read that is not too long, always four lines: header text, '\n', S', '\n', separator text, '\n',
+ *  the WHOLE quality text unchanged, '\n'. S' by `mask`: SCFQ_CPLX_MASK_NONE: S; SCFQ_CPLX_MASK_LOWER (the default): a masked
+ *  byte in 'A' .. 'Z' gets | 0x20, any other byte stays; SCFQ_CPLX_MASK_N: every masked byte becomes 'N'.
+ * All values are integers and exact. Device pipeline: line index (K5), D1 — a wave per read: the triplet codes and, per
+ *  position, a 64-bit word "equal to the triplet d in front" in LDS; lane i of a round owns start 64 w + i and walks its
+ *  interval one triplet at a time, best(i, j) = max(c / (l-1), best(i, j-1), best(i+1, j)) with the neighbour lane's value of
+ *  the step before; 8 bytes and 8 mask words per read —, D2 — a thread per read or pair: low or not, output lengths per group
+ *  of 32, the statistics and the score histogram —, one exclusive scan per output, D3 — a wave per group writes the records. */
+#define SCFQ_CPLX_MAX_LEN       SCFQ_INSERT_MAX_LEN
+#define SCFQ_CPLX_INTERLEAVED   0x1u
+#define SCFQ_CPLX_MASK_NONE     0u
+#define SCFQ_CPLX_MASK_LOWER    1u
+#define SCFQ_CPLX_MASK_N        2u
+#define SCFQ_CPLX_SCORE_BINS    312   /* reads_in by score 0 .. 310; the last bin: too long */
+typedef struct scfq_cplx_opts {
+  uint64_t struct_size;   /* sizeof(scfq_cplx_opts) */
+  uint32_t flags;         /* SCFQ_CPLX_INTERLEAVED */
+  uint32_t window;        /* 8 .. 64 */
+  uint32_t threshold;     /* 1 .. 310 */
+  uint32_t mask;          /* SCFQ_CPLX_MASK_* */
+  uint32_t max_masked_pct;   /* 0 .. 100 */
+  uint32_t reserved[3];   /* 0 */
+} scfq_cplx_opts;
+typedef struct scfq_cplx_rec {     /* the per-read table: 8 bytes per read; paired input: mate m of pair p is entry 2p + m */
+  uint16_t score, masked, first, intervals;   /* a too-long read: {0xFFFF, 0, 0xFFFF, 0} */
+} scfq_cplx_rec;
+typedef struct scfq_cplx_stats {   /* 29 x 8 bytes */
+  uint64_t struct_size;   /* caller sets to sizeof(scfq_cplx_stats) before the call */
+  uint64_t abi_version;   /* library writes SCFQ_ABI_VERSION */
+  uint64_t reads1, reads2;             /* as scfq_trim_stats, down to `unpaired` */
+  uint64_t lines1, lines2;
+  uint64_t input_bytes1, input_bytes2;
+  uint64_t pairs, unpaired;
+  uint64_t reads_in, reads_out;        /* reads_in: reads1, or 2 * pairs; reads_in = reads_out + dropped_reads */
+  uint64_t too_long;
+  uint64_t low_reads;                  /* reads that are low themselves */
+  uint64_t dropped_reads;              /* paired input: both reads of a pair with a low mate */
+  uint64_t masked_reads;               /* reads with masked > 0 */
+  uint64_t perfect_intervals;          /* sum of `intervals` */
+  uint64_t bases_in, bases_out;        /* sums of L over reads_in and reads_out */
+  uint64_t masked_bases;               /* sum of `masked` over reads_in */
+  uint64_t masked_bases_out;           /* the same over reads_out */
+  uint64_t max_score;                  /* over the reads that are not too long */
+  uint64_t out1_bytes, out2_bytes;     /* sizes of the outputs, written or not */
+  uint64_t flags, window, threshold, mask, max_masked_pct;   /* the parameters as used */
+} scfq_cplx_stats;
+
+/* r1 / r2, the outputs, the sizing call, a too-small output (SCFQ_EARG naming it, stats complete, NO byte written to ANY
+ * output: D3 compares the scanned totals with the capacities before it stores) and the device-pointer rules are those of
+ * scfq_trim_buffers. recs: NULL, or memory of the outputs' kind (host with out_is_device = 0, device otherwise) for
+ * recs_cap entries of the per-read table; fewer than reads_in is SCFQ_EARG with text: stats is complete and nothing is
+ * written to the table or to an output. hist_host: NULL, or HOST memory for SCFQ_CPLX_SCORE_BINS words. SCFQ_EARG with
+ * text in scfq_cplx_error_detail(), before any launch: unknown flag bits, window, threshold, mask or max_masked_pct out of
+ * range, reserved not 0, out2 without a second input, a second buffer with SCFQ_CPLX_INTERLEAVED; without text: a NULL stats
+ * or a wrong struct_size (stats' or opts'), a NULL pointer with a size or capacity. opts = NULL: the defaults. There is no
+ * CPU fallback (SCFQ_EHIP without a device). */
+int scfq_cplx_buffers(const void* r1, uint64_t n1, const void* r2, uint64_t n2, int is_device, const scfq_cplx_opts* opts,
+                      scfq_cplx_rec* recs, uint64_t recs_cap, uint64_t* hist_host, void* out1, uint64_t cap1, void* out2,
+                      uint64_t cap2, int out_is_device, scfq_cplx_stats* stats);
+/* As scfq_trim_files: staged inputs, descriptors below 0 are not produced, out1 then out2, SCFQ_EPIPE / SCFQ_EIO.
+ * per_read_fd >= 0: the per-read table as rows of scfq_format_cplx_rec_tsv, each with a '\n', written before the outputs. */
+int scfq_cplx_files(const char* path1, const char* path2, const scfq_opts* opts, const scfq_cplx_opts* copts, int out1_fd,
+                    int out2_fd, int per_read_fd, uint64_t* hist_host, scfq_cplx_stats* stats);
+/* The one-row report without trailing newline; header != 0: the names of its columns instead. The columns: reads_in reads_out
+ * dropped_reads low_reads too_long pairs unpaired masked_reads perfect_intervals bases_in bases_out masked_bases
+ * masked_bases_out max_score out1_bytes out2_bytes. Returns the number of bytes needed (excluding NUL); writes at most cap
+ * bytes incl. NUL. */
+int scfq_format_cplx_stats_tsv(const scfq_cplx_stats* s, int header, char* buf, uint64_t cap);
+/* "<read>\t<length>\t<score>\t<masked>\t<first>\t<intervals>" without trailing newline; r = NULL: the names of the columns.
+ * score is "-" for a too-long read, first is "-" without a masked position. The same return rule. */
+int scfq_format_cplx_rec_tsv(uint64_t read, const scfq_cplx_rec* r, uint64_t length, char* buf, uint64_t cap);
+const char* scfq_cplx_error_detail(void);        /* static, thread-local */
+
 /* ---- `sc fa-gc` (FASTA group): src/fa_gc.nim, docs/fa-gc.md, sc.nim:84-96 --------------------------------------------
  * GC content of the windows [pos - w, pos + w] around 1-based positions of a FASTA. The contract:
  *   Lines.   A header line is a line whose first byte is '>' (a line that starts at byte 0 of the input included); every

@@ -123,6 +123,11 @@ int scfq_debug_kcount_stages(double* ms, uint32_t cap);
  * SCFQ_NORM_TIMING=1 is in the environment (zeros otherwise). The counting pass of the two-pass form is read with
  * scfq_debug_kcount_stages. Writes min(cap, 4) values, returns 4. */
 int scfq_debug_norm_stages(double* ms, uint32_t cap);
+/* Stage times of the calling thread's last scfq_cplx_buffers / scfq_cplx_files, in milliseconds: ms[0] the line indexes of
+ * paired input (host clock, 0 for single-end input), ms[1] D1, the interval kernel, ms[2] D2 with its scans, ms[3] D3, the write
+ * kernel — the last three HIP-event times, taken only while SCFQ_CPLX_TIMING=1 is in the environment (zeros otherwise). Writes
+ * min(cap, 4) values, returns 4. */
+int scfq_debug_cplx_stages(double* ms, uint32_t cap);
 /* Stage times of the calling thread's last scfq_fa_index_buffer / scfq_fa_index_file, in milliseconds: ms[0] F1, the tile scan,
  * ms[1] F2, the scan over the tile records, ms[2] F3, the contig table's kernel, ms[3] unused (0) — HIP-event times, taken only
  * while SCFQ_FA_TIMING=1 is in the environment (zeros otherwise). Writes min(cap, 4) values, returns 4. */

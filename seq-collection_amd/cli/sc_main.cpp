@@ -1076,6 +1076,128 @@ static int cmd_fq_normalize(const std::vector<std::string>& params) {
   return 0;
 }
 
+// command "fq-complexity" (addition, not in the reference): IN.fq, R1.fq R2.fq with --out1=PATH --out2=PATH (or neither: the report
+// only), or --interleaved IN.fq; --window=N, --threshold=N, --mask=lower|n|none, --max-masked-pct=N, --report, --stats, --hist,
+// --per-read=PATH, --out=PATH, -t/--header, -b/--basename, -a/--absolute.  The report goes to stdout, or to stderr while stdout carries the reads.
+static const char* kCplxHistHeader = "score\treads";
+static int cmd_fq_complexity(const std::vector<std::string>& params) {
+  static const char* const help =
+      "Mask and filter low-complexity sequence (symmetric DUST): homopolymer runs, microsatellites and other short-period repeats inside reads\n\n"
+      "Usage:\n  fq-complexity [options] IN.fq > out.fq\n  fq-complexity [options] --out1=PATH --out2=PATH R1.fq R2.fq\n"
+      "  fq-complexity [options] --interleaved IN.fq > out.fq\n\n"
+      "Arguments:\n  IN.fq            One FASTQ: single-end reads, or pairs with --interleaved; the kept reads go to stdout or to --out=PATH\n"
+      "  R1.fq R2.fq      Two FASTQs: record i of each is pair i; without --out1 and --out2 only the report is produced\n\nOptions:\n"
+      "      --window=N             Longest interval that is scored, in bases, 8 .. 64 (default: 64)\n"
+      "      --threshold=N          An interval is low-complexity when ten times its score is above N, 1 .. 310 (default: 20)\n"
+      "      --mask=lower|n|none    Masked bases become lower case, become N, or stay as they are (default: lower)\n"
+      "      --max-masked-pct=N     Drop a read, or a pair with such a mate, when more than N percent of it is masked (default: 100)\n"
+      "      --interleaved          The one argument is an interleaved FASTQ: records 2i and 2i+1 are pair i\n"
+      "      --out=PATH             With one FASTQ: the kept reads, or pairs, go to PATH and the report to stdout\n"
+      "      --out1=PATH            With R1.fq R2.fq: mate 1 of the kept pairs goes to PATH\n"
+      "      --out2=PATH            With R1.fq R2.fq: mate 2 of the kept pairs goes to PATH\n"
+      "      --report               No reads are written: the one-row report on stdout\n"
+      "      --stats                While stdout carries the reads: the report row to stderr\n"
+      "      --hist                 Instead of the report row the table \"score reads\"; the reads that are too long in a last row\n"
+      "      --per-read=PATH        One row per read to PATH: read length score masked first intervals\n"
+      "  -t, --header               Output the header\n  -b, --basename             Add a column with the basename of the first FASTQ\n"
+      "  -a, --absolute             Add a column with the absolute path of the first FASTQ\n"
+      "  -h, --help                 Show this help\n";
+  Columns cols;
+  scfq_cplx_opts co = fresh<scfq_cplx_opts>();
+  co.window = 64;
+  co.threshold = 20;
+  co.mask = SCFQ_CPLX_MASK_LOWER;
+  co.max_masked_pct = 100;
+  bool stats = false, hist = false, report_only = false;
+  std::vector<std::string> files;
+  std::string out, out1, out2, per_read;
+  const std::vector<Opt> table = cols.options({
+      opt_number("window", 6, 8, 64, &co.window),
+      opt_number("threshold", 6, 1, 310, &co.threshold),
+      opt_custom("mask", [&](std::string& v) {
+        if (v == "lower") co.mask = SCFQ_CPLX_MASK_LOWER;
+        else if (v == "n") co.mask = SCFQ_CPLX_MASK_N;
+        else if (v == "none") co.mask = SCFQ_CPLX_MASK_NONE;
+        else return Reject::bad_value;
+        return Reject::none;
+      }),
+      opt_number("max-masked-pct", 6, 0, 100, &co.max_masked_pct),
+      opt_bits("interleaved", &co.flags, SCFQ_CPLX_INTERLEAVED),
+      opt_text("out", &out),
+      opt_text("out1", &out1),
+      opt_text("out2", &out2),
+      opt_flag("report", 0, &report_only),
+      opt_flag("stats", 0, &stats),
+      opt_flag("hist", 0, &hist),
+      opt_text("per-read", &per_read),
+  });
+  if (!parse_options(params, help, table, &files)) return 0;
+  const bool interleaved = co.flags & SCFQ_CPLX_INTERLEAVED;
+  if (files.empty()) quit_no_fastq();
+  if (files.size() > 2 || (interleaved && files.size() != 1)) usage_error(help, "fq-complexity takes one FASTQ, R1.fq and R2.fq, or one FASTQ with --interleaved");
+  const bool two = files.size() == 2;
+  if (two && !out.empty()) usage_error(help, "R1.fq R2.fq write to --out1=PATH and --out2=PATH");
+  if (two && out1.empty() != out2.empty()) usage_error(help, "--out1=PATH and --out2=PATH go together");
+  if (!two && (!out1.empty() || !out2.empty())) usage_error(help, "--out1=PATH and --out2=PATH go with R1.fq R2.fq; one input is written to stdout or to --out=PATH");
+  if (report_only && (!out.empty() || !out1.empty())) usage_error(help, "--report writes no reads: it goes without --out, --out1 and --out2");
+  for (const std::string& f : files) require_suffix_room(f);
+  // the inputs are looked at before an output file is made
+  for (const std::string& f : files)
+    if (access(f.c_str(), R_OK) != 0) quit_unable_to_open(f);
+  const bool to_stdout = !two && out.empty() && !report_only;      // stdout carries the reads: the report goes to stderr
+  const std::string p1 = two ? out1 : out;
+  int fd1 = to_stdout ? 1 : -1, fd2 = -1, fdr = -1;
+  // a call that fails leaves no output file behind: what this process created goes again (fq-trim's rule)
+  auto discard = [&]() {
+    auto drop = [](int fd, const std::string& p) {
+      struct stat st;
+      const bool regular = fstat(fd, &st) == 0 && S_ISREG(st.st_mode);
+      close(fd);
+      if (regular) unlink(p.c_str());
+    };
+    if (!to_stdout && fd1 >= 0) drop(fd1, p1);
+    if (fd2 >= 0) drop(fd2, out2);
+    if (fdr >= 0) drop(fdr, per_read);
+    fd1 = fd2 = fdr = -1;
+  };
+  auto create = [&](const std::string& p) -> int {
+    const int fd = open(p.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
+    if (fd < 0) { discard(); quit_error("Unable to create file: " + p, 1); }
+    return fd;
+  };
+  if (!p1.empty()) fd1 = create(p1);
+  if (two && !out2.empty()) fd2 = create(out2);
+  if (!per_read.empty()) fdr = create(per_read);
+  scfq_cplx_stats st = fresh<scfq_cplx_stats>();
+  std::vector<uint64_t> bins(SCFQ_CPLX_SCORE_BINS);
+  std::fflush(stdout);
+  const int rc = scfq_cplx_files(files[0].c_str(), two ? files[1].c_str() : nullptr, nullptr, &co, fd1, fd2, fdr, bins.data(), &st);
+  if (rc != SCFQ_OK && rc != SCFQ_EPIPE) discard();
+  else { if (!to_stdout && fd1 >= 0) close(fd1); if (fd2 >= 0) close(fd2); if (fdr >= 0) close(fdr); }
+  if (rc == SCFQ_EOPEN) quit_unable_to_open(first_unopenable(files[0], two ? &files[1] : nullptr));
+  if (rc == SCFQ_EPIPE) return 0;              // a reader of stdout that went away: quiet, as `sc fq-dedup | head`
+  if (rc != SCFQ_OK) quit_error(library_error(rc, scfq_cplx_error_detail()), 1);
+  FILE* report = to_stdout ? stderr : stdout;
+  if (to_stdout && !stats && !hist) return 0;
+  char row[1024];
+  if (cols.header) {
+    scfq_format_cplx_stats_tsv(nullptr, 1, row, sizeof row);
+    std::fprintf(report, "%s\n", output_header(hist ? kCplxHistHeader : row, cols.basename, cols.absolute).c_str());
+  }
+  if (hist) {
+    for (uint64_t s = 0; s < SCFQ_CPLX_SCORE_BINS; ++s) {
+      if (!bins[s]) continue;
+      if (s + 1 < SCFQ_CPLX_SCORE_BINS) std::snprintf(row, sizeof row, "%llu\t%llu", (unsigned long long)s, (unsigned long long)bins[s]);
+      else std::snprintf(row, sizeof row, "too_long\t%llu", (unsigned long long)bins[s]);
+      std::fprintf(report, "%s\n", cols.row(row, files[0]).c_str());
+    }
+  } else {
+    scfq_format_cplx_stats_tsv(&st, 0, row, sizeof row);
+    std::fprintf(report, "%s\n", cols.row(row, files[0]).c_str());
+  }
+  return 0;
+}
+
 // command "fq-kcount" (addition, not in the reference): -t/--header, -b/--basename, -a/--absolute as fq-count, --k=N, --canonical,
 // --table-bits=N, --high=N, --totals, --dump [--min-count=C] [--max-count=C], --top=N, IN.fq [IN2.fq]
 static const char* kKcountHistHeader = "count\tkmers";
@@ -1628,7 +1750,8 @@ int main(int argc, char** argv) {
       {"fq-readstats", cmd_fq_readstats}, {"fq-cycles", cmd_fq_cycles},   {"fq-kmers", cmd_fq_kmers},
       {"fq-adapters", cmd_fq_adapters}, {"fq-insert-size", cmd_fq_insert_size}, {"fq-merge", cmd_fq_merge},
       {"fq-trim", cmd_fq_trim},         {"fq-screen", cmd_fq_screen},     {"fq-demux", cmd_fq_demux},
-      {"fq-kcount", cmd_fq_kcount},     {"fq-normalize", cmd_fq_normalize}, {"fa-gc", cmd_fa_gc}};
+      {"fq-kcount", cmd_fq_kcount},     {"fq-normalize", cmd_fq_normalize}, {"fq-complexity", cmd_fq_complexity},
+      {"fa-gc", cmd_fa_gc}};
   for (const auto& c : commands)
     if (params[0] == c.name) return c.run(params);
   help_top(stdout);

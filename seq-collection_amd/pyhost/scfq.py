@@ -64,6 +64,8 @@ EXPORTS = [
     "scfq_format_kcount_tsv", "scfq_kcount_error_detail", "scfq_debug_kcount_stages",
     "scfq_norm_buffers", "scfq_norm_files", "scfq_format_norm_row_tsv", "scfq_format_norm_hist_tsv", "scfq_norm_error_detail",
     "scfq_debug_norm_stages",
+    "scfq_cplx_buffers", "scfq_cplx_files", "scfq_format_cplx_stats_tsv", "scfq_format_cplx_rec_tsv", "scfq_cplx_error_detail",
+    "scfq_debug_cplx_stages",
     "scfq_fa_index_buffer", "scfq_fa_index_file", "scfq_fa_contig_at", "scfq_fa_contig_find", "scfq_fa_count_intervals",
     "scfq_fa_index_free", "scfq_fa_error_detail", "scfq_fa_parse_window", "scfq_fa_gc_interval", "scfq_format_fa_gc_value",
     "scfq_debug_fa_stages",
@@ -357,6 +359,33 @@ class NormStats(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in NORM_STATS_FIELDS]
 
 
+SCFQ_CPLX_INTERLEAVED = 0x1
+SCFQ_CPLX_MASK_NONE, SCFQ_CPLX_MASK_LOWER, SCFQ_CPLX_MASK_N = 0, 1, 2
+SCFQ_CPLX_MAX_LEN, SCFQ_CPLX_SCORE_BINS = 512, 312
+CPLX_MASKS = {"none": SCFQ_CPLX_MASK_NONE, "lower": SCFQ_CPLX_MASK_LOWER, "n": SCFQ_CPLX_MASK_N}
+CPLX_PARAM_FIELDS = ("flags", "window", "threshold", "mask", "max_masked_pct")
+CPLX_REC_FIELDS = ("score", "masked", "first", "intervals")
+CPLX_STATS_FIELDS = ("struct_size", "abi_version", "reads1", "reads2", "lines1", "lines2", "input_bytes1", "input_bytes2", "pairs", "unpaired",
+                     "reads_in", "reads_out", "too_long", "low_reads", "dropped_reads", "masked_reads", "perfect_intervals", "bases_in", "bases_out",
+                     "masked_bases", "masked_bases_out", "max_score", "out1_bytes", "out2_bytes") + CPLX_PARAM_FIELDS
+CPLX_REC_DTYPE = [(n, "<u2") for n in CPLX_REC_FIELDS]      # numpy: np.dtype(CPLX_REC_DTYPE), 8 bytes
+
+
+class CplxOpts(ctypes.Structure):
+    """scfq_cplx_opts (40 bytes)"""
+    _fields_ = [("struct_size", ctypes.c_uint64)] + [(n, ctypes.c_uint32) for n in CPLX_PARAM_FIELDS] + [("reserved", ctypes.c_uint32 * 3)]
+
+
+class CplxRec(ctypes.Structure):
+    """scfq_cplx_rec (8 bytes)"""
+    _fields_ = [(n, ctypes.c_uint16) for n in CPLX_REC_FIELDS]
+
+
+class CplxStats(ctypes.Structure):
+    """scfq_cplx_stats (29 uint64)"""
+    _fields_ = [(n, ctypes.c_uint64) for n in CPLX_STATS_FIELDS]
+
+
 FA_SUMMARY_FIELDS = ("struct_size", "abi_version", "input_bytes", "tiles", "contigs", "bases", "gc_bases", "acgt_bases", "orphan_bases")
 
 
@@ -568,6 +597,13 @@ def lib():
         L.scfq_format_norm_hist_tsv.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_uint64]
         L.scfq_norm_error_detail.restype = ctypes.c_char_p
         L.scfq_debug_norm_stages.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]
+        L.scfq_cplx_buffers.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_int, vp, vp, ctypes.c_uint64, vp, vp, ctypes.c_uint64, vp,
+                                        ctypes.c_uint64, ctypes.c_int, vp]
+        L.scfq_cplx_files.argtypes = [ctypes.c_char_p, ctypes.c_char_p, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]
+        L.scfq_format_cplx_stats_tsv.argtypes = [vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_uint64]
+        L.scfq_format_cplx_rec_tsv.argtypes = [ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_uint64]
+        L.scfq_cplx_error_detail.restype = ctypes.c_char_p
+        L.scfq_debug_cplx_stages.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]
         L.scfq_fa_index_buffer.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, pvp, ctypes.POINTER(FaSummary)]
         L.scfq_fa_index_file.argtypes = [ctypes.c_char_p, ctypes.c_void_p, pvp, ctypes.POINTER(FaSummary)]
         L.scfq_fa_contig_at.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(FaContig)]
@@ -1729,6 +1765,94 @@ def norm_stages():
     zeros unless SCFQ_NORM_TIMING=1 is in the environment"""
     ms = (ctypes.c_double * 4)()
     lib().scfq_debug_norm_stages(ms, 4)
+    return list(ms)
+
+
+def cplx_opts(interleaved=False, window=64, threshold=20, mask="lower", max_masked_pct=100, flags=None, reserved=(0, 0, 0)):
+    """scfq_cplx_opts.  mask: "none", "lower", "n" or the number"""
+    o = CplxOpts()
+    o.struct_size = ctypes.sizeof(CplxOpts)
+    o.flags = flags if flags is not None else (SCFQ_CPLX_INTERLEAVED if interleaved else 0)
+    o.window, o.threshold, o.mask, o.max_masked_pct = window, threshold, CPLX_MASKS.get(mask, mask), max_masked_pct
+    for k in range(3):
+        o.reserved[k] = reserved[k]
+    return o
+
+
+def _cplx_call(fn, what, opts, head, tail, hist=True):
+    """Returns (CplxStats, hist): hist a numpy uint64 array of SCFQ_CPLX_SCORE_BINS entries, or None.  An ScfqError carries the stats as
+    `stats` (complete when an output or the per-read table was too small)."""
+    import numpy as np
+    s = CplxStats()
+    s.struct_size = ctypes.sizeof(CplxStats)
+    h = np.zeros(SCFQ_CPLX_SCORE_BINS, dtype=np.uint64) if hist else None
+    rc = fn(*head, ctypes.byref(opts) if opts is not None else None, *tail(h.ctypes.data if hist else None), ctypes.byref(s))
+    if rc != 0:
+        e = ScfqError(rc, what, lib().scfq_cplx_error_detail().decode() or lib().scfq_last_error_detail().decode())
+        e.stats = s
+        raise e
+    return s, h
+
+
+def cplx_resident(ptr1, n1, ptr2=None, n2=0, opts=None, out1=None, out2=None, recs=None, hist=True):
+    """fq-complexity of device-resident FASTQs (the pointer rules of trim_device; not named *_device: tests/_caller_cases.py lists the wrappers
+    of that name, and this one's caller-stream and thread tests are tests/test_gpu_complexity_callers.py's).  out1 / out2: (device address, capacity) or None; recs:
+    (device address, entries) of the per-read table or None.  Returns (CplxStats, hist)."""
+    return _cplx_call(lib().scfq_cplx_buffers, "scfq_cplx_buffers", opts,
+                      [ctypes.c_void_p(ptr1), n1, ctypes.c_void_p(ptr2) if ptr2 is not None else None, n2, 1],
+                      lambda h: [ctypes.c_void_p(recs[0]) if recs else None, recs[1] if recs else 0, h] + _trim_outputs((out1, out2)) + [1], hist)
+
+
+def cplx_host(data1, data2=None, opts=None, caps=None, recs_cap=None, hist=True):
+    """fq-complexity of host buffers; caps as trim_host's; recs_cap: the entries of the per-read table (None: as many as there are reads,
+    0: no table).  Returns (CplxStats, hist, recs, out1, out2): recs a numpy array of CPLX_REC_DTYPE or None, the outputs as bytes or None."""
+    import numpy as np
+    a1, n1, keep1 = _host_ptr(data1)
+    a2, n2, keep2 = _host_ptr(data2) if data2 is not None else (None, 0, None)
+    head = [a1, n1, a2, n2, 0]
+    fn = lib().scfq_cplx_buffers
+    if caps is None or recs_cap is None:
+        s, _ = _cplx_call(fn, "scfq_cplx_buffers", opts, head, lambda h: [None, 0, h, None, 0, None, 0, 0], False)
+        if caps is None:
+            caps = (s.out1_bytes, s.out2_bytes if data2 is not None else None)
+        if recs_cap is None:
+            recs_cap = int(s.reads_in)
+    recs = np.zeros(recs_cap, dtype=np.dtype(CPLX_REC_DTYPE)) if recs_cap else None
+    bufs = [None if c is None else ctypes.create_string_buffer(max(int(c), 1)) for c in caps]
+    outs = [None if b is None else (ctypes.addressof(b), int(c)) for b, c in zip(bufs, caps)]
+    s, h = _cplx_call(fn, "scfq_cplx_buffers", opts, head,
+                      lambda h: [recs.ctypes.data if recs_cap else None, recs_cap, h] + _trim_outputs(outs) + [0], hist)
+    sizes = (s.out1_bytes, s.out2_bytes)
+    return (s, h, recs[:int(s.reads_in)] if recs_cap else None) + tuple(None if b is None else b.raw[:int(k)] for b, k in zip(bufs, sizes))
+
+
+def cplx_files(path1, path2=None, opts=None, out1_fd=-1, out2_fd=-1, per_read_fd=-1, hist=True):
+    """path2 = None: one input.  A descriptor below 0: that output is not produced.  Returns (CplxStats, hist)"""
+    return _cplx_call(lib().scfq_cplx_files, "scfq_cplx_files", opts, [os.fsencode(path1), os.fsencode(path2) if path2 is not None else None, None],
+                      lambda h: [out1_fd, out2_fd, per_read_fd, h], hist)
+
+
+def format_cplx_stats_tsv(s, header=False):
+    buf = ctypes.create_string_buffer(1024)
+    n = lib().scfq_format_cplx_stats_tsv(ctypes.byref(s) if s is not None else None, 1 if header else 0, buf, 1024)
+    if n < 0:
+        raise ScfqError(n, "scfq_format_cplx_stats_tsv")
+    return buf.value.decode()
+
+
+def format_cplx_rec_tsv(read, rec, length):
+    """rec: None (the column names), a CplxRec or a (score, masked, first, intervals) tuple"""
+    buf = ctypes.create_string_buffer(160)
+    r = rec if rec is None or isinstance(rec, CplxRec) else CplxRec(*[int(v) for v in rec])
+    lib().scfq_format_cplx_rec_tsv(read, ctypes.byref(r) if r is not None else None, length, buf, 160)
+    return buf.value.decode()
+
+
+def cplx_stages():
+    """(line indexes, D1, D2 with its scans, D3) milliseconds of this thread's last fq-complexity call; the last three are HIP-event times,
+    zeros unless SCFQ_CPLX_TIMING=1 is in the environment"""
+    ms = (ctypes.c_double * 4)()
+    lib().scfq_debug_cplx_stages(ms, 4)
     return list(ms)
 
 
