@@ -1287,6 +1287,94 @@ int scfq_format_cplx_stats_tsv(const scfq_cplx_stats* s, int header, char* buf, 
 int scfq_format_cplx_rec_tsv(uint64_t read, const scfq_cplx_rec* r, uint64_t length, char* buf, uint64_t cap);
 const char* scfq_cplx_error_detail(void);        /* static, thread-local */
 
+/* ---- `sc fq-rmdup` (addition; not in the reference): duplicate reads and pairs removed by SEQUENCE --------------------
+ * (scfq_dedup_* above is the reference's fq-dedup: it drops records whose HEADER repeats. This one finds two reads of the
+ * same molecule, which carry different names.)
+ * Inputs, lines, records, texts, pairing (`pairs`, `unpaired`) and interleaving are fq-trim's, word for word. A UNIT is a
+ * read (single-end input) or a pair; units_in is reads1, or pairs.
+ * No length limit. There is no too_long: a sequence text of any length is hashed and compared, in loops over its words.
+ * Key of a read with sequence text S of L bytes: the bytes S[0, min(L, prefix)) together with that length. prefix is 0 (the
+ *  whole text, the default) or 1 .. 65535. The comparison is byte-exact: 'N', lower case and anything else are bytes like any
+ *  other, so two reads that fq-complexity soft-masked alike stay equal. An empty text is a key like any other.
+ * Equality of units. Single-end: equal keys. Paired: key1 = key1' and key2 = key2'; with SCFQ_RMDUP_SWAPPED also
+ *  (key1 = key2' and key2 = key1'): the same fragment read from the other strand. Both relations are equivalences (the
+ *  second compares unordered pairs of keys). The flag with single-end input is SCFQ_EARG with text.
+ * Classes. The REPRESENTATIVE of a class is its unit with the smallest index in input order; every other member is a
+ *  DUPLICATE and is not written. The kept units are echoed in input order exactly as fq-screen echoes a kept unit: each line
+ *  the record has, as text plus '\n'. Two inputs give out1 / out2, interleaved input one output (mate 1, then mate 2). Units
+ *  counted in `unpaired` go nowhere.
+ * Per-unit table: scfq_rmdup_rec, 8 bytes per unit. rep: the index of the representative (the unit's own index when it is
+ *  kept); copies: the class size for a representative, 0 for a duplicate.
+ * Histogram: SCFQ_RMDUP_HIST_BINS words. Bin c, 1 <= c <= 1023: the classes of size c; bin 1024: the classes of size >= 1024;
+ *  bin 0 is 0. The bins add up to units_out.
+ * collisions and rounds are the only two values that depend on the hash: collisions is the number of (unit, round)
+ *  comparisons that found a unit different from the head of its equal-hash run, rounds the number of compare rounds that had
+ *  a candidate. No other field and no output byte depends on the hash or on hash_bits.
+ * All values are integers and exact. Device pipeline: line index (K5); U1 — eight lanes per unit hash its keys in 8-byte
+ *  words; a radix sort of (hash, unit); per round U2 — run starts, the head of every run by a max-scan, the candidates
+ *  compacted — and U3 — eight lanes per candidate compare it with the HEAD of its run, the unequal ones form the next
+ *  round's list in sorted order —; the class sizes; U4 — a thread per unit: the table, output lengths per group of 32, the
+ *  statistics and the histogram —, one exclusive scan per output, U5 — a wave per group echoes the kept records. */
+#define SCFQ_RMDUP_INTERLEAVED  0x1u
+#define SCFQ_RMDUP_SWAPPED      0x2u
+#define SCFQ_RMDUP_HIST_BINS    1025
+#define SCFQ_RMDUP_MAX_PREFIX   65535
+typedef struct scfq_rmdup_opts {
+  uint64_t struct_size;   /* sizeof(scfq_rmdup_opts) */
+  uint32_t flags;         /* SCFQ_RMDUP_INTERLEAVED | SCFQ_RMDUP_SWAPPED */
+  uint32_t prefix;        /* 0: the whole text; 1 .. SCFQ_RMDUP_MAX_PREFIX */
+  uint32_t hash_bits;     /* 0: the library's default (40); 1 .. 64: the bits of the hash that are sorted. Fewer bits make
+                             equal-hash runs of different units (the tests force collisions with it); no result but
+                             `collisions` and `rounds` depends on it */
+  uint32_t reserved[3];   /* 0 */
+} scfq_rmdup_opts;
+typedef struct scfq_rmdup_rec {    /* the per-unit table: 8 bytes per unit */
+  uint32_t rep;           /* the unit's representative */
+  uint32_t copies;        /* a representative: the size of its class; a duplicate: 0 */
+} scfq_rmdup_rec;
+typedef struct scfq_rmdup_stats {  /* 26 x 8 bytes */
+  uint64_t struct_size;   /* caller sets to sizeof(scfq_rmdup_stats) before the call */
+  uint64_t abi_version;   /* library writes SCFQ_ABI_VERSION */
+  uint64_t reads1, reads2;             /* as scfq_trim_stats, down to `unpaired` */
+  uint64_t lines1, lines2;
+  uint64_t input_bytes1, input_bytes2;
+  uint64_t pairs, unpaired;
+  uint64_t units_in, units_out;        /* units_in: reads1, or pairs; units_out: the classes */
+  uint64_t reads_in, reads_out;        /* reads1, or 2 * pairs; the reads of the kept units */
+  uint64_t duplicate_units;            /* units_in - units_out */
+  uint64_t duplicated_classes;         /* classes with copies >= 2 */
+  uint64_t max_copies;                 /* the largest class; 0 without units */
+  uint64_t bases_in, bases_out;        /* sums of L over reads_in and reads_out */
+  uint64_t collisions, rounds;         /* the two that depend on the hash (above) */
+  uint64_t out1_bytes, out2_bytes;     /* sizes of the outputs, written or not */
+  uint64_t flags, prefix, hash_bits;   /* the parameters as used (hash_bits: 40 for 0) */
+} scfq_rmdup_stats;
+
+/* r1 / r2, the outputs, the sizing call, a too-small output (SCFQ_EARG naming it, stats complete, NO byte written to ANY
+ * output: U5 compares the scanned totals with the capacities before it stores) and the device-pointer rules are those of
+ * scfq_trim_buffers. recs: NULL, or memory of the outputs' kind (host with out_is_device = 0, device otherwise) for
+ * recs_cap entries of the per-unit table; fewer than units_in is SCFQ_EARG with text: stats is complete and nothing is
+ * written to the table or to an output. hist_host: NULL, or HOST memory for SCFQ_RMDUP_HIST_BINS words. SCFQ_EARG with
+ * text in scfq_rmdup_error_detail(), before any HIP call: unknown flag bits, prefix or hash_bits out of range, reserved not
+ * 0, SCFQ_RMDUP_SWAPPED with single-end input, out2 without a second input, a second buffer with SCFQ_RMDUP_INTERLEAVED;
+ * without text: a NULL stats or a wrong struct_size (stats' or opts'), a NULL pointer with a size or capacity. opts = NULL:
+ * the defaults. Fewer than 2^31 records per input. There is no CPU fallback (SCFQ_EHIP without a device). */
+int scfq_rmdup_buffers(const void* r1, uint64_t n1, const void* r2, uint64_t n2, int is_device, const scfq_rmdup_opts* opts,
+                       scfq_rmdup_rec* recs, uint64_t recs_cap, uint64_t* hist_host, void* out1, uint64_t cap1, void* out2,
+                       uint64_t cap2, int out_is_device, scfq_rmdup_stats* stats);
+/* As scfq_trim_files: staged inputs, descriptors below 0 are not produced, out1 then out2, SCFQ_EPIPE / SCFQ_EIO.
+ * per_read_fd >= 0: the per-unit table as rows of scfq_format_rmdup_rec_tsv, each with a '\n', written before the outputs. */
+int scfq_rmdup_files(const char* path1, const char* path2, const scfq_rmdup_opts* opts, const scfq_opts* ropts, int out1_fd,
+                     int out2_fd, int per_read_fd, uint64_t* hist_host, scfq_rmdup_stats* stats);
+/* The one-row report without trailing newline; header != 0: the names of its columns instead. The columns: units_in units_out
+ * duplicate_units duplicate_pct duplicated_classes max_copies reads_in reads_out pairs unpaired bases_in bases_out out1_bytes
+ * out2_bytes. duplicate_pct is floor(10000 * duplicate_units / units_in) printed as X.YY ("0.00" for no units), in integers
+ * only. Returns the number of bytes needed (excluding NUL); writes at most cap bytes incl. NUL. */
+int scfq_format_rmdup_stats_tsv(const scfq_rmdup_stats* s, int header, char* buf, uint64_t cap);
+/* "<unit>\t<rep>\t<copies>" without trailing newline; rec = NULL: the names of the columns. The same return rule. */
+int scfq_format_rmdup_rec_tsv(uint64_t unit, const scfq_rmdup_rec* rec, char* buf, uint64_t cap);
+const char* scfq_rmdup_error_detail(void);       /* static, thread-local */
+
 /* ---- `sc fa-gc` (FASTA group): src/fa_gc.nim, docs/fa-gc.md, sc.nim:84-96 --------------------------------------------
  * GC content of the windows [pos - w, pos + w] around 1-based positions of a FASTA. The contract:
  *   Lines.   A header line is a line whose first byte is '>' (a line that starts at byte 0 of the input included); every

@@ -128,6 +128,11 @@ int scfq_debug_norm_stages(double* ms, uint32_t cap);
  * kernel — the last three HIP-event times, taken only while SCFQ_CPLX_TIMING=1 is in the environment (zeros otherwise). Writes
  * min(cap, 4) values, returns 4. */
 int scfq_debug_cplx_stages(double* ms, uint32_t cap);
+/* Stage times of the calling thread's last scfq_rmdup_buffers / scfq_rmdup_files, in milliseconds: ms[0] the line indexes of
+ * paired input (host clock, 0 for single-end input), ms[1] U1, the key hash, ms[2] the radix sort, ms[3] the rounds of U2 + U3,
+ * ms[4] the class sizes, ms[5] U4 with its scans, ms[6] U5, the write kernel — the last six HIP-event times, taken only while
+ * SCFQ_RMDUP_TIMING=1 is in the environment (zeros otherwise). Writes min(cap, 7) values, returns 7. */
+int scfq_debug_rmdup_stages(double* ms, uint32_t cap);
 /* Stage times of the calling thread's last scfq_fa_index_buffer / scfq_fa_index_file, in milliseconds: ms[0] F1, the tile scan,
  * ms[1] F2, the scan over the tile records, ms[2] F3, the contig table's kernel, ms[3] unused (0) — HIP-event times, taken only
  * while SCFQ_FA_TIMING=1 is in the environment (zeros otherwise). Writes min(cap, 4) values, returns 4. */

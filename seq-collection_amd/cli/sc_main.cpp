@@ -1198,6 +1198,118 @@ static int cmd_fq_complexity(const std::vector<std::string>& params) {
   return 0;
 }
 
+// command "fq-rmdup" (addition, not in the reference): IN.fq, R1.fq R2.fq with --out1=PATH --out2=PATH (or neither: the report only), or
+// --interleaved IN.fq; --prefix=N, --swapped, --report, --stats, --hist, --per-read=PATH, --out=PATH, -t/--header, -b/--basename,
+// -a/--absolute.  The forms and output rules are fq-complexity's: the report goes to stdout, or to stderr while stdout carries the reads.
+static const char* kRmdupHistHeader = "copies\tclasses\tunits";
+static int cmd_fq_rmdup(const std::vector<std::string>& params) {
+  static const char* const help =
+      "Remove duplicate reads and pairs by sequence: of the units with the same sequence text(s) the first in input order is kept\n\n"
+      "Usage:\n  fq-rmdup [options] IN.fq > out.fq\n  fq-rmdup [options] --out1=PATH --out2=PATH R1.fq R2.fq\n"
+      "  fq-rmdup [options] --interleaved IN.fq > out.fq\n\n"
+      "Arguments:\n  IN.fq            One FASTQ: single-end reads, or pairs with --interleaved; the kept reads go to stdout or to --out=PATH\n"
+      "  R1.fq R2.fq      Two FASTQs: record i of each is pair i; without --out1 and --out2 only the report is produced\n\nOptions:\n"
+      "      --prefix=N             Compare the first N bytes of every sequence, 1 .. 65535 (default: 0, the whole sequence)\n"
+      "      --swapped              Pairs: (a, b) and (b, a) are duplicates too, the same fragment read from the other strand\n"
+      "      --interleaved          The one argument is an interleaved FASTQ: records 2i and 2i+1 are pair i\n"
+      "      --out=PATH             With one FASTQ: the kept reads, or pairs, go to PATH and the report to stdout\n"
+      "      --out1=PATH            With R1.fq R2.fq: mate 1 of the kept pairs goes to PATH\n"
+      "      --out2=PATH            With R1.fq R2.fq: mate 2 of the kept pairs goes to PATH\n"
+      "      --report               No reads are written: the one-row report on stdout\n"
+      "      --stats                While stdout carries the reads: the report row to stderr\n"
+      "      --hist                 Instead of the report row the table \"copies classes units\"; the classes of 1024 and more in a last row\n"
+      "      --per-read=PATH        One row per read, or pair, to PATH: unit rep copies\n"
+      "  -t, --header               Output the header\n  -b, --basename             Add a column with the basename of the first FASTQ\n"
+      "  -a, --absolute             Add a column with the absolute path of the first FASTQ\n"
+      "  -h, --help                 Show this help\n";
+  Columns cols;
+  scfq_rmdup_opts co = fresh<scfq_rmdup_opts>();
+  bool stats = false, hist = false, report_only = false;
+  std::vector<std::string> files;
+  std::string out, out1, out2, per_read;
+  const std::vector<Opt> table = cols.options({
+      opt_number("prefix", 6, 0, SCFQ_RMDUP_MAX_PREFIX, &co.prefix),
+      opt_bits("swapped", &co.flags, SCFQ_RMDUP_SWAPPED),
+      opt_bits("interleaved", &co.flags, SCFQ_RMDUP_INTERLEAVED),
+      opt_text("out", &out),
+      opt_text("out1", &out1),
+      opt_text("out2", &out2),
+      opt_flag("report", 0, &report_only),
+      opt_flag("stats", 0, &stats),
+      opt_flag("hist", 0, &hist),
+      opt_text("per-read", &per_read),
+  });
+  if (!parse_options(params, help, table, &files)) return 0;
+  const bool interleaved = co.flags & SCFQ_RMDUP_INTERLEAVED;
+  if (files.empty()) quit_no_fastq();
+  if (files.size() > 2 || (interleaved && files.size() != 1)) usage_error(help, "fq-rmdup takes one FASTQ, R1.fq and R2.fq, or one FASTQ with --interleaved");
+  const bool two = files.size() == 2;
+  if ((co.flags & SCFQ_RMDUP_SWAPPED) && !two && !interleaved) usage_error(help, "--swapped compares the mates of pairs: it goes with R1.fq R2.fq or --interleaved");
+  if (two && !out.empty()) usage_error(help, "R1.fq R2.fq write to --out1=PATH and --out2=PATH");
+  if (two && out1.empty() != out2.empty()) usage_error(help, "--out1=PATH and --out2=PATH go together");
+  if (!two && (!out1.empty() || !out2.empty())) usage_error(help, "--out1=PATH and --out2=PATH go with R1.fq R2.fq; one input is written to stdout or to --out=PATH");
+  if (report_only && (!out.empty() || !out1.empty())) usage_error(help, "--report writes no reads: it goes without --out, --out1 and --out2");
+  for (const std::string& f : files) require_suffix_room(f);
+  // the inputs are looked at before an output file is made
+  for (const std::string& f : files)
+    if (access(f.c_str(), R_OK) != 0) quit_unable_to_open(f);
+  const bool to_stdout = !two && out.empty() && !report_only;      // stdout carries the reads: the report goes to stderr
+  const std::string p1 = two ? out1 : out;
+  int fd1 = to_stdout ? 1 : -1, fd2 = -1, fdr = -1;
+  // a call that fails leaves no output file behind: what this process created goes again (fq-trim's rule)
+  auto discard = [&]() {
+    auto drop = [](int fd, const std::string& p) {
+      struct stat st;
+      const bool regular = fstat(fd, &st) == 0 && S_ISREG(st.st_mode);
+      close(fd);
+      if (regular) unlink(p.c_str());
+    };
+    if (!to_stdout && fd1 >= 0) drop(fd1, p1);
+    if (fd2 >= 0) drop(fd2, out2);
+    if (fdr >= 0) drop(fdr, per_read);
+    fd1 = fd2 = fdr = -1;
+  };
+  auto create = [&](const std::string& p) -> int {
+    const int fd = open(p.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
+    if (fd < 0) { discard(); quit_error("Unable to create file: " + p, 1); }
+    return fd;
+  };
+  if (!p1.empty()) fd1 = create(p1);
+  if (two && !out2.empty()) fd2 = create(out2);
+  if (!per_read.empty()) fdr = create(per_read);
+  scfq_rmdup_stats st = fresh<scfq_rmdup_stats>();
+  std::vector<uint64_t> bins(SCFQ_RMDUP_HIST_BINS);
+  std::fflush(stdout);
+  const int rc = scfq_rmdup_files(files[0].c_str(), two ? files[1].c_str() : nullptr, &co, nullptr, fd1, fd2, fdr, bins.data(), &st);
+  if (rc != SCFQ_OK && rc != SCFQ_EPIPE) discard();
+  else { if (!to_stdout && fd1 >= 0) close(fd1); if (fd2 >= 0) close(fd2); if (fdr >= 0) close(fdr); }
+  if (rc == SCFQ_EOPEN) quit_unable_to_open(first_unopenable(files[0], two ? &files[1] : nullptr));
+  if (rc == SCFQ_EPIPE) return 0;              // a reader of stdout that went away: quiet, as `sc fq-dedup | head`
+  if (rc != SCFQ_OK) quit_error(library_error(rc, scfq_rmdup_error_detail()), 1);
+  FILE* report = to_stdout ? stderr : stdout;
+  if (to_stdout && !stats && !hist) return 0;
+  char row[1024];
+  if (cols.header) {
+    scfq_format_rmdup_stats_tsv(nullptr, 1, row, sizeof row);
+    std::fprintf(report, "%s\n", output_header(hist ? kRmdupHistHeader : row, cols.basename, cols.absolute).c_str());
+  }
+  if (hist) {
+    // the units of the last bin are what the other bins leave of units_in
+    uint64_t below = 0;
+    for (uint64_t c = 1; c + 1 < SCFQ_RMDUP_HIST_BINS; ++c) below += c * bins[c];
+    for (uint64_t c = 1; c < SCFQ_RMDUP_HIST_BINS; ++c) {
+      if (!bins[c]) continue;
+      if (c + 1 < SCFQ_RMDUP_HIST_BINS) std::snprintf(row, sizeof row, "%llu\t%llu\t%llu", (unsigned long long)c, (unsigned long long)bins[c], (unsigned long long)(c * bins[c]));
+      else std::snprintf(row, sizeof row, "1024+\t%llu\t%llu", (unsigned long long)bins[c], (unsigned long long)(st.units_in - below));
+      std::fprintf(report, "%s\n", cols.row(row, files[0]).c_str());
+    }
+  } else {
+    scfq_format_rmdup_stats_tsv(&st, 0, row, sizeof row);
+    std::fprintf(report, "%s\n", cols.row(row, files[0]).c_str());
+  }
+  return 0;
+}
+
 // command "fq-kcount" (addition, not in the reference): -t/--header, -b/--basename, -a/--absolute as fq-count, --k=N, --canonical,
 // --table-bits=N, --high=N, --totals, --dump [--min-count=C] [--max-count=C], --top=N, IN.fq [IN2.fq]
 static const char* kKcountHistHeader = "count\tkmers";
@@ -1751,6 +1863,7 @@ int main(int argc, char** argv) {
       {"fq-adapters", cmd_fq_adapters}, {"fq-insert-size", cmd_fq_insert_size}, {"fq-merge", cmd_fq_merge},
       {"fq-trim", cmd_fq_trim},         {"fq-screen", cmd_fq_screen},     {"fq-demux", cmd_fq_demux},
       {"fq-kcount", cmd_fq_kcount},     {"fq-normalize", cmd_fq_normalize}, {"fq-complexity", cmd_fq_complexity},
+      {"fq-rmdup", cmd_fq_rmdup},
       {"fa-gc", cmd_fa_gc}};
   for (const auto& c : commands)
     if (params[0] == c.name) return c.run(params);

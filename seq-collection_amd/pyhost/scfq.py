@@ -66,6 +66,8 @@ EXPORTS = [
     "scfq_debug_norm_stages",
     "scfq_cplx_buffers", "scfq_cplx_files", "scfq_format_cplx_stats_tsv", "scfq_format_cplx_rec_tsv", "scfq_cplx_error_detail",
     "scfq_debug_cplx_stages",
+    "scfq_rmdup_buffers", "scfq_rmdup_files", "scfq_format_rmdup_stats_tsv", "scfq_format_rmdup_rec_tsv", "scfq_rmdup_error_detail",
+    "scfq_debug_rmdup_stages",
     "scfq_fa_index_buffer", "scfq_fa_index_file", "scfq_fa_contig_at", "scfq_fa_contig_find", "scfq_fa_count_intervals",
     "scfq_fa_index_free", "scfq_fa_error_detail", "scfq_fa_parse_window", "scfq_fa_gc_interval", "scfq_format_fa_gc_value",
     "scfq_debug_fa_stages",
@@ -386,6 +388,31 @@ class CplxStats(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in CPLX_STATS_FIELDS]
 
 
+SCFQ_RMDUP_INTERLEAVED, SCFQ_RMDUP_SWAPPED = 0x1, 0x2
+SCFQ_RMDUP_HIST_BINS, SCFQ_RMDUP_MAX_PREFIX = 1025, 65535
+RMDUP_PARAM_FIELDS = ("flags", "prefix", "hash_bits")
+RMDUP_REC_FIELDS = ("rep", "copies")
+RMDUP_STATS_FIELDS = ("struct_size", "abi_version", "reads1", "reads2", "lines1", "lines2", "input_bytes1", "input_bytes2", "pairs", "unpaired",
+                      "units_in", "units_out", "reads_in", "reads_out", "duplicate_units", "duplicated_classes", "max_copies", "bases_in", "bases_out",
+                      "collisions", "rounds", "out1_bytes", "out2_bytes") + RMDUP_PARAM_FIELDS
+RMDUP_REC_DTYPE = [(n, "<u4") for n in RMDUP_REC_FIELDS]      # numpy: np.dtype(RMDUP_REC_DTYPE), 8 bytes
+
+
+class RmdupOpts(ctypes.Structure):
+    """scfq_rmdup_opts (32 bytes)"""
+    _fields_ = [("struct_size", ctypes.c_uint64)] + [(n, ctypes.c_uint32) for n in RMDUP_PARAM_FIELDS] + [("reserved", ctypes.c_uint32 * 3)]
+
+
+class RmdupRec(ctypes.Structure):
+    """scfq_rmdup_rec (8 bytes)"""
+    _fields_ = [(n, ctypes.c_uint32) for n in RMDUP_REC_FIELDS]
+
+
+class RmdupStats(ctypes.Structure):
+    """scfq_rmdup_stats (26 uint64)"""
+    _fields_ = [(n, ctypes.c_uint64) for n in RMDUP_STATS_FIELDS]
+
+
 FA_SUMMARY_FIELDS = ("struct_size", "abi_version", "input_bytes", "tiles", "contigs", "bases", "gc_bases", "acgt_bases", "orphan_bases")
 
 
@@ -604,6 +631,13 @@ def lib():
         L.scfq_format_cplx_rec_tsv.argtypes = [ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_uint64]
         L.scfq_cplx_error_detail.restype = ctypes.c_char_p
         L.scfq_debug_cplx_stages.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]
+        L.scfq_rmdup_buffers.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_int, vp, vp, ctypes.c_uint64, vp, vp, ctypes.c_uint64, vp,
+                                         ctypes.c_uint64, ctypes.c_int, vp]
+        L.scfq_rmdup_files.argtypes = [ctypes.c_char_p, ctypes.c_char_p, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]
+        L.scfq_format_rmdup_stats_tsv.argtypes = [vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_uint64]
+        L.scfq_format_rmdup_rec_tsv.argtypes = [ctypes.c_uint64, vp, ctypes.c_char_p, ctypes.c_uint64]
+        L.scfq_rmdup_error_detail.restype = ctypes.c_char_p
+        L.scfq_debug_rmdup_stages.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]
         L.scfq_fa_index_buffer.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, pvp, ctypes.POINTER(FaSummary)]
         L.scfq_fa_index_file.argtypes = [ctypes.c_char_p, ctypes.c_void_p, pvp, ctypes.POINTER(FaSummary)]
         L.scfq_fa_contig_at.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(FaContig)]
@@ -1853,6 +1887,100 @@ def cplx_stages():
     zeros unless SCFQ_CPLX_TIMING=1 is in the environment"""
     ms = (ctypes.c_double * 4)()
     lib().scfq_debug_cplx_stages(ms, 4)
+    return list(ms)
+
+
+def rmdup_opts(interleaved=False, swapped=False, prefix=0, hash_bits=0, flags=None, reserved=(0, 0, 0)):
+    """scfq_rmdup_opts.  prefix: 0 (the whole sequence text) or the bytes of it that are compared; hash_bits: 0 (the library's default) or the
+    bits of the hash that are sorted"""
+    o = RmdupOpts()
+    o.struct_size = ctypes.sizeof(RmdupOpts)
+    o.flags = flags if flags is not None else ((SCFQ_RMDUP_INTERLEAVED if interleaved else 0) | (SCFQ_RMDUP_SWAPPED if swapped else 0))
+    o.prefix, o.hash_bits = prefix, hash_bits
+    for k in range(3):
+        o.reserved[k] = reserved[k]
+    return o
+
+
+def _rmdup_call(fn, what, head, tail, hist=True):
+    """Returns (RmdupStats, hist): hist a numpy uint64 array of SCFQ_RMDUP_HIST_BINS entries, or None.  An ScfqError carries the stats as
+    `stats` (complete when an output or the per-unit table was too small)."""
+    import numpy as np
+    s = RmdupStats()
+    s.struct_size = ctypes.sizeof(RmdupStats)
+    h = np.zeros(SCFQ_RMDUP_HIST_BINS, dtype=np.uint64) if hist else None
+    rc = fn(*head, *tail(h.ctypes.data if hist else None), ctypes.byref(s))
+    if rc != 0:
+        e = ScfqError(rc, what, lib().scfq_rmdup_error_detail().decode() or lib().scfq_last_error_detail().decode())
+        e.stats = s
+        raise e
+    return s, h
+
+
+def _opts_ref(opts):
+    return ctypes.byref(opts) if opts is not None else None
+
+
+def rmdup_resident(ptr1, n1, ptr2=None, n2=0, opts=None, out1=None, out2=None, recs=None, hist=True):
+    """fq-rmdup of device-resident FASTQs (the pointer rules of trim_device; not named *_device: tests/_caller_cases.py lists the wrappers
+    of that name, and this one's caller-stream and thread tests are tests/test_gpu_rmdup_callers.py's).  out1 / out2: (device address,
+    capacity) or None; recs: (device address, entries) of the per-unit table or None.  Returns (RmdupStats, hist)."""
+    return _rmdup_call(lib().scfq_rmdup_buffers, "scfq_rmdup_buffers",
+                       [ctypes.c_void_p(ptr1), n1, ctypes.c_void_p(ptr2) if ptr2 is not None else None, n2, 1, _opts_ref(opts)],
+                       lambda h: [ctypes.c_void_p(recs[0]) if recs else None, recs[1] if recs else 0, h] + _trim_outputs((out1, out2)) + [1], hist)
+
+
+def rmdup_host(data1, data2=None, opts=None, caps=None, recs_cap=None, hist=True):
+    """fq-rmdup of host buffers; caps as trim_host's; recs_cap: the entries of the per-unit table (None: as many as there are units,
+    0: no table).  Returns (RmdupStats, hist, recs, out1, out2): recs a numpy array of RMDUP_REC_DTYPE or None, the outputs as bytes or None."""
+    import numpy as np
+    a1, n1, keep1 = _host_ptr(data1)
+    a2, n2, keep2 = _host_ptr(data2) if data2 is not None else (None, 0, None)
+    head = [a1, n1, a2, n2, 0, _opts_ref(opts)]
+    fn = lib().scfq_rmdup_buffers
+    if caps is None or recs_cap is None:
+        s, _ = _rmdup_call(fn, "scfq_rmdup_buffers", head, lambda h: [None, 0, h, None, 0, None, 0, 0], False)
+        if caps is None:
+            caps = (s.out1_bytes, s.out2_bytes if data2 is not None else None)
+        if recs_cap is None:
+            recs_cap = int(s.units_in)
+    recs = np.zeros(recs_cap, dtype=np.dtype(RMDUP_REC_DTYPE)) if recs_cap else None
+    bufs = [None if c is None else ctypes.create_string_buffer(max(int(c), 1)) for c in caps]
+    outs = [None if b is None else (ctypes.addressof(b), int(c)) for b, c in zip(bufs, caps)]
+    s, h = _rmdup_call(fn, "scfq_rmdup_buffers", head,
+                       lambda h: [recs.ctypes.data if recs_cap else None, recs_cap, h] + _trim_outputs(outs) + [0], hist)
+    sizes = (s.out1_bytes, s.out2_bytes)
+    return (s, h, recs[:int(s.units_in)] if recs_cap else None) + tuple(None if b is None else b.raw[:int(k)] for b, k in zip(bufs, sizes))
+
+
+def rmdup_files(path1, path2=None, opts=None, out1_fd=-1, out2_fd=-1, per_read_fd=-1, hist=True):
+    """path2 = None: one input.  A descriptor below 0: that output is not produced.  Returns (RmdupStats, hist)"""
+    return _rmdup_call(lib().scfq_rmdup_files, "scfq_rmdup_files",
+                       [os.fsencode(path1), os.fsencode(path2) if path2 is not None else None, _opts_ref(opts), None],
+                       lambda h: [out1_fd, out2_fd, per_read_fd, h], hist)
+
+
+def format_rmdup_stats_tsv(s, header=False):
+    buf = ctypes.create_string_buffer(1024)
+    n = lib().scfq_format_rmdup_stats_tsv(ctypes.byref(s) if s is not None else None, 1 if header else 0, buf, 1024)
+    if n < 0:
+        raise ScfqError(n, "scfq_format_rmdup_stats_tsv")
+    return buf.value.decode()
+
+
+def format_rmdup_rec_tsv(unit, rec):
+    """rec: None (the column names), an RmdupRec or a (rep, copies) tuple"""
+    buf = ctypes.create_string_buffer(96)
+    r = rec if rec is None or isinstance(rec, RmdupRec) else RmdupRec(*[int(v) for v in rec])
+    lib().scfq_format_rmdup_rec_tsv(unit, ctypes.byref(r) if r is not None else None, buf, 96)
+    return buf.value.decode()
+
+
+def rmdup_stages():
+    """(line indexes, U1, sort, U2 + U3 rounds, class sizes, U4 with its scans, U5) milliseconds of this thread's last fq-rmdup call; all but
+    the first are HIP-event times, zeros unless SCFQ_RMDUP_TIMING=1 is in the environment"""
+    ms = (ctypes.c_double * 7)()
+    lib().scfq_debug_rmdup_stages(ms, 7)
     return list(ms)
 
 
