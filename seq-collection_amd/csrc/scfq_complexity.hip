@@ -28,7 +28,6 @@
 //                             by the lanes, a byte each under the read's mask words.
 // D3 compares the two totals with the capacities before it stores anything: a result that does not fit leaves both outputs alone.
 // D2 and D3 get a record's lengths from the same function (read_of).  Everything is integer / byte work; there is no CPU fallback.
-// (text_span, echo_len and echo_record repeat scfq_trim.hip's: sharing them would change that file, whose kernels stay as they are.)
 #include "../../include/sc_fqcount.h"
 #include "../../include/sc_fqcount_debug.h"
 
@@ -36,10 +35,7 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
-#include "scfq_fdwrite.hpp"
-#include "scfq_overlap.hpp"
-#include "scfq_record_device.hpp"
-#include "scfq_scratch.hpp"
+#include "scfq_reads_host.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -54,31 +50,21 @@ namespace {
 thread_local char g_cerr[scfq_scratch::kErrBytes] = "";
 thread_local double g_stage_ms[4] = {0, 0, 0, 0};
 
-using scfq_scratch::DevBuf;
+using scfq_reads::Dest;
+using scfq_reads::DevBuf;
+using scfq_reads::finish;
+using scfq_reads::Mode;
 
 constexpr uint32_t kCxWaves = 4;                         // reads a block of D1 works on at a time; groups of a block of D3
 constexpr uint32_t kCxMaxBlocks = 4096;                  // of D1
 constexpr uint32_t kCxWords = SCFQ_CPLX_MAX_LEN / 64;    // mask words of a read
-constexpr uint32_t kCxGroup = 32;                        // reads or pairs of a group: one wave of D3, one entry of the scans
+constexpr uint32_t kCxGroup = kRecGroup;                 // reads or pairs of a group: one wave of D3, one entry of the scans
 constexpr uint32_t kCxPad = 64;                          // invalid codes in front of position 0: j - d never leaves the array
 constexpr uint16_t kNoFirst = 0xFFFF, kScoreTooLong = 0xFFFF;
 static_assert(SCFQ_CPLX_MAX_LEN == 512 && kCxWords == 8, "a position is 9 bits, the mask words of a read are kept by lanes 0 .. 7");
 
 // the counters of D2; the histogram follows them
 enum { kTooLong = 0, kLow, kDropped, kMaskedReads, kIntervals, kBasesIn, kBasesOut, kMaskedBases, kMaskedBasesOut, kMaxScore, kCounters };
-
-struct CxInput {          // one input: the bytes and their line index
-  const uint8_t* base;
-  uint64_t n;
-  const uint64_t* line_off;
-  uint64_t lines;
-  bool has_cr;
-};
-
-struct CxOut {            // one output: where it goes (nullptr: nowhere) and what it holds
-  uint8_t* p;
-  uint64_t cap;
-};
 
 struct CxSteps { uint32_t window, threshold, mask, max_masked_pct; };
 
@@ -89,12 +75,6 @@ struct CxWave {
   uint16_t reach[SCFQ_CPLX_MAX_LEN];           // per start: its furthest perfect end + 3, or 0
   uint8_t code[kCxPad + SCFQ_CPLX_MAX_LEN];    // t(i) at kCxPad + i, 0xFF for a triplet that is not valid
 };
-
-// the text of line j (a line the input does not have is empty)
-__device__ __forceinline__ void text_span(const CxInput& in, uint64_t j, uint64_t& s, uint64_t& e) {
-  s = e = 0;
-  if (j < in.lines) line_span(in.base, in.n, in.line_off, j, s, e, in.has_cr);
-}
 
 // the 2-bit code of a base in bits 0 and 1; bit 7 for a byte that is not exactly A C G T (bits 1 and 2 of 'A' 'C' 'T' 'G' are 0 1 2 3)
 __device__ __forceinline__ uint32_t base_code(uint32_t b) {
@@ -116,7 +96,7 @@ constexpr uint32_t kFrZero = 1u;      // 0 / 1
 
 // D1.  Read r is record r of `a` (single-end: paired = 0) or mate r & 1 of pair r >> 1: record p * stride of a, record p * stride + second
 // of b.  maskw: kCxWords words per read.
-__global__ __launch_bounds__(64 * kCxWaves) void cx_score(CxInput a, CxInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t reads,
+__global__ __launch_bounds__(64 * kCxWaves) void cx_score(RecInput a, RecInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t reads,
                                                          CxSteps st, scfq_cplx_rec* recs, uint64_t* maskw) {
   __shared__ CxWave lds[kCxWaves];
   const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -130,7 +110,7 @@ __global__ __launch_bounds__(64 * kCxWaves) void cx_score(CxInput a, CxInput b, 
     if (r >= reads) continue;
     const uint64_t p = paired ? r >> 1 : r;
     const bool mate2 = paired && (r & 1);
-    const CxInput& in = mate2 ? b : a;
+    const RecInput& in = mate2 ? b : a;
     const uint64_t i = paired ? p * stride + (mate2 ? second : 0) : r;
     uint64_t ss, se;
     text_span(in, 4 * i + 1, ss, se);
@@ -218,37 +198,6 @@ __global__ __launch_bounds__(64 * kCxWaves) void cx_score(CxInput a, CxInput b, 
   }
 }
 
-// bytes record i echoes: its lines 4i .. min(4i+3, lines-1), each text + '\n' (dd_record_lengths' rule)
-__device__ __forceinline__ uint64_t echo_len(const CxInput& in, uint64_t i) {
-  if (4 * i >= in.lines) return 0;
-  if (!in.has_cr) {
-    const uint64_t j1 = (4 * i + 4 < in.lines) ? 4 * i + 4 : in.lines;
-    return in.line_off[j1] - in.line_off[4 * i];
-  }
-  uint64_t total = 0;
-  for (uint64_t j = 4 * i; j < 4 * i + 4 && j < in.lines; ++j) {
-    uint64_t s, e;
-    line_span(in.base, in.n, in.line_off, j, s, e);
-    total += e - s + 1;
-  }
-  return total;
-}
-
-// record i of `in` echoed to dst, len bytes (dd_gather's rule: one copy when the echo is the record's own bytes)
-__device__ __forceinline__ void echo_record(const CxInput& in, uint64_t i, uint8_t* dst, uint64_t len, uint32_t lane) {
-  const uint64_t j0 = 4 * i, j1 = (j0 + 4 < in.lines) ? j0 + 4 : in.lines;
-  const uint64_t r0 = in.line_off[j0], r1 = in.line_off[j1];
-  if (r1 - r0 == len && r1 <= in.n) { wave_copy(dst, in.base + r0, len, lane); return; }
-  uint64_t w = 0;
-  for (uint64_t j = j0; j < j1; ++j) {
-    uint64_t s, e;
-    line_span(in.base, in.n, in.line_off, j, s, e);
-    for (uint64_t k = lane; k < e - s; k += 64) dst[w + k] = in.base[s + k];
-    if (lane == 0) dst[w + (e - s)] = '\n';
-    w += e - s + 1;
-  }
-}
-
 // what a read adds to its output if it is kept and where its pieces lie.  D2 and D3 both get it from here, so the lengths the scans saw
 // are the lengths D3 writes
 enum : uint32_t { kPieces = 0, kCopy, kEcho };
@@ -260,7 +209,7 @@ struct CxRead {
   uint32_t kind;                       // kPieces: the four pieces; kCopy: len bytes from hs on; kEcho: a too-long read
 };
 
-__device__ __forceinline__ CxRead read_of(const CxInput& in, uint64_t i, uint64_t idx, const scfq_cplx_rec& rec, uint32_t mask_mode, uint64_t& seq_len) {
+__device__ __forceinline__ CxRead read_of(const RecInput& in, uint64_t i, uint64_t idx, const scfq_cplx_rec& rec, uint32_t mask_mode, uint64_t& seq_len) {
   CxRead r = {};
   uint64_t e;
   r.idx = idx;
@@ -288,7 +237,7 @@ __device__ __forceinline__ CxRead read_of(const CxInput& in, uint64_t i, uint64_
 }
 
 // a kept read's record, by the whole wave
-__device__ __forceinline__ void write_read(const CxInput& in, uint64_t i, const CxRead& r, const uint64_t* maskw, uint32_t mask_mode, uint8_t* dst, uint32_t lane) {
+__device__ __forceinline__ void write_read(const RecInput& in, uint64_t i, const CxRead& r, const uint64_t* maskw, uint32_t mask_mode, uint8_t* dst, uint32_t lane) {
   if (r.kind == kEcho) { echo_record(in, i, dst, r.len, lane); return; }
   if (r.kind == kCopy) { wave_copy(dst, in.base + r.hs, r.len, lane); return; }
   uint8_t* const s = dst + r.hl + 1;
@@ -324,7 +273,7 @@ struct CxUnit {
   bool low[2], dropped;
 };
 
-__device__ __forceinline__ CxUnit look_up(const CxInput& a, const CxInput& b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t u,
+__device__ __forceinline__ CxUnit look_up(const RecInput& a, const RecInput& b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t u,
                                           const scfq_cplx_rec* recs, const CxSteps& st) {
   CxUnit t = {};
   t.mates = paired ? 2u : 1u;
@@ -345,18 +294,11 @@ __device__ __forceinline__ CxUnit look_up(const CxInput& a, const CxInput& b, ui
   return t;
 }
 
-__device__ __forceinline__ uint64_t half_sum(uint64_t v) {      // over the 32 lanes of a half wave
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor((unsigned long long)v, o, 64);
-  return v;
-}
-
 // D2.  group_len: two arrays of n_groups + 1 entries, one after the other (the last entry of each stays 0: the scan's total).  counters:
 // kCounters words, then the SCFQ_CPLX_SCORE_BINS of the histogram.  lens: L of every read, for the per-read rows of the file form
-__global__ __launch_bounds__(256) void cx_lengths(CxInput a, CxInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t units,
+__global__ __launch_bounds__(256) void cx_lengths(RecInput a, RecInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t units,
                                                  const scfq_cplx_rec* recs, CxSteps st, uint64_t n_groups, uint64_t* group_len, uint32_t* lens,
                                                  unsigned long long* counters) {
-  static_assert(kCxGroup == 32, "the sums below run over the two halves of a wave");
   __shared__ uint64_t sum_sh[kCounters][4];
   __shared__ uint32_t hist_sh[SCFQ_CPLX_SCORE_BINS];
   for (uint32_t k = threadIdx.x; k < SCFQ_CPLX_SCORE_BINS; k += 256) hist_sh[k] = 0;
@@ -389,10 +331,7 @@ __global__ __launch_bounds__(256) void cx_lengths(CxInput a, CxInput b, uint64_t
     }
   }
 #pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const uint64_t s = half_sum(len[k]);
-    if ((threadIdx.x & 31) == 0 && u < units) group_len[(uint64_t)k * (n_groups + 1) + u / kCxGroup] = s;
-  }
+  for (int k = 0; k < 2; ++k) store_group_len(len[k], k, u, units, n_groups, group_len);
   // the statistics: ONE atomic per block and counter (dd_count_marks: an atomic per wave on one address costs more than the kernel)
 #pragma unroll
   for (int k = 0; k < kCounters; ++k) {
@@ -414,9 +353,7 @@ __global__ __launch_bounds__(256) void cx_lengths(CxInput a, CxInput b, uint64_t
     if (hist_sh[k]) atomicAdd(&counters[kCounters + k], (unsigned long long)hist_sh[k]);
 }
 
-__device__ __forceinline__ uint64_t bcast(uint64_t v, uint32_t from) { return (uint64_t)__shfl((unsigned long long)v, (int)from, 64); }
-__device__ __forceinline__ uint32_t bcast(uint32_t v, uint32_t from) { return (uint32_t)__shfl((int)v, (int)from, 64); }
-
+using ::bcast;      // (the overload below hides the shared ones otherwise)
 __device__ __forceinline__ CxRead bcast(const CxRead& m, uint32_t from) {
   CxRead r;
   r.len = bcast(m.len, from);
@@ -428,31 +365,23 @@ __device__ __forceinline__ CxRead bcast(const CxRead& m, uint32_t from) {
 }
 
 // D3.  group_off: the two scanned arrays of D2's layout
-__global__ __launch_bounds__(64 * kCxWaves) void cx_write(CxInput a, CxInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t units,
+__global__ __launch_bounds__(64 * kCxWaves) void cx_write(RecInput a, RecInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t units,
                                                          const scfq_cplx_rec* recs, const uint64_t* maskw, CxSteps st, uint64_t n_groups,
-                                                         const uint64_t* group_off, CxOut o1, CxOut o2) {
+                                                         const uint64_t* group_off, RecOut o1, RecOut o2) {
   const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const uint64_t* off_1 = group_off;
-  const uint64_t* off_2 = group_off + (n_groups + 1);
-  // (each scan's last entry is its output's size: when one is more than its output holds, nothing is written to either)
-  const bool fits = (!o1.p || off_1[n_groups] <= o1.cap) && (!o2.p || off_2[n_groups] <= o2.cap);
-  if (!fits) return;
+  // (when one result is more than its output holds, nothing is written to either)
+  if (!(output_fits(o1, 0, n_groups, group_off) && output_fits(o2, 1, n_groups, group_off))) return;
   const uint64_t g = (uint64_t)blockIdx.x * kCxWaves + wave;
   if (g >= n_groups) return;
   const uint64_t u0 = g * kCxGroup;
   const uint32_t count = (uint32_t)std::min<uint64_t>(kCxGroup, units - u0);
   CxUnit mine = {};
   if (lane < count) mine = look_up(a, b, stride, second, paired, u0 + lane, recs, st);
-  // where the unit of this lane goes: the group's offsets and the lengths of the units in front of it
-  uint64_t at_1 = mine.len1, at_2 = mine.len2;
-#pragma unroll
-  for (int o = 1; o < (int)kCxGroup; o <<= 1) {
-    const uint64_t v1 = __shfl_up((unsigned long long)at_1, o, 64), v2 = __shfl_up((unsigned long long)at_2, o, 64);
-    if (lane >= (uint32_t)o) { at_1 += v1; at_2 += v2; }
-  }
-  at_1 += off_1[g] - mine.len1; at_2 += off_2[g] - mine.len2;
+  const uint64_t len[2] = {mine.len1, mine.len2};
+  uint64_t at[2];
+  place_units(len, g, n_groups, group_off, lane, at);
   for (uint32_t q = 0; q < count; ++q) {
-    const uint64_t l1 = bcast(mine.len1, q), l2 = bcast(mine.len2, q), first = bcast(mine.first, q), w1 = bcast(at_1, q), w2 = bcast(at_2, q);
+    const uint64_t l1 = bcast(mine.len1, q), l2 = bcast(mine.len2, q), first = bcast(mine.first, q), w1 = bcast(at[0], q), w2 = bcast(at[1], q);
     if (l1 + l2 == 0) continue;                            // (a dropped unit; a kept record has its four '\n' at the least, or is an echo of nothing)
     const uint64_t u = u0 + q;
     const uint64_t i1 = paired ? u * stride : u, i2 = u * stride + second;
@@ -494,13 +423,6 @@ bool args_ok(const scfq_cplx_opts* opts, const scfq_cplx_stats* st, Params& p) {
   return true;
 }
 
-enum class Mode { single, two, interleaved };
-
-// one output of a call: `want` it, and then the caller's device memory (p, cap) or, with own_outputs, pool memory that cplx_device
-// takes by the size the scan reports (own[k]; cap is then the caller's host capacity, checked here all the same)
-struct Dest { uint8_t* p; uint64_t cap; bool want; };
-const char* const kDestName[2] = {"out1", "out2"};
-
 // recs_dev / recs_cap: the caller's per-read table in device memory, or nullptr; want_recs with check_recs: a table of recs_cap entries is
 // wanted wherever it lives, and one that is too small is an error once the statistics are complete.  recs_keep, lens_keep: where the
 // table and the lengths stay for the caller of this function.  hist_host: nullptr, or SCFQ_CPLX_SCORE_BINS words
@@ -517,42 +439,28 @@ int cplx_device(const uint8_t* d1, uint64_t n1, const uint8_t* d2, uint64_t n2, 
   scfq_overlap::Indexed ix;
   int rc = SCFQ_OK;
   double index_ms = 0;
-  if (paired) {
-    rc = scfq_overlap::index_inputs(d1, n1, d2, n2, interleaved, stream, g_cerr, ix, &index_ms);
-  } else {
-    // single-end input: K5 directly
-    if ((rc = scfq_scratch::build_line_index(d1, n1, stream, g_cerr, ix.off1, &ix.lines1, &ix.cr1))) return rc;
-    ix.reads1 = (ix.lines1 + 3) / 4;
-    if (ix.reads1 >= (1ull << 31)) { std::snprintf(g_cerr, sizeof g_cerr, "more than 2^31 records in one input"); rc = SCFQ_EARG; }
-  }
-  st->lines1 = ix.lines1; st->lines2 = ix.lines2;
-  st->reads1 = ix.reads1; st->reads2 = ix.reads2;
-  if (rc) return rc;
-  st->pairs = ix.pairs;
-  st->unpaired = ix.unpaired;
-  const uint64_t units = paired ? ix.pairs : ix.reads1, reads = paired ? 2 * ix.pairs : ix.reads1;
+  uint64_t units = 0, reads = 0;
+  if ((rc = scfq_reads::index_units(d1, n1, d2, n2, mode, stream, g_cerr, ix, &index_ms, st, &units, &reads))) return rc;
   st->reads_in = reads;
   const bool recs_small = check_recs && want_recs && recs_cap < reads;
   if (units == 0) return SCFQ_OK;           // (two empty outputs: they fit into anything)
-  const uint64_t n_groups = (units + kCxGroup - 1) / kCxGroup, row = n_groups + 1;
+  const uint64_t n_groups = (units + kCxGroup - 1) / kCxGroup;
   const bool to_caller = recs_dev && !recs_small;
   constexpr size_t kWordsOut = kCounters + SCFQ_CPLX_SCORE_BINS;
   DevBuf maskw, group_len, group_off, counters, tmp;
+  scfq_reads::GroupScan gs(2, n_groups, group_len, group_off, stream, g_cerr);
   if ((!to_caller && (rc = recs_keep.alloc(reads * sizeof(scfq_cplx_rec), stream, g_cerr))) || (rc = lens_keep.alloc(reads * 4, stream, g_cerr)) ||
-      (rc = maskw.alloc(reads * kCxWords * 8, stream, g_cerr)) || (rc = group_len.alloc(2 * row * 8, stream, g_cerr)) ||
-      (rc = group_off.alloc(2 * row * 8, stream, g_cerr)) || (rc = counters.alloc(kWordsOut * 8, stream, g_cerr)))
+      (rc = maskw.alloc(reads * kCxWords * 8, stream, g_cerr)) || (rc = gs.alloc()) || (rc = counters.alloc(kWordsOut * 8, stream, g_cerr)))
     return rc;
   scfq_cplx_rec* const recs = to_caller ? recs_dev : recs_keep.as<scfq_cplx_rec>();
   size_t scan_bytes = 0;
-  SCFQ_SCRATCH_CHK(g_cerr, rocprim::exclusive_scan(nullptr, scan_bytes, group_len.as<uint64_t>(), group_off.as<uint64_t>(), (uint64_t)0, (size_t)row,
-                                                   rocprim::plus<uint64_t>(), stream));
-  if ((rc = tmp.alloc(scan_bytes, stream, g_cerr))) return rc;
+  if ((rc = gs.scratch_bytes(&scan_bytes)) || (rc = tmp.alloc(scan_bytes, stream, g_cerr))) return rc;
   static const bool timing = scfq_scratch::env_switch("SCFQ_CPLX_TIMING");
   scfq_scratch::StageClock clk(stream, timing);
   SCFQ_SCRATCH_CHK(g_cerr, hipMemsetAsync(counters.p, 0, kWordsOut * 8, stream));
-  SCFQ_SCRATCH_CHK(g_cerr, hipMemsetAsync(group_len.p, 0, 2 * row * 8, stream));       // (each scan's last input: its last output is the total)
-  const CxInput a = {d1, n1, ix.off1.as<uint64_t>(), ix.lines1, ix.cr1};
-  const CxInput b = mode == Mode::two ? CxInput{d2, n2, ix.off2.as<uint64_t>(), ix.lines2, ix.cr2} : a;
+  if ((rc = gs.zero())) return rc;
+  const RecInput a = {d1, n1, ix.off1.as<uint64_t>(), ix.lines1, ix.cr1};
+  const RecInput b = mode == Mode::two ? RecInput{d2, n2, ix.off2.as<uint64_t>(), ix.lines2, ix.cr2} : a;
   const uint64_t stride = interleaved ? 2 : 1, second = interleaved ? 1 : 0;
   clk.mark(0);
   hipLaunchKernelGGL(cx_score, dim3((unsigned)std::min<uint64_t>((reads + kCxWaves - 1) / kCxWaves, kCxMaxBlocks)), dim3(64 * kCxWaves), 0, stream, a, b, stride,
@@ -560,40 +468,27 @@ int cplx_device(const uint8_t* d1, uint64_t n1, const uint8_t* d2, uint64_t n2, 
   SCFQ_SCRATCH_CHK(g_cerr, hipGetLastError());
   clk.mark(1);
   hipLaunchKernelGGL(cx_lengths, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, stream, a, b, stride, second, paired ? 1u : 0u, units, recs, prm.steps,
-                     n_groups, group_len.as<uint64_t>(), lens_keep.as<uint32_t>(), counters.as<unsigned long long>());
+                     n_groups, gs.len(), lens_keep.as<uint32_t>(), counters.as<unsigned long long>());
   SCFQ_SCRATCH_CHK(g_cerr, hipGetLastError());
-  for (uint64_t k = 0; k < 2; ++k)
-    SCFQ_SCRATCH_CHK(g_cerr, rocprim::exclusive_scan(tmp.p, scan_bytes, group_len.as<uint64_t>() + k * row, group_off.as<uint64_t>() + k * row, (uint64_t)0, (size_t)row,
-                                                     rocprim::plus<uint64_t>(), stream));
+  if ((rc = gs.scan(tmp.p, scan_bytes))) return rc;
   clk.mark(2);
   // the sizes and the statistics come back first: pool memory for the outputs is taken to fit, and a caller's buffer that is too small
   // is known here
-  uint64_t total[2] = {0, 0};
   std::vector<uint64_t> h(kWordsOut);
-  for (uint64_t k = 0; k < 2; ++k) SCFQ_SCRATCH_CHK(g_cerr, hipMemcpyAsync(&total[k], group_off.as<uint64_t>() + k * row + n_groups, 8, hipMemcpyDeviceToHost, stream));
+  if ((rc = gs.read_totals())) return rc;
   SCFQ_SCRATCH_CHK(g_cerr, hipMemcpyAsync(h.data(), counters.p, kWordsOut * 8, hipMemcpyDeviceToHost, stream));
   SCFQ_SCRATCH_CHK(g_cerr, hipStreamSynchronize(stream));
-  st->out1_bytes = total[0]; st->out2_bytes = total[1];
+  st->out1_bytes = gs.total[0]; st->out2_bytes = gs.total[1];
   st->too_long = h[kTooLong]; st->low_reads = h[kLow]; st->dropped_reads = h[kDropped]; st->reads_out = reads - h[kDropped];
   st->masked_reads = h[kMaskedReads]; st->perfect_intervals = h[kIntervals];
   st->bases_in = h[kBasesIn]; st->bases_out = h[kBasesOut]; st->masked_bases = h[kMaskedBases]; st->masked_bases_out = h[kMaskedBasesOut];
   st->max_score = h[kMaxScore];
   if (hist_host) std::memcpy(hist_host, h.data() + kCounters, SCFQ_CPLX_SCORE_BINS * 8);
-  int small = -1;
-  for (int k = 1; k >= 0; --k)
-    if (check_caps && dst[k].want && total[k] > dst[k].cap) small = k;
-  CxOut out[2];
-  for (int k = 0; k < 2; ++k) {
-    out[k] = CxOut{nullptr, 0};
-    if (!dst[k].want || recs_small) continue;
-    if (!own_outputs) { out[k] = CxOut{dst[k].p, dst[k].cap}; continue; }      // (too small or not: D3 looks at the totals itself)
-    if (small >= 0 || total[k] == 0) continue;
-    if ((rc = own[k].alloc(total[k], stream, g_cerr))) return rc;
-    out[k] = CxOut{own[k].as<uint8_t>(), total[k]};
-  }
-  if (out[0].p || out[1].p) {
+  const scfq_reads::Placement put = scfq_reads::place_outputs(gs, scfq_reads::kOutNames, dst, own_outputs, check_caps, recs_small, own, stream, g_cerr);
+  if (put.rc) return put.rc;
+  if (put.out[0].p || put.out[1].p) {
     hipLaunchKernelGGL(cx_write, dim3((unsigned)((n_groups + kCxWaves - 1) / kCxWaves)), dim3(64 * kCxWaves), 0, stream, a, b, stride, second, paired ? 1u : 0u,
-                       units, recs, maskw.as<uint64_t>(), prm.steps, n_groups, group_off.as<uint64_t>(), out[0], out[1]);
+                       units, recs, maskw.as<uint64_t>(), prm.steps, n_groups, gs.off(), put.out[0], put.out[1]);
     SCFQ_SCRATCH_CHK(g_cerr, hipGetLastError());
   }
   clk.mark(3);
@@ -606,28 +501,7 @@ int cplx_device(const uint8_t* d1, uint64_t n1, const uint8_t* d2, uint64_t n2, 
     std::snprintf(g_cerr, sizeof g_cerr, "the per-read table holds %llu entries, the input has %llu reads", (unsigned long long)recs_cap, (unsigned long long)reads);
     return SCFQ_EARG;
   }
-  if (small >= 0) {
-    std::snprintf(g_cerr, sizeof g_cerr, "the %s output holds %llu bytes, the result has %llu", kDestName[small], (unsigned long long)dst[small].cap,
-                  (unsigned long long)total[small]);
-    return SCFQ_EARG;
-  }
-  return SCFQ_OK;
-}
-
-// after a failure kernels that read the second input may still be queued on the first one's stream: they are waited for before the
-// second input's memory goes back (as fq-merge's)
-int finish(scfq_scratch::ResidentInput& in1, int rc) {
-  if (rc != SCFQ_OK) (void)hipStreamSynchronize(in1.stream);
-  return rc;
-}
-
-int copy_text(const char* text, int m, char* buf, uint64_t cap) {
-  if (buf && cap) {
-    const uint64_t ncopy = ((uint64_t)m < cap - 1) ? (uint64_t)m : cap - 1;
-    std::memcpy(buf, text, ncopy);
-    buf[ncopy] = 0;
-  }
-  return m;
+  return put.verdict;      // (SCFQ_EARG for an output that is too small: place_outputs has left the text)
 }
 
 }  // namespace
@@ -641,25 +515,25 @@ int scfq_debug_cplx_stages(double* ms, uint32_t cap) { return scfq_scratch::copy
 int scfq_format_cplx_stats_tsv(const scfq_cplx_stats* s, int header, char* buf, uint64_t cap) {
   static const char kNames[] = "reads_in\treads_out\tdropped_reads\tlow_reads\ttoo_long\tpairs\tunpaired\tmasked_reads\tperfect_intervals\tbases_in\tbases_out\t"
                                "masked_bases\tmasked_bases_out\tmax_score\tout1_bytes\tout2_bytes";
-  if (header) return copy_text(kNames, (int)sizeof kNames - 1, buf, cap);
+  if (header) return scfq_reads::copy_text(kNames, (int)sizeof kNames - 1, buf, cap);
   if (!s) return SCFQ_EARG;
   const uint64_t v[] = {s->reads_in, s->reads_out, s->dropped_reads, s->low_reads, s->too_long, s->pairs, s->unpaired, s->masked_reads, s->perfect_intervals,
                         s->bases_in, s->bases_out, s->masked_bases, s->masked_bases_out, s->max_score, s->out1_bytes, s->out2_bytes};
   char tmp[512];
   int m = 0;
   for (const uint64_t x : v) m += std::snprintf(tmp + m, sizeof tmp - m, m ? "\t%llu" : "%llu", (unsigned long long)x);
-  return copy_text(tmp, m, buf, cap);
+  return scfq_reads::copy_text(tmp, m, buf, cap);
 }
 
 int scfq_format_cplx_rec_tsv(uint64_t read, const scfq_cplx_rec* r, uint64_t length, char* buf, uint64_t cap) {
   static const char kNames[] = "read\tlength\tscore\tmasked\tfirst\tintervals";
-  if (!r) return copy_text(kNames, (int)sizeof kNames - 1, buf, cap);
+  if (!r) return scfq_reads::copy_text(kNames, (int)sizeof kNames - 1, buf, cap);
   char tmp[160], score[16] = "-", first[16] = "-";
   if (r->score != kScoreTooLong) std::snprintf(score, sizeof score, "%u", (unsigned)r->score);
   if (r->first != kNoFirst) std::snprintf(first, sizeof first, "%u", (unsigned)r->first);
   const int m = std::snprintf(tmp, sizeof tmp, "%llu\t%llu\t%s\t%u\t%s\t%u", (unsigned long long)read, (unsigned long long)length, score, (unsigned)r->masked, first,
                               (unsigned)r->intervals);
-  return copy_text(tmp, m, buf, cap);
+  return scfq_reads::copy_text(tmp, m, buf, cap);
 }
 
 int scfq_cplx_buffers(const void* r1, uint64_t n1, const void* r2, uint64_t n2, int is_device, const scfq_cplx_opts* opts, scfq_cplx_rec* recs, uint64_t recs_cap,
@@ -686,8 +560,8 @@ int scfq_cplx_buffers(const void* r1, uint64_t n1, const void* r2, uint64_t n2, 
   if (recs && !recs_on_device && stats->reads_in)
     SCFQ_SCRATCH_CHK(g_cerr, hipMemcpyAsync(recs, recs_keep.p, stats->reads_in * sizeof(scfq_cplx_rec), hipMemcpyDeviceToHost, in1.stream));
   if (!direct) {
-    for (int k = 0; k < 2; ++k)
-      if (own[k].p) SCFQ_SCRATCH_CHK(g_cerr, hipMemcpyAsync(dst[k].p, own[k].p, k == 0 ? stats->out1_bytes : stats->out2_bytes, hipMemcpyDeviceToHost, in1.stream));
+    const uint64_t bytes[2] = {stats->out1_bytes, stats->out2_bytes};
+    if ((rc = scfq_reads::outputs_to_host(2, dst, own, bytes, in1.stream, g_cerr))) return rc;
   }
   SCFQ_SCRATCH_CHK(g_cerr, hipStreamSynchronize(in1.stream));
   for (DevBuf& o : own) o.drop();
@@ -737,14 +611,8 @@ int scfq_cplx_files(const char* path1, const char* path2, const scfq_opts* opts,
       }
     }
   }
-  if (!own[0].p && !own[1].p) { in1.mark_clean(); return SCFQ_OK; }
-  // one output after the other, each in full: HBM -> two pinned buffers -> write()
-  scfq_fdwrite::Pinned pinned;
-  if ((rc = pinned.init(g_cerr))) return finish(in1, rc);
   const uint64_t bytes[2] = {stats->out1_bytes, stats->out2_bytes};
-  for (int k = 0; k < 2; ++k)
-    if (own[k].p && (rc = pinned.device_to_fd(own[k].as<uint8_t>(), bytes[k], fd[k], in1.stream, g_cerr))) return finish(in1, rc);
-  return SCFQ_OK;
+  return scfq_reads::outputs_to_fds(2, own, bytes, fd, in1, g_cerr);
 }
 
 }  // extern "C"

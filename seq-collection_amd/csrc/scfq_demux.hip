@@ -21,8 +21,7 @@
 //                               needs '\n' put right its four pieces
 // Guards: a unit number read from the sorted array is compared with `units` before it is used, a sample number read from the
 // per-unit table with N; every loop runs over a line's span, a barcode's 32 bytes or the N samples; nothing waits for another
-// wave.  The host compares the scanned totals with the capacities and launches X3 only when everything fits.  No CPU fallback.
-// (text_span and the four-piece writer repeat scfq_trim.hip's: sharing them would change that file, whose kernels stay as they are.)
+// wave.  X3 compares the scanned totals with the capacities before it stores anything.  No CPU fallback.
 #include "../../include/sc_fqcount.h"
 #include "../../include/sc_fqcount_debug.h"
 
@@ -31,10 +30,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "scfq_demux_host.hpp"
-#include "scfq_fdwrite.hpp"
-#include "scfq_overlap.hpp"
-#include "scfq_record_device.hpp"
-#include "scfq_scratch.hpp"
+#include "scfq_reads_host.hpp"
 
 #include <fcntl.h>
 #include <sys/stat.h>
@@ -57,36 +53,20 @@ namespace {
 thread_local char g_xerr[scfq_scratch::kErrBytes] = "";
 thread_local double g_stage_ms[4] = {0, 0, 0, 0};
 
-using scfq_scratch::DevBuf;
+using scfq_reads::Dest;
+using scfq_reads::DevBuf;
+using scfq_reads::finish;
+using scfq_reads::Mode;
 
-constexpr uint32_t kDxGroup = 32;                        // sorted positions of a group: one wave of X3, one entry of the scans
+constexpr uint32_t kDxGroup = kRecGroup;                 // sorted positions of a group: one wave of X3, one entry of the scans
 constexpr uint32_t kDxWaves = 4;                         // groups of a block of X3
 constexpr uint64_t kPairMask = 0x5555555555555555ull;
-
-struct DxInput {          // one input: the bytes and their line index
-  const uint8_t* base;
-  uint64_t n;
-  const uint64_t* line_off;
-  uint64_t lines;
-  bool has_cr;
-};
-
-struct DxOut {            // one output: where it goes (nullptr: nowhere) and what it holds
-  uint8_t* p;
-  uint64_t cap;
-};
 
 struct DxSheet {          // the sheet on the device
   const uint64_t* codes;  // 2 words per sample
   const uint32_t* lens;   // m1 | m2 << 8
   uint32_t n;
 };
-
-// the text of line j (a line the input does not have is empty)
-__device__ __forceinline__ void text_span(const DxInput& in, uint64_t j, uint64_t& s, uint64_t& e) {
-  s = e = 0;
-  if (j < in.lines) line_span(in.base, in.n, in.line_off, j, s, e, in.has_cr);
-}
 
 // the first min(32, e - s) bytes of [s, e): byte i's code at bits 2i and 2i + 1 of `code`, bit 2i of `bad` set iff the byte is not
 // exactly A, C, G or T (the plane of such bytes, spread to where the folded XOR has its bits)
@@ -119,7 +99,7 @@ enum { kPerfect = 0, kMismatched, kUnmatched, kAmbiguous, kNoBarcode, kKinds };
 
 // X1.  Unit u is record u of `a` (single-end: paired = 0) or the pair of record u * stride of a and record u * stride + second of b.
 // header = 1: the candidates come from a's header line.  max_mm: M
-__global__ __launch_bounds__(256) void dx_assign(DxInput a, DxInput b, uint64_t stride, uint64_t second, uint32_t paired, uint32_t header, uint64_t units,
+__global__ __launch_bounds__(256) void dx_assign(RecInput a, RecInput b, uint64_t stride, uint64_t second, uint32_t paired, uint32_t header, uint64_t units,
                                                 const uint64_t* __restrict__ codes, const uint32_t* __restrict__ lens, uint32_t n_samples, uint32_t max_mm,
                                                 scfq_demux_rec* __restrict__ recs, uint16_t* __restrict__ keys, uint32_t* __restrict__ idx,
                                                 unsigned long long* __restrict__ counters) {
@@ -207,7 +187,7 @@ struct DxRead {
 enum : uint32_t { kPieces = 0, kWhole, kRuns };
 
 // record i of `in` with the first `clip` bases and qualities left out; seq_len: L
-__device__ __forceinline__ DxRead read_of(const DxInput& in, uint64_t i, uint64_t clip, uint64_t& seq_len) {
+__device__ __forceinline__ DxRead read_of(const RecInput& in, uint64_t i, uint64_t clip, uint64_t& seq_len) {
   DxRead r = {};
   uint64_t e;
   text_span(in, 4 * i + 1, r.ss, e);
@@ -233,7 +213,7 @@ __device__ __forceinline__ DxRead read_of(const DxInput& in, uint64_t i, uint64_
 }
 
 // a record, by the whole wave: len bytes at dst
-__device__ __forceinline__ void write_read(const DxInput& in, const DxRead& r, uint8_t* dst, uint32_t lane) {
+__device__ __forceinline__ void write_read(const RecInput& in, const DxRead& r, uint8_t* dst, uint32_t lane) {
   if (r.kind == kWhole) { wave_copy(dst, in.base + r.hs, r.len, lane); return; }
   uint8_t* const s = dst + r.hl + 1;
   uint8_t* const p = s + r.sl + 1;
@@ -265,7 +245,7 @@ struct DxUnit {
 };
 
 // clip_on: inline mode without SCFQ_DEMUX_KEEP_BARCODE
-__device__ __forceinline__ DxUnit look_up(const DxInput& a, const DxInput& b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t u,
+__device__ __forceinline__ DxUnit look_up(const RecInput& a, const RecInput& b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t u,
                                           const scfq_demux_rec* recs, const DxSheet& sh, uint32_t clip_on) {
   DxUnit t = {};
   const scfq_demux_rec rec = recs[u];
@@ -281,22 +261,15 @@ __device__ __forceinline__ DxUnit look_up(const DxInput& a, const DxInput& b, ui
   return t;
 }
 
-__device__ __forceinline__ uint64_t half_sum(uint64_t v) {      // over the 32 lanes of a half wave
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor((unsigned long long)v, o, 64);
-  return v;
-}
-
 // a destination's sums on the device: kRowWords words per destination, and two words behind the N + 1 rows
 enum { kRowUnits = 0, kRowPerfect, kRowMismatched, kRowBases, kRowBytes1, kRowBytes2, kRowWords };
 enum { kBasesIn = 0, kBasesClipped, kTotals };
 
 // X2.  order: the sorted unit numbers.  group_len: two arrays of n_groups + 1 entries, one after the other (the last entry of each
 // stays 0: the scan's total).  rows: (N + 1) * kRowWords words, then kTotals
-__global__ __launch_bounds__(256) void dx_lengths(DxInput a, DxInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t units, const uint32_t* order,
+__global__ __launch_bounds__(256) void dx_lengths(RecInput a, RecInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t units, const uint32_t* order,
                                                  const scfq_demux_rec* recs, DxSheet sh, uint32_t clip_on, uint64_t n_groups, uint64_t* group_len,
                                                  unsigned long long* rows) {
-  static_assert(kDxGroup == 32, "the sums below run over the two halves of a wave");
   __shared__ unsigned long long total_sh[kTotals];
   if (threadIdx.x < kTotals) total_sh[threadIdx.x] = 0;
   __syncthreads();
@@ -320,10 +293,7 @@ __global__ __launch_bounds__(256) void dx_lengths(DxInput a, DxInput b, uint64_t
     c[kRowBytes2] = t.len2;
   }
 #pragma unroll
-  for (int x = 0; x < 2; ++x) {
-    const uint64_t s = half_sum(len[x]);
-    if ((threadIdx.x & 31) == 0 && p < units) group_len[(uint64_t)x * (n_groups + 1) + p / kDxGroup] = s;
-  }
+  for (int x = 0; x < 2; ++x) store_group_len(len[x], x, p, units, n_groups, group_len);
   // the rows.  A wave's positions are neighbours in sorted order and nearly always have one destination: then the wave sums first and
   // its first lane adds once per word.  Where destinations meet, every lane adds for itself (dest <= N by look_up)
   const uint32_t lane = threadIdx.x & 63u;
@@ -347,9 +317,7 @@ __global__ __launch_bounds__(256) void dx_lengths(DxInput a, DxInput b, uint64_t
   if (threadIdx.x < kTotals && total_sh[threadIdx.x]) atomicAdd(&rows[(uint64_t)(sh.n + 1) * kRowWords + threadIdx.x], total_sh[threadIdx.x]);
 }
 
-__device__ __forceinline__ uint64_t bcast(uint64_t v, uint32_t from) { return (uint64_t)__shfl((unsigned long long)v, (int)from, 64); }
-__device__ __forceinline__ uint32_t bcast(uint32_t v, uint32_t from) { return (uint32_t)__shfl((int)v, (int)from, 64); }
-
+using ::bcast;      // (the overload below hides the shared ones otherwise)
 __device__ __forceinline__ DxRead bcast(const DxRead& m, uint32_t from) {
   DxRead r;
   r.len = bcast(m.len, from);
@@ -359,16 +327,13 @@ __device__ __forceinline__ DxRead bcast(const DxRead& m, uint32_t from) {
   return r;
 }
 
-// X3.  group_off: the two scanned arrays of X2's layout.  The host has compared their last entries with the capacities
-__global__ __launch_bounds__(64 * kDxWaves) void dx_write(DxInput a, DxInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t units,
+// X3.  group_off: the two scanned arrays of X2's layout
+__global__ __launch_bounds__(64 * kDxWaves) void dx_write(RecInput a, RecInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t units,
                                                          const uint32_t* order, const scfq_demux_rec* recs, DxSheet sh, uint32_t clip_on, uint64_t n_groups,
-                                                         const uint64_t* group_off, DxOut o1, DxOut o2) {
+                                                         const uint64_t* group_off, RecOut o1, RecOut o2) {
   const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const uint64_t* off_1 = group_off;
-  const uint64_t* off_2 = group_off + (n_groups + 1);
-  // (each scan's last entry is its output's size: when one is more than its output holds, nothing is written to either)
-  const bool fits = (!o1.p || off_1[n_groups] <= o1.cap) && (!o2.p || off_2[n_groups] <= o2.cap);
-  if (!fits) return;
+  // (when one result is more than its output holds, nothing is written to either)
+  if (!(output_fits(o1, 0, n_groups, group_off) && output_fits(o2, 1, n_groups, group_off))) return;
   const uint64_t g = (uint64_t)blockIdx.x * kDxWaves + wave;
   if (g >= n_groups) return;
   const uint64_t p0 = g * kDxGroup;
@@ -377,16 +342,11 @@ __global__ __launch_bounds__(64 * kDxWaves) void dx_write(DxInput a, DxInput b, 
   uint64_t my_unit = units;
   if (lane < count) my_unit = order[p0 + lane];
   if (my_unit < units) mine = look_up(a, b, stride, second, paired, my_unit, recs, sh, clip_on);      // (a number that is none: nothing, as in X2)
-  // where the unit of this lane goes: the group's offsets and the lengths of the units in front of it
-  uint64_t at_1 = mine.len1, at_2 = mine.len2;
-#pragma unroll
-  for (int o = 1; o < (int)kDxGroup; o <<= 1) {
-    const uint64_t v1 = __shfl_up((unsigned long long)at_1, o, 64), v2 = __shfl_up((unsigned long long)at_2, o, 64);
-    if (lane >= (uint32_t)o) { at_1 += v1; at_2 += v2; }
-  }
-  at_1 += off_1[g] - mine.len1; at_2 += off_2[g] - mine.len2;
+  const uint64_t len[2] = {mine.len1, mine.len2};
+  uint64_t at[2];
+  place_units(len, g, n_groups, group_off, lane, at);
   for (uint32_t q = 0; q < count; ++q) {
-    const uint64_t l1 = bcast(mine.len1, q), l2 = bcast(mine.len2, q), first = bcast(mine.first, q), w1 = bcast(at_1, q), w2 = bcast(at_2, q);
+    const uint64_t l1 = bcast(mine.len1, q), l2 = bcast(mine.len2, q), first = bcast(mine.first, q), w1 = bcast(at[0], q), w2 = bcast(at[1], q);
     if (l1 + l2 == 0) continue;                            // (only a unit number that is none: a record has its four '\n' at the least)
     const DxRead m1 = bcast(mine.m[0], q);                 // (every lane takes part in the shuffles)
     if (o1.p) write_read(a, m1, o1.p + w1, lane);
@@ -399,11 +359,6 @@ __global__ __launch_bounds__(64 * kDxWaves) void dx_write(DxInput a, DxInput b, 
 }
 
 using scfq_demux_host::Params;
-
-enum class Mode { single, two, interleaved };
-
-struct Dest { uint8_t* p; uint64_t cap; bool want; };
-const char* const kDestName[2] = {"out1", "out2"};
 
 uint32_t key_bits(uint32_t n_samples) {                  // ceil(log2(N + 1)): the keys are 0 .. N
   uint32_t bits = 1;
@@ -426,39 +381,28 @@ int demux_device(const scfq_demux_host::Sheet& sheet, const uint8_t* d1, uint64_
   scfq_overlap::Indexed ix;
   int rc = SCFQ_OK;
   double index_ms = 0;
-  if (paired) {
-    rc = scfq_overlap::index_inputs(d1, n1, d2, n2, interleaved, stream, g_xerr, ix, &index_ms);
-  } else {
-    if ((rc = scfq_scratch::build_line_index(d1, n1, stream, g_xerr, ix.off1, &ix.lines1, &ix.cr1))) return rc;
-    ix.reads1 = (ix.lines1 + 3) / 4;
-    if (ix.reads1 >= (1ull << 31)) { std::snprintf(g_xerr, sizeof g_xerr, "more than 2^31 records in one input"); rc = SCFQ_EARG; }
-  }
-  st->lines1 = ix.lines1; st->lines2 = ix.lines2;
-  st->reads1 = ix.reads1; st->reads2 = ix.reads2;
-  if (rc) return rc;
-  st->pairs = ix.pairs;
-  st->unpaired = ix.unpaired;
-  const uint64_t units = paired ? ix.pairs : ix.reads1;
+  uint64_t units = 0, reads = 0;
+  if ((rc = scfq_reads::index_units(d1, n1, d2, n2, mode, stream, g_xerr, ix, &index_ms, st, &units, &reads))) return rc;
   st->units_in = units;
-  st->reads_in = st->reads_out = paired ? 2 * ix.pairs : ix.reads1;
+  st->reads_in = st->reads_out = reads;
   if (check_rec_cap && recs_out && rec_cap < units) {
     std::snprintf(g_xerr, sizeof g_xerr, "the per-unit table holds %llu entries, the input has %llu units", (unsigned long long)rec_cap, (unsigned long long)units);
     return SCFQ_EARG;
   }
   if (units == 0) return SCFQ_OK;           // (two empty outputs: they fit into anything; nothing is launched)
-  const uint64_t n_groups = (units + kDxGroup - 1) / kDxGroup, row = n_groups + 1;
+  const uint64_t n_groups = (units + kDxGroup - 1) / kDxGroup;
   const uint64_t row_words = (uint64_t)(N + 1) * kRowWords + kTotals;
   DevBuf codes, lens, keys, keys2, idx, idx2, group_len, group_off, counters, d_rows, tmp;
+  scfq_reads::GroupScan gs(2, n_groups, group_len, group_off, stream, g_xerr);
   if ((!recs_out && (rc = recs_keep.alloc(units * sizeof(scfq_demux_rec), stream, g_xerr))) || (rc = codes.alloc((size_t)N * 16, stream, g_xerr)) ||
       (rc = lens.alloc((size_t)N * 4, stream, g_xerr)) || (rc = keys.alloc(units * 2, stream, g_xerr)) || (rc = keys2.alloc(units * 2, stream, g_xerr)) ||
-      (rc = idx.alloc(units * 4, stream, g_xerr)) || (rc = idx2.alloc(units * 4, stream, g_xerr)) || (rc = group_len.alloc(2 * row * 8, stream, g_xerr)) ||
-      (rc = group_off.alloc(2 * row * 8, stream, g_xerr)) || (rc = counters.alloc(kKinds * 8, stream, g_xerr)) || (rc = d_rows.alloc(row_words * 8, stream, g_xerr)))
+      (rc = idx.alloc(units * 4, stream, g_xerr)) || (rc = idx2.alloc(units * 4, stream, g_xerr)) || (rc = gs.alloc()) ||
+      (rc = counters.alloc(kKinds * 8, stream, g_xerr)) || (rc = d_rows.alloc(row_words * 8, stream, g_xerr)))
     return rc;
   scfq_demux_rec* const recs = recs_out ? recs_out : recs_keep.as<scfq_demux_rec>();
   const uint32_t bits = key_bits(N);
   size_t scan_bytes = 0, sort_bytes = 0;
-  SCFQ_SCRATCH_CHK(g_xerr, rocprim::exclusive_scan(nullptr, scan_bytes, group_len.as<uint64_t>(), group_off.as<uint64_t>(), (uint64_t)0, (size_t)row,
-                                                   rocprim::plus<uint64_t>(), stream));
+  if ((rc = gs.scratch_bytes(&scan_bytes))) return rc;
   SCFQ_SCRATCH_CHK(g_xerr, rocprim::radix_sort_pairs(nullptr, sort_bytes, keys.as<uint16_t>(), keys2.as<uint16_t>(), idx.as<uint32_t>(), idx2.as<uint32_t>(),
                                                      (size_t)units, 0u, bits, stream));
   if ((rc = tmp.alloc(std::max(scan_bytes, sort_bytes), stream, g_xerr))) return rc;
@@ -468,9 +412,9 @@ int demux_device(const scfq_demux_host::Sheet& sheet, const uint8_t* d1, uint64_
   SCFQ_SCRATCH_CHK(g_xerr, hipMemcpyAsync(lens.p, sheet.lens.data(), (size_t)N * 4, hipMemcpyHostToDevice, stream));
   SCFQ_SCRATCH_CHK(g_xerr, hipMemsetAsync(counters.p, 0, kKinds * 8, stream));
   SCFQ_SCRATCH_CHK(g_xerr, hipMemsetAsync(d_rows.p, 0, row_words * 8, stream));
-  SCFQ_SCRATCH_CHK(g_xerr, hipMemsetAsync(group_len.p, 0, 2 * row * 8, stream));       // (each scan's last input: its last output is the total)
-  const DxInput a = {d1, n1, ix.off1.as<uint64_t>(), ix.lines1, ix.cr1};
-  const DxInput b = mode == Mode::two ? DxInput{d2, n2, ix.off2.as<uint64_t>(), ix.lines2, ix.cr2} : a;
+  if ((rc = gs.zero())) return rc;
+  const RecInput a = {d1, n1, ix.off1.as<uint64_t>(), ix.lines1, ix.cr1};
+  const RecInput b = mode == Mode::two ? RecInput{d2, n2, ix.off2.as<uint64_t>(), ix.lines2, ix.cr2} : a;
   const uint64_t stride = interleaved ? 2 : 1, second = interleaved ? 1 : 0;
   const uint32_t header = (prm.flags & SCFQ_DEMUX_HEADER) ? 1u : 0u;
   const uint32_t clip_on = !header && !(prm.flags & SCFQ_DEMUX_KEEP_BARCODE) ? 1u : 0u;
@@ -486,21 +430,19 @@ int demux_device(const scfq_demux_host::Sheet& sheet, const uint8_t* d1, uint64_
   clk.mark(2);
   const uint32_t* const order = idx2.as<uint32_t>();
   hipLaunchKernelGGL(dx_lengths, dim3(blocks), dim3(256), 0, stream, a, b, stride, second, paired ? 1u : 0u, units, order, recs, dsh, clip_on, n_groups,
-                     group_len.as<uint64_t>(), d_rows.as<unsigned long long>());
+                     gs.len(), d_rows.as<unsigned long long>());
   SCFQ_SCRATCH_CHK(g_xerr, hipGetLastError());
-  for (uint64_t x = 0; x < 2; ++x)
-    SCFQ_SCRATCH_CHK(g_xerr, rocprim::exclusive_scan(tmp.p, scan_bytes, group_len.as<uint64_t>() + x * row, group_off.as<uint64_t>() + x * row, (uint64_t)0, (size_t)row,
-                                                     rocprim::plus<uint64_t>(), stream));
+  if ((rc = gs.scan(tmp.p, scan_bytes))) return rc;
   clk.mark(3);
   // the sizes, the rows and the kinds come back first: pool memory for the outputs is taken to fit, and a caller's buffer that is too
   // small is known here, before anything is stored
-  uint64_t total[2] = {0, 0}, kinds[kKinds];
+  uint64_t kinds[kKinds];
   std::vector<uint64_t> h_rows(row_words);
-  for (uint64_t x = 0; x < 2; ++x) SCFQ_SCRATCH_CHK(g_xerr, hipMemcpyAsync(&total[x], group_off.as<uint64_t>() + x * row + n_groups, 8, hipMemcpyDeviceToHost, stream));
+  if ((rc = gs.read_totals())) return rc;
   SCFQ_SCRATCH_CHK(g_xerr, hipMemcpyAsync(kinds, counters.p, sizeof kinds, hipMemcpyDeviceToHost, stream));
   SCFQ_SCRATCH_CHK(g_xerr, hipMemcpyAsync(h_rows.data(), d_rows.p, row_words * 8, hipMemcpyDeviceToHost, stream));
   SCFQ_SCRATCH_CHK(g_xerr, hipStreamSynchronize(stream));
-  st->out1_bytes = total[0]; st->out2_bytes = total[1];
+  st->out1_bytes = gs.total[0]; st->out2_bytes = gs.total[1];
   st->perfect = kinds[kPerfect]; st->mismatched = kinds[kMismatched];
   st->unmatched = kinds[kUnmatched]; st->ambiguous = kinds[kAmbiguous]; st->no_barcode = kinds[kNoBarcode];
   st->assigned = st->perfect + st->mismatched;
@@ -514,38 +456,17 @@ int demux_device(const scfq_demux_host::Sheet& sheet, const uint8_t* d1, uint64_
   }
   st->bases_in = h_rows[(size_t)(N + 1) * kRowWords + kBasesIn];
   st->bases_clipped = h_rows[(size_t)(N + 1) * kRowWords + kBasesClipped];
-  int small = -1;
-  for (int x = 1; x >= 0; --x)
-    if (check_caps && dst[x].want && total[x] > dst[x].cap) small = x;
-  DxOut out[2];
-  for (int x = 0; x < 2; ++x) {
-    out[x] = DxOut{nullptr, 0};
-    if (!dst[x].want || small >= 0) continue;
-    if (!own_outputs) { out[x] = DxOut{dst[x].p, dst[x].cap}; continue; }
-    if (total[x] == 0) continue;
-    if ((rc = own[x].alloc(total[x], stream, g_xerr))) return rc;
-    out[x] = DxOut{own[x].as<uint8_t>(), total[x]};
-  }
-  if (out[0].p || out[1].p) {
+  const scfq_reads::Placement put = scfq_reads::place_outputs(gs, scfq_reads::kOutNames, dst, own_outputs, check_caps, false, own, stream, g_xerr);
+  if (put.rc) return put.rc;
+  if (put.out[0].p || put.out[1].p) {
     hipLaunchKernelGGL(dx_write, dim3((unsigned)((n_groups + kDxWaves - 1) / kDxWaves)), dim3(64 * kDxWaves), 0, stream, a, b, stride, second, paired ? 1u : 0u,
-                       units, order, recs, dsh, clip_on, n_groups, group_off.as<uint64_t>(), out[0], out[1]);
+                       units, order, recs, dsh, clip_on, n_groups, gs.off(), put.out[0], put.out[1]);
     SCFQ_SCRATCH_CHK(g_xerr, hipGetLastError());
   }
   clk.mark(4);
   SCFQ_SCRATCH_CHK(g_xerr, hipStreamSynchronize(stream));
   for (int k = 0; k < 4; ++k) g_stage_ms[k] = clk.between(k, k + 1);
-  if (small >= 0) {
-    std::snprintf(g_xerr, sizeof g_xerr, "the %s output holds %llu bytes, the result has %llu", kDestName[small], (unsigned long long)dst[small].cap,
-                  (unsigned long long)total[small]);
-    return SCFQ_EARG;
-  }
-  return SCFQ_OK;
-}
-
-// after a failure kernels that read the second input may still be queued on the first one's stream (as fq-merge's)
-int finish(scfq_scratch::ResidentInput& in1, int rc) {
-  if (rc != SCFQ_OK) (void)hipStreamSynchronize(in1.stream);
-  return rc;
+  return put.verdict;      // (SCFQ_EARG for an output that is too small: place_outputs has left the text)
 }
 
 // what both entry points decide before any device call
@@ -617,8 +538,7 @@ int scfq_demux_buffers(const scfq_demux_sheet* sheet, const void* r1, uint64_t n
   if (rc) return finish(in1, rc);
   if (!direct) {
     const uint64_t bytes[2] = {stats->out1_bytes, stats->out2_bytes};
-    for (int x = 0; x < 2; ++x)
-      if (own[x].p) SCFQ_SCRATCH_CHK(g_xerr, hipMemcpyAsync(dst[x].p, own[x].p, bytes[x], hipMemcpyDeviceToHost, in1.stream));
+    if ((rc = scfq_reads::outputs_to_host(2, dst, own, bytes, in1.stream, g_xerr))) return rc;
     SCFQ_SCRATCH_CHK(g_xerr, hipStreamSynchronize(in1.stream));
   }
   for (DevBuf& o : own) o.drop();

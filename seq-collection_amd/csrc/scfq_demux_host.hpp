@@ -4,6 +4,8 @@
 #pragma once
 #include "../../include/sc_fqcount.h"
 
+#include "scfq_copy_text.hpp"
+
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -118,15 +120,6 @@ inline std::string out_path(const Sheet& sh, const char* out_dir, uint32_t d, bo
   return p + ".fq";
 }
 
-inline int copy_out(const char* text, int m, char* buf, uint64_t cap) {
-  if (buf && cap) {
-    const uint64_t ncopy = ((uint64_t)m < cap - 1) ? (uint64_t)m : cap - 1;
-    std::memcpy(buf, text, ncopy);
-    buf[ncopy] = 0;
-  }
-  return m;
-}
-
 // the report row (include/sc_fqcount.h: scfq_format_demux_row_tsv)
 inline int format_row(const scfq_demux_stats* s, const Sheet& sh, uint32_t d, const scfq_demux_row* row, char* buf, uint64_t cap) {
   if (!s || !row || d > sh.n() || s->n_samples != sh.n()) return SCFQ_EARG;
@@ -138,7 +131,7 @@ inline int format_row(const scfq_demux_stats* s, const Sheet& sh, uint32_t d, co
                               (unsigned long long)row->units, (unsigned long long)(pct / 100), (unsigned long long)(pct % 100), (unsigned long long)row->perfect,
                               (unsigned long long)row->mismatched, (unsigned long long)row->bases_out, (unsigned long long)row->bytes1,
                               (unsigned long long)row->bytes2);
-  return copy_out(tmp, m, buf, cap);
+  return scfq_reads::copy_text(tmp, m, buf, cap);
 }
 
 }  // namespace scfq_demux_host

@@ -6,6 +6,7 @@
 //   src/fq_count.nim:42-45   sequence line is i mod 4 == 2  == relative class r = 1 from phase 0
 //   src/fq_count.nim:47-51   output fields and `$` formatting (Nim 1.0.6 `$float` = "%.16g" + ".0" rule)
 #include "../../include/sc_fqcount.h"
+#include "scfq_copy_text.hpp"
 
 #include <cmath>
 #include <cstdio>
@@ -92,17 +93,6 @@ static int nim_float_to_str(double v, char* f, size_t cap) {
   return m;
 }
 
-// the end of every scfq_format_*: as much of the m bytes of text as fits into buf[cap], always terminated; the full length
-// comes back, so a call without a buffer is the sizing call
-static int copy_out(const char* text, int m, char* buf, uint64_t cap) {
-  if (buf && cap) {
-    const uint64_t ncopy = ((uint64_t)m < cap - 1) ? (uint64_t)m : cap - 1;
-    std::memcpy(buf, text, ncopy);
-    buf[ncopy] = 0;
-  }
-  return m;
-}
-
 int scfq_format_tsv(const scfq_counts* c, char* buf, uint64_t cap) {
   if (!c) return SCFQ_EARG;
   // $(gc_cnt.float / (total_len - n_cnt).float)      src/fq_count.nim:48 (int64 -> float64)
@@ -113,7 +103,7 @@ int scfq_format_tsv(const scfq_counts* c, char* buf, uint64_t cap) {
   const int m = std::snprintf(tmp, sizeof tmp, "%llu\t%s\t%llu\t%llu\t%llu", (unsigned long long)c->reads, f,
                               (unsigned long long)c->gc_bases, (unsigned long long)c->n_bases,
                               (unsigned long long)c->bases);
-  return copy_out(tmp, m, buf, cap);
+  return scfq_reads::copy_text(tmp, m, buf, cap);
 }
 
 // the fq-readstats row: mean_len and mean_qual by the same `$float` rule
@@ -127,7 +117,7 @@ int scfq_format_read_stats_tsv(const scfq_read_summary* s, char* buf, uint64_t c
                               (unsigned long long)s->bases, (unsigned long long)s->min_len, (unsigned long long)s->max_len, ml,
                               (unsigned long long)s->n50, (unsigned long long)s->l50, (unsigned long long)s->n90,
                               (unsigned long long)s->l90, mq);
-  return copy_out(tmp, m, buf, cap);
+  return scfq_reads::copy_text(tmp, m, buf, cap);
 }
 
 // the fq-cycles row: other = bases - a - c - g - t - n, mean_qual by the same `$float` rule
@@ -140,7 +130,7 @@ int scfq_format_cycle_row_tsv(const scfq_cycle_row* r, char* buf, uint64_t cap) 
                               (unsigned long long)r->a, (unsigned long long)r->c, (unsigned long long)r->g, (unsigned long long)r->t,
                               (unsigned long long)r->n, (unsigned long long)(r->bases - r->a - r->c - r->g - r->t - r->n),
                               (unsigned long long)r->quals, mq);
-  return copy_out(tmp, m, buf, cap);
+  return scfq_reads::copy_text(tmp, m, buf, cap);
 }
 
 // the fq-kmers row: the k letters of the index, first base first, and the count
@@ -149,7 +139,7 @@ int scfq_format_kmer_tsv(uint32_t k, uint64_t index, uint64_t count, char* buf, 
   char tmp[64];
   for (uint32_t i = 0; i < k; ++i) tmp[i] = "ACGT"[(index >> (2 * (k - 1 - i))) & 3u];
   const int m = (int)k + std::snprintf(tmp + k, sizeof tmp - k, "\t%llu", (unsigned long long)count);
-  return copy_out(tmp, m, buf, cap);
+  return scfq_reads::copy_text(tmp, m, buf, cap);
 }
 
 // the built-in probes of fq-adapters: the names and 12-mers the common QC tools use
@@ -177,7 +167,7 @@ int scfq_format_adapter_row_tsv(const scfq_adapter_row* r, uint32_t n_probes, ui
     else m += nim_float_to_str(100.0 * (double)v / (double)reads, tmp + m, 96);
   }
   tmp[m] = 0;
-  return copy_out(tmp, m, buf, cap);
+  return scfq_reads::copy_text(tmp, m, buf, cap);
 }
 
 // the fq-insert-size row.  The variance's numerator is exact (128 bits) and becomes a double once, so a checker with big integers
@@ -195,7 +185,7 @@ int scfq_format_insert_size_tsv(const scfq_insert_summary* s, char* buf, uint64_
                               (unsigned long long)s->overlapped, pct, (unsigned long long)s->min_insert, (unsigned long long)s->median_insert,
                               mean, sd, (unsigned long long)s->mode_insert, (unsigned long long)s->max_insert,
                               (unsigned long long)s->read_through, mr);
-  return copy_out(tmp, m, buf, cap);
+  return scfq_reads::copy_text(tmp, m, buf, cap);
 }
 
 // the fq-merge row: integers but for the share of merged pairs
@@ -208,7 +198,7 @@ int scfq_format_merge_stats_tsv(const scfq_merge_stats* s, char* buf, uint64_t c
   char tmp[1024];
   int m = std::snprintf(tmp, sizeof tmp, "%llu\t%llu\t%s", (unsigned long long)s->pairs, (unsigned long long)s->merged, pct);
   for (const uint64_t v : tail) m += std::snprintf(tmp + m, sizeof tmp - m, "\t%llu", (unsigned long long)v);
-  return copy_out(tmp, m, buf, cap);
+  return scfq_reads::copy_text(tmp, m, buf, cap);
 }
 
 // the fq-trim row: integers only; the reads per probe as one field
@@ -223,7 +213,7 @@ int scfq_format_trim_stats_tsv(const scfq_trim_stats* s, char* buf, uint64_t cap
   for (uint64_t j = 0; j < s->n_probes; ++j) m += std::snprintf(tmp + m, sizeof tmp - m, j ? ",%llu" : "%llu", (unsigned long long)s->adapter_reads[j]);
   if (!s->n_probes) m += std::snprintf(tmp + m, sizeof tmp - m, "-");
   m += std::snprintf(tmp + m, sizeof tmp - m, "\t%llu\t%llu", (unsigned long long)s->out1_bytes, (unsigned long long)s->out2_bytes);
-  return copy_out(tmp, m, buf, cap);
+  return scfq_reads::copy_text(tmp, m, buf, cap);
 }
 
 const char* scfq_strerror(int rc) {

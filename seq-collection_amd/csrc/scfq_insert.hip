@@ -24,7 +24,7 @@
 #include <hip/hip_runtime.h>
 
 #include "scfq_overlap.hpp"
-#include "scfq_record_device.hpp"
+#include "scfq_reads_device.hpp"
 #include "scfq_scratch.hpp"
 
 #include <algorithm>
@@ -49,18 +49,9 @@ static_assert(SCFQ_INSERT_MAX_LEN % 64 == 0 && 2 * SCFQ_INSERT_MAX_LEN <= SCFQ_I
 enum { kOverlapped = 0, kNotOverlapped, kTooLong, kReadThrough, kOverlapBases, kMismatches, kInsertSum, kInsertSqSum, kMin, kMax, kMode, kMedian, kSums };
 constexpr uint32_t kIsAcc = SCFQ_INSERT_HIST_BINS + kSums;
 
-struct IsInput {          // one input: the bytes and their line index
-  const uint8_t* base;
-  uint64_t n;
-  const uint64_t* line_off;
-  uint64_t lines;
-  bool has_cr;
-};
-
 // the text of the sequence line of record r (a line the input does not have is empty)
-__device__ __forceinline__ void seq_span(const IsInput& in, uint64_t r, uint64_t& s, uint64_t& e) {
-  s = e = 0;
-  if (4 * r + 1 < in.lines) line_span(in.base, in.n, in.line_off, 4 * r + 1, s, e, in.has_cr);
+__device__ __forceinline__ void seq_span(const RecInput& in, uint64_t r, uint64_t& s, uint64_t& e) {
+  text_span(in, 4 * r + 1, s, e);
 }
 
 // code (bit 0, bit 1) and valid bit of a byte: bits 1 and 2 of 'A' 'C' 'T' 'G' are 0 1 2 3
@@ -73,7 +64,7 @@ __device__ __forceinline__ void classify(uint32_t b, bool& c0, bool& c1, bool& v
 
 // P1.  a, b: the inputs of mate 1 and mate 2 (the same one twice for interleaved input); pair p is record p * stride of a and
 // record p * stride + second of b
-__global__ __launch_bounds__(kIsThreads) void is_overlap(IsInput a, IsInput b, uint64_t stride, uint64_t second, uint64_t pairs, uint32_t min_overlap,
+__global__ __launch_bounds__(kIsThreads) void is_overlap(RecInput a, RecInput b, uint64_t stride, uint64_t second, uint64_t pairs, uint32_t min_overlap,
                                                         uint32_t max_mm, uint32_t max_pct, scfq_overlap_rec* recs, unsigned long long* acc) {
   __shared__ uint32_t bins[SCFQ_INSERT_HIST_BINS];
   __shared__ uint64_t pa[kIsWaves][3][kIsSlots];
@@ -315,8 +306,8 @@ int index_inputs(const uint8_t* d1, uint64_t n1, const uint8_t* d2, uint64_t n2,
 
 int queue_overlap(const uint8_t* d1, uint64_t n1, const uint8_t* d2, uint64_t n2, bool interleaved, const Indexed& ix, const Params& prm,
                   scfq_overlap_rec* recs, unsigned long long* acc, hipStream_t stream, char* errbuf) {
-  const IsInput a = {d1, n1, static_cast<const uint64_t*>(ix.off1.p), ix.lines1, ix.cr1};
-  const IsInput b = interleaved ? a : IsInput{d2, n2, static_cast<const uint64_t*>(ix.off2.p), ix.lines2, ix.cr2};
+  const RecInput a = {d1, n1, static_cast<const uint64_t*>(ix.off1.p), ix.lines1, ix.cr1};
+  const RecInput b = interleaved ? a : RecInput{d2, n2, static_cast<const uint64_t*>(ix.off2.p), ix.lines2, ix.cr2};
   const unsigned blocks = (unsigned)std::min<uint64_t>((ix.pairs + kIsWaves - 1) / kIsWaves, kIsMaxBlocks);
   hipLaunchKernelGGL(is_overlap, dim3(blocks), dim3(kIsThreads), 0, stream, a, b, interleaved ? 2ull : 1ull, interleaved ? 1ull : 0ull, ix.pairs,
                      prm.min_overlap, prm.max_mm, prm.max_pct, recs, acc);

@@ -23,10 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
-#include "scfq_fdwrite.hpp"
-#include "scfq_overlap.hpp"
-#include "scfq_record_device.hpp"
-#include "scfq_scratch.hpp"
+#include "scfq_reads_host.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -37,48 +34,17 @@ namespace {
 thread_local char g_merr[scfq_scratch::kErrBytes] = "";
 thread_local double g_stage_ms[4] = {0, 0, 0, 0};
 
-using scfq_scratch::DevBuf;
+using scfq_reads::Dest;
+using scfq_reads::DevBuf;
+using scfq_reads::finish;
+using scfq_reads::Mode;
 
-constexpr uint32_t kMgGroup = 32;      // pairs of a group: one wave of M2, one entry of the scans
+constexpr uint32_t kMgGroup = kRecGroup;      // pairs of a group: one wave of M2, one entry of the scans
 constexpr uint32_t kMgWaves = 4;       // waves (groups) of a block of M2
 constexpr uint32_t kMgRun = 4;         // consecutive positions of a merged read a lane builds and stores at a time: one 32-bit word
 static_assert(kMgRun == 4, "a run is one 32-bit word");
 // the counters: M1's six, then M2's three
 enum { kMerged = 0, kNotOverlapped, kTooLong, kMergedBases, kOverlapBases, kMismatches, kTook1, kTook2, kNeither, kCounters };
-
-struct MgInput {          // one input: the bytes and their line index
-  const uint8_t* base;
-  uint64_t n;
-  const uint64_t* line_off;
-  uint64_t lines;
-  bool has_cr;
-};
-
-struct MgOut {            // one output: where it goes (nullptr: nowhere) and what it holds
-  uint8_t* p;
-  uint64_t cap;
-};
-
-// the text of line j (a line the input does not have is empty)
-__device__ __forceinline__ void text_span(const MgInput& in, uint64_t j, uint64_t& s, uint64_t& e) {
-  s = e = 0;
-  if (j < in.lines) line_span(in.base, in.n, in.line_off, j, s, e, in.has_cr);
-}
-
-// bytes record i echoes: its lines 4i .. min(4i+3, lines-1), each text + '\n' (dd_record_lengths' rule)
-__device__ __forceinline__ uint64_t echo_len(const MgInput& in, uint64_t i) {
-  if (!in.has_cr) {
-    const uint64_t j1 = (4 * i + 4 < in.lines) ? 4 * i + 4 : in.lines;
-    return in.line_off[j1] - in.line_off[4 * i];
-  }
-  uint64_t total = 0;
-  for (uint64_t j = 4 * i; j < 4 * i + 4 && j < in.lines; ++j) {
-    uint64_t s, e;
-    line_span(in.base, in.n, in.line_off, j, s, e);
-    total += e - s + 1;
-  }
-  return total;
-}
 
 // what a pair adds to the outputs and, for a merged pair, where its texts lie.  M1 and M2 both get it from here, so the lengths the
 // scans saw are the lengths M2 writes
@@ -92,7 +58,7 @@ struct MgPair {
   uint32_t ov, mm;
 };
 
-__device__ __forceinline__ MgPair look_up(const MgInput& a, const MgInput& b, uint64_t stride, uint64_t second, uint64_t p, const scfq_overlap_rec* recs) {
+__device__ __forceinline__ MgPair look_up(const RecInput& a, const RecInput& b, uint64_t stride, uint64_t second, uint64_t p, const scfq_overlap_rec* recs) {
   MgPair r = {};
   const scfq_overlap_rec rec = recs[p];
   const uint64_t i1 = p * stride, i2 = p * stride + second;
@@ -122,16 +88,9 @@ __device__ __forceinline__ MgPair look_up(const MgInput& a, const MgInput& b, ui
   return r;
 }
 
-__device__ __forceinline__ uint64_t half_sum(uint64_t v) {      // over the 32 lanes of a half wave
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor((unsigned long long)v, o, 64);
-  return v;
-}
-
 // M1.  group_len: three arrays of n_groups + 1 entries, one after another (the last entry of each stays 0: the scan's total)
-__global__ __launch_bounds__(256) void mg_lengths(MgInput a, MgInput b, uint64_t stride, uint64_t second, uint64_t pairs, const scfq_overlap_rec* recs,
+__global__ __launch_bounds__(256) void mg_lengths(RecInput a, RecInput b, uint64_t stride, uint64_t second, uint64_t pairs, const scfq_overlap_rec* recs,
                                                  uint64_t n_groups, uint64_t* group_len, unsigned long long* counters) {
-  static_assert(kMgGroup == 32, "the sums below run over the two halves of a wave");
   __shared__ uint64_t sum_sh[6][4];
   const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   uint64_t len[3] = {0, 0, 0}, c[6] = {0, 0, 0, 0, 0, 0};
@@ -143,10 +102,7 @@ __global__ __launch_bounds__(256) void mg_lengths(MgInput a, MgInput b, uint64_t
     c[kOverlapBases] = r.ov; c[kMismatches] = r.mm;
   }
 #pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const uint64_t s = half_sum(len[k]);
-    if ((threadIdx.x & 31) == 0 && p < pairs) group_len[(uint64_t)k * (n_groups + 1) + p / kMgGroup] = s;
-  }
+  for (int k = 0; k < 3; ++k) store_group_len(len[k], k, p, pairs, n_groups, group_len);
   // the statistics: ONE atomic per block and counter (dd_count_marks: an atomic per wave on one address costs more than the kernel)
 #pragma unroll
   for (int k = 0; k < 6; ++k) {
@@ -182,7 +138,7 @@ __device__ __forceinline__ uint32_t comp_of(uint32_t b) { return is_acgt(b) ? (0
 // words of the sequence are stored aligned.  The quality text begins s + 3 bytes further on, so its words are aligned for one s in
 // four; they are stored as words all the same (an unaligned 32-bit store is one instruction here), the first and last run of either
 // text byte by byte.
-__device__ __forceinline__ void write_merged(const MgInput& a, const MgInput& b, const MgPair& r, uint8_t* dst, uint32_t q0, uint32_t lane,
+__device__ __forceinline__ void write_merged(const RecInput& a, const RecInput& b, const MgPair& r, uint8_t* dst, uint32_t q0, uint32_t lane,
                                              uint32_t& took1, uint32_t& took2, uint32_t& neither) {
   const int s = r.d + r.lb;
   uint8_t* seq = dst + r.hl + 1;
@@ -237,35 +193,14 @@ __device__ __forceinline__ void write_merged(const MgInput& a, const MgInput& b,
   }
 }
 
-// record i of `in` echoed to dst, len bytes (dd_gather's rule: one copy when the echo is the record's own bytes)
-__device__ __forceinline__ void echo_record(const MgInput& in, uint64_t i, uint8_t* dst, uint64_t len, uint32_t lane) {
-  if (!len) return;
-  const uint64_t j0 = 4 * i, j1 = (j0 + 4 < in.lines) ? j0 + 4 : in.lines;
-  const uint64_t r0 = in.line_off[j0], r1 = in.line_off[j1];
-  if (r1 - r0 == len && r1 <= in.n) { wave_copy(dst, in.base + r0, len, lane); return; }
-  uint64_t w = 0;
-  for (uint64_t j = j0; j < j1; ++j) {
-    uint64_t s, e;
-    line_span(in.base, in.n, in.line_off, j, s, e);
-    for (uint64_t k = lane; k < e - s; k += 64) dst[w + k] = in.base[s + k];
-    if (lane == 0) dst[w + (e - s)] = '\n';
-    w += e - s + 1;
-  }
-}
-
-__device__ __forceinline__ uint64_t bcast(uint64_t v, uint32_t from) { return (uint64_t)__shfl((unsigned long long)v, (int)from, 64); }
-
 // M2.  group_off: the three scanned arrays of M1's layout
-__global__ __launch_bounds__(64 * kMgWaves) void mg_write(MgInput a, MgInput b, uint64_t stride, uint64_t second, uint64_t pairs, const scfq_overlap_rec* recs,
-                                                         uint64_t n_groups, const uint64_t* group_off, MgOut om, MgOut o1, MgOut o2, uint32_t q0,
+__global__ __launch_bounds__(64 * kMgWaves) void mg_write(RecInput a, RecInput b, uint64_t stride, uint64_t second, uint64_t pairs, const scfq_overlap_rec* recs,
+                                                         uint64_t n_groups, const uint64_t* group_off, RecOut om, RecOut o1, RecOut o2, uint32_t q0,
                                                          unsigned long long* counters) {
   __shared__ uint32_t sum_sh[3][kMgWaves];
   const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const uint64_t* off_m = group_off;
-  const uint64_t* off_1 = group_off + (n_groups + 1);
-  const uint64_t* off_2 = group_off + 2 * (n_groups + 1);
-  // (each scan's last entry is its output's size: when one is more than its output holds, nothing is written to any)
-  const bool fits = (!om.p || off_m[n_groups] <= om.cap) && (!o1.p || off_1[n_groups] <= o1.cap) && (!o2.p || off_2[n_groups] <= o2.cap);
+  // (when one result is more than its output holds, nothing is written to any; the mates' votes are counted all the same)
+  const bool fits = output_fits(om, 0, n_groups, group_off) && output_fits(o1, 1, n_groups, group_off) && output_fits(o2, 2, n_groups, group_off);
   uint8_t* const out_m = fits ? om.p : nullptr;
   uint8_t* const out_1 = fits ? o1.p : nullptr;
   uint8_t* const out_2 = fits ? o2.p : nullptr;
@@ -277,14 +212,9 @@ __global__ __launch_bounds__(64 * kMgWaves) void mg_write(MgInput a, MgInput b, 
     MgPair mine = {};
     mine.kind = 3;
     if (lane < count) mine = look_up(a, b, stride, second, p0 + lane, recs);
-    // where the pair of this lane goes: the group's offsets and the lengths of the pairs in front of it
-    uint64_t at_m = mine.len_m, at_1 = mine.len_u1, at_2 = mine.len_u2;
-#pragma unroll
-    for (int o = 1; o < (int)kMgGroup; o <<= 1) {
-      const uint64_t um = __shfl_up((unsigned long long)at_m, o, 64), u1 = __shfl_up((unsigned long long)at_1, o, 64), u2 = __shfl_up((unsigned long long)at_2, o, 64);
-      if (lane >= (uint32_t)o) { at_m += um; at_1 += u1; at_2 += u2; }
-    }
-    at_m += off_m[g] - mine.len_m; at_1 += off_1[g] - mine.len_u1; at_2 += off_2[g] - mine.len_u2;
+    const uint64_t len[3] = {mine.len_m, mine.len_u1, mine.len_u2};
+    uint64_t at[3];
+    place_units(len, g, n_groups, group_off, lane, at);
     for (uint32_t q = 0; q < count; ++q) {
       const uint32_t kind = (uint32_t)__shfl((int)mine.kind, (int)q, 64);
       if (kind == 0) {
@@ -293,11 +223,11 @@ __global__ __launch_bounds__(64 * kMgWaves) void mg_write(MgInput a, MgInput b, 
         r.sa = bcast(mine.sa, q); r.qa = bcast(mine.qa, q); r.sb = bcast(mine.sb, q); r.qb = bcast(mine.qb, q);
         r.la = __shfl(mine.la, (int)q, 64); r.lb = __shfl(mine.lb, (int)q, 64); r.qla = __shfl(mine.qla, (int)q, 64);
         r.qlb = __shfl(mine.qlb, (int)q, 64); r.d = __shfl(mine.d, (int)q, 64);
-        const uint64_t at = bcast(at_m, q);
-        write_merged(a, b, r, out_m ? out_m + at : nullptr, q0, lane, took1, took2, neither);
+        const uint64_t w = bcast(at[0], q);
+        write_merged(a, b, r, out_m ? out_m + w : nullptr, q0, lane, took1, took2, neither);
       } else {
         const uint64_t p = p0 + q, first = bcast(mine.len_first, q), l1 = bcast(mine.len_u1, q), l2 = bcast(mine.len_u2, q);
-        const uint64_t w1 = bcast(at_1, q), w2 = bcast(at_2, q);
+        const uint64_t w1 = bcast(at[1], q), w2 = bcast(at[2], q);
         if (out_1) {
           echo_record(a, p * stride, out_1 + w1, first, lane);
           if (second) echo_record(b, p * stride + second, out_1 + w1 + first, l1 - first, lane);
@@ -332,9 +262,6 @@ bool args_ok(const scfq_merge_opts* opts, const scfq_merge_stats* st, Params& p)
   return true;
 }
 
-// one output of a call: `want` it, and then the caller's device memory (p, cap) or, with own_outputs, pool memory that
-// merge_device takes by the size the scan reports (own[k]; cap is then the caller's host capacity, checked here all the same)
-struct Dest { uint8_t* p; uint64_t cap; bool want; };
 const char* const kDestName[3] = {"merged", "unmerged1", "unmerged2"};
 
 int merge_device(const uint8_t* d1, uint64_t n1, const uint8_t* d2, uint64_t n2, bool interleaved, const Params& prm, bool own_outputs, Dest dst[3],
@@ -347,61 +274,42 @@ int merge_device(const uint8_t* d1, uint64_t n1, const uint8_t* d2, uint64_t n2,
   st->max_mismatch_pct = prm.ov.max_pct;
   st->phred_offset = prm.q0;
   scfq_overlap::Indexed ix;
-  int rc = scfq_overlap::index_inputs(d1, n1, d2, n2, interleaved, stream, g_merr, ix, &g_stage_ms[0]);
-  st->lines1 = ix.lines1; st->lines2 = ix.lines2;
-  st->reads1 = ix.reads1; st->reads2 = ix.reads2;
-  if (rc) return rc;
-  const uint64_t pairs = ix.pairs;
-  st->pairs = pairs;
-  st->unpaired = ix.unpaired;
+  int rc = SCFQ_OK;
+  uint64_t pairs = 0;
+  if ((rc = scfq_reads::index_units(d1, n1, d2, n2, interleaved ? Mode::interleaved : Mode::two, stream, g_merr, ix, &g_stage_ms[0], st, &pairs, nullptr))) return rc;
   if (pairs == 0) return SCFQ_OK;           // (three empty outputs: they fit into anything)
-  const uint64_t n_groups = (pairs + kMgGroup - 1) / kMgGroup, row = n_groups + 1;
+  const uint64_t n_groups = (pairs + kMgGroup - 1) / kMgGroup;
   DevBuf recs, acc, group_len, group_off, counters, tmp;
-  if ((rc = recs.alloc(pairs * sizeof(scfq_overlap_rec), stream, g_merr)) || (rc = acc.alloc(scfq_overlap::kAccWords * 8, stream, g_merr)) ||
-      (rc = group_len.alloc(3 * row * 8, stream, g_merr)) || (rc = group_off.alloc(3 * row * 8, stream, g_merr)) ||
+  scfq_reads::GroupScan gs(3, n_groups, group_len, group_off, stream, g_merr);
+  if ((rc = recs.alloc(pairs * sizeof(scfq_overlap_rec), stream, g_merr)) || (rc = acc.alloc(scfq_overlap::kAccWords * 8, stream, g_merr)) || (rc = gs.alloc()) ||
       (rc = counters.alloc(kCounters * 8, stream, g_merr)))
     return rc;
   size_t scan_bytes = 0;
-  SCFQ_SCRATCH_CHK(g_merr, rocprim::exclusive_scan(nullptr, scan_bytes, group_len.as<uint64_t>(), group_off.as<uint64_t>(), (uint64_t)0, (size_t)row,
-                                                   rocprim::plus<uint64_t>(), stream));
-  if ((rc = tmp.alloc(scan_bytes, stream, g_merr))) return rc;
+  if ((rc = gs.scratch_bytes(&scan_bytes)) || (rc = tmp.alloc(scan_bytes, stream, g_merr))) return rc;
   static const bool timing = scfq_scratch::env_switch("SCFQ_MERGE_TIMING");
   scfq_scratch::StageClock clk(stream, timing);
   SCFQ_SCRATCH_CHK(g_merr, hipMemsetAsync(acc.p, 0, scfq_overlap::kAccWords * 8, stream));
   SCFQ_SCRATCH_CHK(g_merr, hipMemsetAsync(counters.p, 0, kCounters * 8, stream));
-  SCFQ_SCRATCH_CHK(g_merr, hipMemsetAsync(group_len.p, 0, 3 * row * 8, stream));       // (each scan's last input: its last output is the total)
+  if ((rc = gs.zero())) return rc;
   clk.mark(0);
   if ((rc = scfq_overlap::queue_overlap(d1, n1, d2, n2, interleaved, ix, prm.ov, recs.as<scfq_overlap_rec>(), acc.as<unsigned long long>(), stream, g_merr))) return rc;
   clk.mark(1);
-  const MgInput a = {d1, n1, ix.off1.as<uint64_t>(), ix.lines1, ix.cr1};
-  const MgInput b = interleaved ? a : MgInput{d2, n2, ix.off2.as<uint64_t>(), ix.lines2, ix.cr2};
+  const RecInput a = {d1, n1, ix.off1.as<uint64_t>(), ix.lines1, ix.cr1};
+  const RecInput b = interleaved ? a : RecInput{d2, n2, ix.off2.as<uint64_t>(), ix.lines2, ix.cr2};
   const uint64_t stride = interleaved ? 2 : 1, second = interleaved ? 1 : 0;
   hipLaunchKernelGGL(mg_lengths, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, stream, a, b, stride, second, pairs, recs.as<scfq_overlap_rec>(), n_groups,
-                     group_len.as<uint64_t>(), counters.as<unsigned long long>());
+                     gs.len(), counters.as<unsigned long long>());
   SCFQ_SCRATCH_CHK(g_merr, hipGetLastError());
-  for (uint64_t k = 0; k < 3; ++k)
-    SCFQ_SCRATCH_CHK(g_merr, rocprim::exclusive_scan(tmp.p, scan_bytes, group_len.as<uint64_t>() + k * row, group_off.as<uint64_t>() + k * row, (uint64_t)0, (size_t)row,
-                                                     rocprim::plus<uint64_t>(), stream));
+  if ((rc = gs.scan(tmp.p, scan_bytes))) return rc;
   clk.mark(2);
   // the sizes come back first: pool memory for the outputs is taken to fit, and a caller's buffer that is too small is known here
-  uint64_t total[3] = {0, 0, 0};
-  for (uint64_t k = 0; k < 3; ++k) SCFQ_SCRATCH_CHK(g_merr, hipMemcpyAsync(&total[k], group_off.as<uint64_t>() + k * row + n_groups, 8, hipMemcpyDeviceToHost, stream));
+  if ((rc = gs.read_totals())) return rc;
   SCFQ_SCRATCH_CHK(g_merr, hipStreamSynchronize(stream));
-  st->merged_bytes = total[0]; st->unmerged1_bytes = total[1]; st->unmerged2_bytes = total[2];
-  int small = -1;
-  for (int k = 2; k >= 0; --k)
-    if (check_caps && dst[k].want && total[k] > dst[k].cap) small = k;
-  MgOut out[3];
-  for (int k = 0; k < 3; ++k) {
-    out[k] = MgOut{nullptr, 0};
-    if (!dst[k].want) continue;
-    if (!own_outputs) { out[k] = MgOut{dst[k].p, dst[k].cap}; continue; }      // (too small or not: M2 looks at the totals itself)
-    if (small >= 0 || total[k] == 0) continue;
-    if ((rc = own[k].alloc(total[k], stream, g_merr))) return rc;
-    out[k] = MgOut{own[k].as<uint8_t>(), total[k]};
-  }
+  st->merged_bytes = gs.total[0]; st->unmerged1_bytes = gs.total[1]; st->unmerged2_bytes = gs.total[2];
+  const scfq_reads::Placement put = scfq_reads::place_outputs(gs, kDestName, dst, own_outputs, check_caps, false, own, stream, g_merr);
+  if (put.rc) return put.rc;
   hipLaunchKernelGGL(mg_write, dim3((unsigned)((n_groups + kMgWaves - 1) / kMgWaves)), dim3(64 * kMgWaves), 0, stream, a, b, stride, second, pairs,
-                     recs.as<scfq_overlap_rec>(), n_groups, group_off.as<uint64_t>(), out[0], out[1], out[2], prm.q0, counters.as<unsigned long long>());
+                     recs.as<scfq_overlap_rec>(), n_groups, gs.off(), put.out[0], put.out[1], put.out[2], prm.q0, counters.as<unsigned long long>());
   SCFQ_SCRATCH_CHK(g_merr, hipGetLastError());
   clk.mark(3);
   uint64_t h[kCounters];
@@ -413,19 +321,7 @@ int merge_device(const uint8_t* d1, uint64_t n1, const uint8_t* d2, uint64_t n2,
   g_stage_ms[1] = clk.between(0, 1);
   g_stage_ms[2] = clk.between(1, 2);
   g_stage_ms[3] = clk.between(2, 3);
-  if (small >= 0) {
-    std::snprintf(g_merr, sizeof g_merr, "the %s output holds %llu bytes, the result has %llu", kDestName[small], (unsigned long long)dst[small].cap,
-                  (unsigned long long)total[small]);
-    return SCFQ_EARG;
-  }
-  return SCFQ_OK;
-}
-
-// after a failure kernels that read the second input may still be queued on the first one's stream: they are waited for before the
-// second input's memory goes back (as fq-insert-size's run())
-int finish(scfq_scratch::ResidentInput& in1, int rc) {
-  if (rc != SCFQ_OK) (void)hipStreamSynchronize(in1.stream);
-  return rc;
+  return put.verdict;      // (SCFQ_EARG for an output that is too small: place_outputs has left the text)
 }
 
 }  // namespace
@@ -457,9 +353,8 @@ int scfq_merge_buffers(const void* r1, uint64_t n1, const void* r2, uint64_t n2,
   rc = merge_device(in1.d_in, in1.n, in2.d_in, in2.n, interleaved, prm, /*own_outputs=*/!direct, dst, own, /*check_caps=*/true, stats, in1.stream);
   if (rc) return finish(in1, rc);
   if (!direct) {
-    for (int k = 0; k < 3; ++k)
-      if (own[k].p) SCFQ_SCRATCH_CHK(g_merr, hipMemcpyAsync(dst[k].p, own[k].p, k == 0 ? stats->merged_bytes : k == 1 ? stats->unmerged1_bytes : stats->unmerged2_bytes,
-                                                            hipMemcpyDeviceToHost, in1.stream));
+    const uint64_t bytes[3] = {stats->merged_bytes, stats->unmerged1_bytes, stats->unmerged2_bytes};
+    if ((rc = scfq_reads::outputs_to_host(3, dst, own, bytes, in1.stream, g_merr))) return rc;
     SCFQ_SCRATCH_CHK(g_merr, hipStreamSynchronize(in1.stream));
   }
   for (DevBuf& o : own) o.drop();
@@ -485,14 +380,8 @@ int scfq_merge_files(const char* path1, const char* path2, const scfq_opts* opts
   DevBuf own[3];
   rc = merge_device(in1.d_in, in1.n, in2.d_in, in2.n, interleaved, prm, /*own_outputs=*/true, dst, own, /*check_caps=*/false, stats, in1.stream);
   if (rc) return finish(in1, rc);
-  if (!own[0].p && !own[1].p && !own[2].p) { in1.mark_clean(); return SCFQ_OK; }
-  // one output after another, each in full: HBM -> two pinned buffers -> write()
-  scfq_fdwrite::Pinned pinned;
-  if ((rc = pinned.init(g_merr))) return finish(in1, rc);
   const uint64_t bytes[3] = {stats->merged_bytes, stats->unmerged1_bytes, stats->unmerged2_bytes};
-  for (int k = 0; k < 3; ++k)
-    if (own[k].p && (rc = pinned.device_to_fd(own[k].as<uint8_t>(), bytes[k], fd[k], in1.stream, g_merr))) return finish(in1, rc);
-  return SCFQ_OK;
+  return scfq_reads::outputs_to_fds(3, own, bytes, fd, in1, g_merr);
 }
 
 }  // extern "C"

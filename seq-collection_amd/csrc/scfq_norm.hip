@@ -23,8 +23,7 @@
 //   N3  nm_write              a wave per group echoes the kept records with wave_copy
 // Every loop is bounded: probes by max_probe, select rounds by 32, chunk loops by the line's length from the index.  Nothing spins and no
 // block waits for another.  There is no CPU fallback.
-// (text_span, echo_len, echo_record and the front of N1 repeat scfq_screen.hip's: sharing them would change that file, whose kernels
-// stay as they are.)
+// (The front of N1 repeats S2's of scfq_screen.hip: the two kernels part ways inside their window loop.)
 #include "../../include/sc_fqcount.h"
 #include "../../include/sc_fqcount_debug.h"
 
@@ -32,12 +31,9 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
-#include "scfq_fdwrite.hpp"
 #include "scfq_kcount_internal.hpp"
 #include "scfq_norm_host.hpp"
-#include "scfq_overlap.hpp"
-#include "scfq_record_device.hpp"
-#include "scfq_scratch.hpp"
+#include "scfq_reads_host.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -51,14 +47,17 @@ namespace {
 using namespace scfq_norm_host;
 using scfq_kcount_host::kEmpty;
 using scfq_kcount_host::mix64;
-using scfq_scratch::DevBuf;
+using scfq_reads::Dest;
+using scfq_reads::DevBuf;
+using scfq_reads::finish;
+using scfq_reads::Mode;
 
 thread_local char g_nerr[scfq_scratch::kErrBytes] = "";
 thread_local double g_stage_ms[4] = {0, 0, 0, 0};
 
 constexpr uint32_t kNmWaves = 4;                         // reads a block of N1 works on at a time; groups of a block of N3
 constexpr uint32_t kNmMaxBlocks = 2048;                  // of N1
-constexpr uint32_t kNmGroup = 32;                        // units of a group: one wave of N3, one entry of the scans
+constexpr uint32_t kNmGroup = kRecGroup;                 // units of a group: one wave of N3, one entry of the scans
 constexpr uint32_t kChunk = 512;                         // window starts of a chunk of N1
 constexpr uint32_t kCodeWords = 18, kInvWords = 10;      // 64-bit words of a wave's two planes: 9 rounds of 64 bases, and the word behind
 constexpr uint32_t kNmC = 2048;                          // counts of a wave in LDS: 8 KiB
@@ -71,19 +70,6 @@ static_assert(kMarker == SCFQ_NORM_MAX_DEPTH + 1u, "the marker lies above every 
 
 struct alignas(16) KcSlot { unsigned long long key, count; };      // (scfq_kcount.hip's slot)
 
-struct NmInput {          // one input: the bytes and their line index
-  const uint8_t* base;
-  uint64_t n;
-  const uint64_t* line_off;
-  uint64_t lines;
-  bool has_cr;
-};
-
-struct NmOut {            // one output: where it goes (nullptr: nowhere) and what it holds
-  uint8_t* p;
-  uint64_t cap;
-};
-
 struct NmTable {          // the table as N1 sees it
   const KcSlot* slots;
   uint64_t slot_mask, ones;
@@ -94,12 +80,6 @@ struct NmRule { uint32_t target, min_depth, keep_no_kmers; uint64_t seed; };
 
 // the words N0 and N1 add into
 enum : uint32_t { kCuLongReads = 0, kCuLongWindows = 1, kCuCursor = 2, kCuAbsent = 3, kCuOverrun = 4, kCuWords = 5 };
-
-// the text of line j (a line the input does not have is empty)
-__device__ __forceinline__ void text_span(const NmInput& in, uint64_t j, uint64_t& s, uint64_t& e) {
-  s = e = 0;
-  if (j < in.lines) line_span(in.base, in.n, in.line_off, j, s, e, in.has_cr);
-}
 
 // what a wave has written to LDS is read by its other lanes behind this
 __device__ __forceinline__ void wave_lds_sync() {
@@ -117,18 +97,18 @@ __device__ __forceinline__ uint64_t rev_comp(uint64_t f, uint32_t k) {
 }
 
 // Read r is record r of `a` (single-end: paired = 0) or mate r & 1 of pair r >> 1: record p * stride of a, record p * stride + second of b.
-__device__ __forceinline__ const NmInput& read_text(const NmInput& a, const NmInput& b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t r,
+__device__ __forceinline__ const RecInput& read_text(const RecInput& a, const RecInput& b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t r,
                                                     uint64_t& ss, uint64_t& se) {
   const uint64_t p = paired ? r >> 1 : r;
   const bool mate2 = paired && (r & 1);
-  const NmInput& in = mate2 ? b : a;
+  const RecInput& in = mate2 ? b : a;
   const uint64_t i = paired ? p * stride + (mate2 ? second : 0) : r;
   text_span(in, 4 * i + 1, ss, se);
   return in;
 }
 
 // N0.  cu[kCuLongReads], cu[kCuLongWindows]: the reads with more than lds_windows windows and the sum of their windows
-__global__ __launch_bounds__(256) void nm_long_windows(NmInput a, NmInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t reads, uint32_t k,
+__global__ __launch_bounds__(256) void nm_long_windows(RecInput a, RecInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t reads, uint32_t k,
                                                       uint32_t lds_windows, unsigned long long* cu) {
   uint64_t n_long = 0, w_long = 0;
   for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < reads; r += (uint64_t)gridDim.x * 256) {
@@ -175,7 +155,7 @@ __device__ __forceinline__ uint32_t select_rank(const uint32_t* lds, const uint3
 
 // N1.  long_counts: long_cap words for the reads with more than lds_windows (<= kNmC) windows, handed out through cu[kCuCursor]
 template <bool kCanon>
-__global__ __launch_bounds__(64 * kNmWaves) void nm_depth(NmInput a, NmInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t reads, NmTable t,
+__global__ __launch_bounds__(64 * kNmWaves) void nm_depth(RecInput a, RecInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t reads, NmTable t,
                                                          uint32_t lds_windows, uint32_t* long_counts, uint64_t long_cap, unsigned long long* cu,
                                                          scfq_norm_rec* recs) {
   __shared__ uint64_t planes[kNmWaves][kCodeWords + kInvWords];
@@ -192,7 +172,7 @@ __global__ __launch_bounds__(64 * kNmWaves) void nm_depth(NmInput a, NmInput b, 
     const uint64_t r = r0 + wave;
     if (r >= reads) continue;                            // (wave-uniform)
     uint64_t ss, se;
-    const NmInput& in = read_text(a, b, stride, second, paired, r, ss, se);
+    const RecInput& in = read_text(a, b, stride, second, paired, r, ss, se);
     const uint64_t len = se - ss, n_win = len >= k ? len - k + 1 : 0;
     const bool in_lds = n_win <= lds_windows;            // (wave-uniform; lds_windows <= kNmC)
     uint32_t* dev = nullptr;
@@ -274,37 +254,6 @@ __global__ __launch_bounds__(64 * kNmWaves) void nm_depth(NmInput a, NmInput b, 
   if (lane == 0 && absent) atomicAdd(&cu[kCuAbsent], (unsigned long long)absent);
 }
 
-// bytes record i echoes: its lines 4i .. min(4i+3, lines-1), each text + '\n' (dd_record_lengths' rule)
-__device__ __forceinline__ uint64_t echo_len(const NmInput& in, uint64_t i) {
-  if (4 * i >= in.lines) return 0;
-  if (!in.has_cr) {
-    const uint64_t j1 = (4 * i + 4 < in.lines) ? 4 * i + 4 : in.lines;
-    return in.line_off[j1] - in.line_off[4 * i];
-  }
-  uint64_t total = 0;
-  for (uint64_t j = 4 * i; j < 4 * i + 4 && j < in.lines; ++j) {
-    uint64_t s, e;
-    line_span(in.base, in.n, in.line_off, j, s, e);
-    total += e - s + 1;
-  }
-  return total;
-}
-
-// record i of `in` echoed to dst, len bytes (dd_gather's rule: one copy when the echo is the record's own bytes)
-__device__ __forceinline__ void echo_record(const NmInput& in, uint64_t i, uint8_t* dst, uint64_t len, uint32_t lane) {
-  const uint64_t j0 = 4 * i, j1 = (j0 + 4 < in.lines) ? j0 + 4 : in.lines;
-  const uint64_t r0 = in.line_off[j0], r1 = in.line_off[j1];
-  if (r1 - r0 == len && r1 <= in.n) { wave_copy(dst, in.base + r0, len, lane); return; }
-  uint64_t w = 0;
-  for (uint64_t j = j0; j < j1; ++j) {
-    uint64_t s, e;
-    line_span(in.base, in.n, in.line_off, j, s, e);
-    for (uint64_t x = lane; x < e - s; x += 64) dst[w + x] = in.base[s + x];
-    if (lane == 0) dst[w + (e - s)] = '\n';
-    w += e - s + 1;
-  }
-}
-
 // a unit: a single-end read, or a pair.  N2 and N3 both get it from here, so the lengths the scans saw are the lengths N3 writes
 struct NmUnit {
   uint64_t len1, len2;                 // bytes for out1 and out2 (0 for a unit that is not written)
@@ -313,7 +262,7 @@ struct NmUnit {
   bool kept;
 };
 
-__device__ __forceinline__ NmUnit look_up(const NmInput& a, const NmInput& b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t u,
+__device__ __forceinline__ NmUnit look_up(const RecInput& a, const RecInput& b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t u,
                                           const scfq_norm_rec* recs, const NmRule& rule) {
   NmUnit t = {};
   const scfq_norm_rec r1 = recs[paired ? 2 * u : u];
@@ -328,21 +277,14 @@ __device__ __forceinline__ NmUnit look_up(const NmInput& a, const NmInput& b, ui
   return t;
 }
 
-__device__ __forceinline__ uint64_t half_sum(uint64_t v) {      // over the 32 lanes of a half wave
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor((unsigned long long)v, o, 64);
-  return v;
-}
-
 // the counters of N2
 enum { kOut = 0, kDropNoKmers, kDropLow, kDropHigh, kShort, kBasesIn, kBasesOut, kWindows, kKmers, kWeak, kCounters };
 
 // N2.  group_len: two arrays of n_groups + 1 entries, one after the other (the last entry of each stays 0: the scan's total).
 // hist: nullptr, or 2 * bins words: [2d] units with D = d, [2d + 1] the kept ones among them; the last bin gathers D >= bins - 1
-__global__ __launch_bounds__(256) void nm_decide(NmInput a, NmInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t units,
+__global__ __launch_bounds__(256) void nm_decide(RecInput a, RecInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t units,
                                                 const scfq_norm_rec* recs, NmRule rule, uint32_t k, uint64_t n_groups, uint64_t* group_len,
                                                 unsigned long long* hist, uint64_t bins, unsigned long long* counters) {
-  static_assert(kNmGroup == 32, "the sums below run over the two halves of a wave");
   __shared__ unsigned long long sum_sh[kCounters];
   __shared__ uint32_t hist_sh[2 * kNmHistLds];           // (a block sees fewer than 2^32 units)
   const uint32_t in_lds = hist ? (uint32_t)(bins < kNmHistLds ? bins : kNmHistLds) : 0u;
@@ -390,10 +332,7 @@ __global__ __launch_bounds__(256) void nm_decide(NmInput a, NmInput b, uint64_t 
       }
     }
 #pragma unroll
-    for (int x = 0; x < 2; ++x) {
-      const uint64_t s = half_sum(len[x]);
-      if ((threadIdx.x & 31) == 0 && live) group_len[(uint64_t)x * (n_groups + 1) + u / kNmGroup] = s;
-    }
+    for (int x = 0; x < 2; ++x) store_group_len(len[x], x, u, units, n_groups, group_len);
   }
   // the statistics: a sum per wave into LDS, then ONE atomic per block and counter
   const bool first_lane = (threadIdx.x & 63) == 0;
@@ -408,33 +347,24 @@ __global__ __launch_bounds__(256) void nm_decide(NmInput a, NmInput b, uint64_t 
     if (hist_sh[x]) atomicAdd(&hist[x], (unsigned long long)hist_sh[x]);
 }
 
-__device__ __forceinline__ uint64_t bcast(uint64_t v, uint32_t from) { return (uint64_t)__shfl((unsigned long long)v, (int)from, 64); }
-
 // N3.  group_off: the two scanned arrays of N2's layout
-__global__ __launch_bounds__(64 * kNmWaves) void nm_write(NmInput a, NmInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t units,
-                                                         const scfq_norm_rec* recs, NmRule rule, uint64_t n_groups, const uint64_t* group_off, NmOut o1,
-                                                         NmOut o2) {
+__global__ __launch_bounds__(64 * kNmWaves) void nm_write(RecInput a, RecInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t units,
+                                                         const scfq_norm_rec* recs, NmRule rule, uint64_t n_groups, const uint64_t* group_off, RecOut o1,
+                                                         RecOut o2) {
   const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const uint64_t* off_1 = group_off;
-  const uint64_t* off_2 = group_off + (n_groups + 1);
-  // (each scan's last entry is its output's size: when one is more than its output holds, nothing is written to either)
-  const bool fits = (!o1.p || off_1[n_groups] <= o1.cap) && (!o2.p || off_2[n_groups] <= o2.cap);
-  if (!fits) return;
+  // (when one result is more than its output holds, nothing is written to either)
+  if (!(output_fits(o1, 0, n_groups, group_off) && output_fits(o2, 1, n_groups, group_off))) return;
   const uint64_t g = (uint64_t)blockIdx.x * kNmWaves + wave;
   if (g >= n_groups) return;
   const uint64_t u0 = g * kNmGroup;
   const uint32_t count = (uint32_t)std::min<uint64_t>(kNmGroup, units - u0);
   NmUnit mine = {};
   if (lane < count) mine = look_up(a, b, stride, second, paired, u0 + lane, recs, rule);
-  uint64_t at_1 = mine.len1, at_2 = mine.len2;
-#pragma unroll
-  for (int o = 1; o < (int)kNmGroup; o <<= 1) {
-    const uint64_t v1 = __shfl_up((unsigned long long)at_1, o, 64), v2 = __shfl_up((unsigned long long)at_2, o, 64);
-    if (lane >= (uint32_t)o) { at_1 += v1; at_2 += v2; }
-  }
-  at_1 += off_1[g] - mine.len1; at_2 += off_2[g] - mine.len2;
+  const uint64_t len[2] = {mine.len1, mine.len2};
+  uint64_t at[2];
+  place_units(len, g, n_groups, group_off, lane, at);
   for (uint32_t q = 0; q < count; ++q) {
-    const uint64_t l1 = bcast(mine.len1, q), l2 = bcast(mine.len2, q), first = bcast(mine.first, q), w1 = bcast(at_1, q), w2 = bcast(at_2, q);
+    const uint64_t l1 = bcast(mine.len1, q), l2 = bcast(mine.len2, q), first = bcast(mine.first, q), w1 = bcast(at[0], q), w2 = bcast(at[1], q);
     if (l1 + l2 == 0) continue;                            // (a unit that is not written, or the echo of nothing)
     const uint64_t u = u0 + q;
     const uint64_t i1 = paired ? u * stride : u, i2 = u * stride + second;
@@ -445,11 +375,6 @@ __global__ __launch_bounds__(64 * kNmWaves) void nm_write(NmInput a, NmInput b, 
     }
   }
 }
-
-enum class Mode { single, two, interleaved };
-
-struct Dest { uint8_t* p; uint64_t cap; bool want; };
-const char* const kDestName[2] = {"out1", "out2"};
 
 uint32_t lds_windows_env() {
   static const uint32_t v = [] {
@@ -464,27 +389,14 @@ uint32_t lds_windows_env() {
 int index_and_check(const uint8_t* d1, uint64_t n1, const uint8_t* d2, uint64_t n2, Mode mode, const Params& prm, bool check_rec_cap, uint64_t rec_cap,
                     scfq_overlap::Indexed& ix, scfq_norm_stats* st, hipStream_t stream) {
   for (double& m : g_stage_ms) m = 0;
-  const bool paired = mode != Mode::single;
   st->input_bytes1 = n1;
   st->input_bytes2 = n2;
   st->flags = prm.flags; st->target = prm.target; st->min_depth = prm.min_depth; st->weak_below = prm.weak_below; st->seed = prm.seed;
-  int rc = SCFQ_OK;
-  if (paired) {
-    rc = scfq_overlap::index_inputs(d1, n1, d2, n2, mode == Mode::interleaved, stream, g_nerr, ix, &g_stage_ms[0]);
-  } else {
-    const auto t_a = std::chrono::steady_clock::now();
-    if ((rc = scfq_scratch::build_line_index(d1, n1, stream, g_nerr, ix.off1, &ix.lines1, &ix.cr1))) return rc;
-    g_stage_ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_a).count();
-    ix.reads1 = (ix.lines1 + 3) / 4;
-    if (ix.reads1 >= (1ull << 31)) { std::snprintf(g_nerr, sizeof g_nerr, "more than 2^31 records in one input"); rc = SCFQ_EARG; }
-  }
-  st->lines1 = ix.lines1; st->lines2 = ix.lines2;
-  st->reads1 = ix.reads1; st->reads2 = ix.reads2;
+  const auto t_a = std::chrono::steady_clock::now();
+  const int rc = scfq_reads::index_units(d1, n1, d2, n2, mode, stream, g_nerr, ix, &g_stage_ms[0], st, &st->units_in, &st->reads_in);
+  // (index_units takes the time of paired input only; this pipeline reports the one index of single-end input as well)
+  if (mode == Mode::single) g_stage_ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_a).count();
   if (rc) return rc;
-  st->pairs = ix.pairs;
-  st->unpaired = ix.unpaired;
-  st->units_in = paired ? ix.pairs : ix.reads1;
-  st->reads_in = paired ? 2 * ix.pairs : ix.reads1;
   if (check_rec_cap && rec_cap < st->reads_in) {
     std::snprintf(g_nerr, sizeof g_nerr, "the per-read table holds %llu entries, the input has %llu reads", (unsigned long long)rec_cap,
                   (unsigned long long)st->reads_in);
@@ -516,27 +428,26 @@ int norm_device(const scfq_kcount_internal::View& tv, const uint8_t* d1, uint64_
   const uint64_t units = st->units_in, reads = st->reads_in;
   if (hist_host) std::memset(hist_host, 0, 2 * bins * 8);
   if (units == 0) return SCFQ_OK;           // (two empty outputs: they fit into anything)
-  const uint64_t n_groups = (units + kNmGroup - 1) / kNmGroup, row = n_groups + 1;
+  const uint64_t n_groups = (units + kNmGroup - 1) / kNmGroup;
   const size_t hist_bytes = hist_host ? 2 * bins * 8 : 0;
   int rc = SCFQ_OK;
   DevBuf group_len, group_off, counters, cursors, tmp, hist, long_counts;
-  if ((!recs_out && (rc = recs_keep.alloc(reads * sizeof(scfq_norm_rec), stream, g_nerr))) || (rc = group_len.alloc(2 * row * 8, stream, g_nerr)) ||
-      (rc = group_off.alloc(2 * row * 8, stream, g_nerr)) || (rc = counters.alloc(kCounters * 8, stream, g_nerr)) ||
+  scfq_reads::GroupScan gs(2, n_groups, group_len, group_off, stream, g_nerr);
+  if ((!recs_out && (rc = recs_keep.alloc(reads * sizeof(scfq_norm_rec), stream, g_nerr))) || (rc = gs.alloc()) ||
+      (rc = counters.alloc(kCounters * 8, stream, g_nerr)) ||
       (rc = cursors.alloc(kCuWords * 8, stream, g_nerr)) || (hist_bytes && (rc = hist.alloc(hist_bytes, stream, g_nerr))))
     return rc;
   scfq_norm_rec* const recs = recs_out ? recs_out : recs_keep.as<scfq_norm_rec>();
   size_t scan_bytes = 0;
-  SCFQ_SCRATCH_CHK(g_nerr, rocprim::exclusive_scan(nullptr, scan_bytes, group_len.as<uint64_t>(), group_off.as<uint64_t>(), (uint64_t)0, (size_t)row,
-                                                   rocprim::plus<uint64_t>(), stream));
-  if ((rc = tmp.alloc(scan_bytes, stream, g_nerr))) return rc;
+  if ((rc = gs.scratch_bytes(&scan_bytes)) || (rc = tmp.alloc(scan_bytes, stream, g_nerr))) return rc;
   static const bool timing = scfq_scratch::env_switch("SCFQ_NORM_TIMING");
   const uint32_t lds_windows = lds_windows_env();
   SCFQ_SCRATCH_CHK(g_nerr, hipMemsetAsync(counters.p, 0, kCounters * 8, stream));
   SCFQ_SCRATCH_CHK(g_nerr, hipMemsetAsync(cursors.p, 0, kCuWords * 8, stream));
-  SCFQ_SCRATCH_CHK(g_nerr, hipMemsetAsync(group_len.p, 0, 2 * row * 8, stream));       // (each scan's last input: its last output is the total)
+  if ((rc = gs.zero())) return rc;
   if (hist_bytes) SCFQ_SCRATCH_CHK(g_nerr, hipMemsetAsync(hist.p, 0, hist_bytes, stream));
-  const NmInput a = {d1, n1, static_cast<const uint64_t*>(ix.off1.p), ix.lines1, ix.cr1};
-  const NmInput b = mode == Mode::two ? NmInput{d2, n2, static_cast<const uint64_t*>(ix.off2.p), ix.lines2, ix.cr2} : a;
+  const RecInput a = {d1, n1, static_cast<const uint64_t*>(ix.off1.p), ix.lines1, ix.cr1};
+  const RecInput b = mode == Mode::two ? RecInput{d2, n2, static_cast<const uint64_t*>(ix.off2.p), ix.lines2, ix.cr2} : a;
   const uint64_t stride = interleaved ? 2 : 1, second = interleaved ? 1 : 0;
   const NmRule rule = {prm.target, prm.min_depth, (prm.flags & SCFQ_NORM_KEEP_NO_KMERS) ? 1u : 0u, prm.seed};
   const NmTable table = {static_cast<const KcSlot*>(tv.slots), tv.n_slots - 1, tv.ones, tv.max_probe, tv.k, prm.weak_below};
@@ -562,17 +473,15 @@ int norm_device(const scfq_kcount_internal::View& tv, const uint8_t* d1, uint64_
   SCFQ_SCRATCH_CHK(g_nerr, hipGetLastError());
   clk.mark(1);
   hipLaunchKernelGGL(nm_decide, dim3((unsigned)std::min<uint64_t>((units + 255) / 256, kNmDecideBlocks)), dim3(256), 0, stream, a, b, stride, second,
-                     paired ? 1u : 0u, units, recs, rule, tv.k, n_groups, group_len.as<uint64_t>(), hist.as<unsigned long long>(), bins,
+                     paired ? 1u : 0u, units, recs, rule, tv.k, n_groups, gs.len(), hist.as<unsigned long long>(), bins,
                      counters.as<unsigned long long>());
   SCFQ_SCRATCH_CHK(g_nerr, hipGetLastError());
-  for (uint64_t x = 0; x < 2; ++x)
-    SCFQ_SCRATCH_CHK(g_nerr, rocprim::exclusive_scan(tmp.p, scan_bytes, group_len.as<uint64_t>() + x * row, group_off.as<uint64_t>() + x * row, (uint64_t)0, (size_t)row,
-                                                     rocprim::plus<uint64_t>(), stream));
+  if ((rc = gs.scan(tmp.p, scan_bytes))) return rc;
   clk.mark(2);
   // the sizes and the statistics come back first: pool memory for the outputs is taken to fit, and a caller's buffer that is too small
   // is known here
-  uint64_t total[2] = {0, 0}, h[kCounters];
-  for (uint64_t x = 0; x < 2; ++x) SCFQ_SCRATCH_CHK(g_nerr, hipMemcpyAsync(&total[x], group_off.as<uint64_t>() + x * row + n_groups, 8, hipMemcpyDeviceToHost, stream));
+  uint64_t h[kCounters];
+  if ((rc = gs.read_totals())) return rc;
   SCFQ_SCRATCH_CHK(g_nerr, hipMemcpyAsync(h, counters.p, sizeof h, hipMemcpyDeviceToHost, stream));
   SCFQ_SCRATCH_CHK(g_nerr, hipMemcpyAsync(hcu, cursors.p, sizeof hcu, hipMemcpyDeviceToHost, stream));
   SCFQ_SCRATCH_CHK(g_nerr, hipStreamSynchronize(stream));
@@ -581,27 +490,17 @@ int norm_device(const scfq_kcount_internal::View& tv, const uint8_t* d1, uint64_
     std::snprintf(g_nerr, sizeof g_nerr, "N1 took %llu words for its long reads, N0 counted %llu", (unsigned long long)hcu[kCuCursor], (unsigned long long)long_cap);
     return SCFQ_EHIP;
   }
-  st->out1_bytes = total[0]; st->out2_bytes = total[1];
+  st->out1_bytes = gs.total[0]; st->out2_bytes = gs.total[1];
   st->units_out = h[kOut]; st->reads_out = h[kOut] * (paired ? 2 : 1);
   st->dropped_no_kmers = h[kDropNoKmers]; st->dropped_low = h[kDropLow]; st->dropped_high = h[kDropHigh];
   st->short_reads = h[kShort]; st->bases_in = h[kBasesIn]; st->bases_out = h[kBasesOut];
   st->windows = h[kWindows]; st->kmers = h[kKmers]; st->skipped = h[kWindows] - h[kKmers];
   st->weak_kmers = h[kWeak]; st->absent_kmers = hcu[kCuAbsent];
-  int small = -1;
-  for (int x = 1; x >= 0; --x)
-    if (check_caps && dst[x].want && total[x] > dst[x].cap) small = x;
-  NmOut out[2];
-  for (int x = 0; x < 2; ++x) {
-    out[x] = NmOut{nullptr, 0};
-    if (!dst[x].want) continue;
-    if (!own_outputs) { out[x] = NmOut{dst[x].p, dst[x].cap}; continue; }      // (too small or not: N3 looks at the totals itself)
-    if (small >= 0 || total[x] == 0) continue;
-    if ((rc = own[x].alloc(total[x], stream, g_nerr))) return rc;
-    out[x] = NmOut{own[x].as<uint8_t>(), total[x]};
-  }
-  if (out[0].p || out[1].p) {
+  const scfq_reads::Placement put = scfq_reads::place_outputs(gs, scfq_reads::kOutNames, dst, own_outputs, check_caps, false, own, stream, g_nerr);
+  if (put.rc) return put.rc;
+  if (put.out[0].p || put.out[1].p) {
     hipLaunchKernelGGL(nm_write, dim3((unsigned)((n_groups + kNmWaves - 1) / kNmWaves)), dim3(64 * kNmWaves), 0, stream, a, b, stride, second, paired ? 1u : 0u,
-                       units, recs, rule, n_groups, group_off.as<uint64_t>(), out[0], out[1]);
+                       units, recs, rule, n_groups, gs.off(), put.out[0], put.out[1]);
     SCFQ_SCRATCH_CHK(g_nerr, hipGetLastError());
   }
   clk.mark(3);
@@ -609,18 +508,7 @@ int norm_device(const scfq_kcount_internal::View& tv, const uint8_t* d1, uint64_
   g_stage_ms[1] = clk.between(0, 1);
   g_stage_ms[2] = clk.between(1, 2);
   g_stage_ms[3] = clk.between(2, 3);
-  if (small >= 0) {
-    std::snprintf(g_nerr, sizeof g_nerr, "the %s output holds %llu bytes, the result has %llu", kDestName[small], (unsigned long long)dst[small].cap,
-                  (unsigned long long)total[small]);
-    return SCFQ_EARG;
-  }
-  return SCFQ_OK;
-}
-
-// after a failure kernels that read the second input may still be queued on the first one's stream (as fq-merge's)
-int finish(scfq_scratch::ResidentInput& in1, int rc) {
-  if (rc != SCFQ_OK) (void)hipStreamSynchronize(in1.stream);
-  return rc;
+  return put.verdict;      // (SCFQ_EARG for an output that is too small: place_outputs has left the text)
 }
 
 struct OwnTable {          // the table of the two-pass form
@@ -683,8 +571,8 @@ int scfq_norm_buffers(const scfq_kcount* table, const void* r1, uint64_t n1, con
                    bins, stats, in1.stream);
   if (rc) return finish(in1, rc);
   if (!direct) {
-    for (int x = 0; x < 2; ++x)
-      if (own[x].p) SCFQ_SCRATCH_CHK(g_nerr, hipMemcpyAsync(dst[x].p, own[x].p, x == 0 ? stats->out1_bytes : stats->out2_bytes, hipMemcpyDeviceToHost, in1.stream));
+    const uint64_t bytes[2] = {stats->out1_bytes, stats->out2_bytes};
+    if ((rc = scfq_reads::outputs_to_host(2, dst, own, bytes, in1.stream, g_nerr))) return rc;
     SCFQ_SCRATCH_CHK(g_nerr, hipStreamSynchronize(in1.stream));
   }
   for (DevBuf& o : own) o.drop();
@@ -731,14 +619,8 @@ int scfq_norm_files(const scfq_kcount* table, const char* path1, const char* pat
     SCFQ_SCRATCH_CHK(g_nerr, hipMemcpyAsync(recs_host, recs_keep.p, stats->reads_in * sizeof(scfq_norm_rec), hipMemcpyDeviceToHost, in1.stream));
     SCFQ_SCRATCH_CHK(g_nerr, hipStreamSynchronize(in1.stream));
   }
-  if (!own[0].p && !own[1].p) { in1.mark_clean(); return SCFQ_OK; }
-  // one output after the other, each in full: HBM -> two pinned buffers -> write()
-  scfq_fdwrite::Pinned pinned;
-  if ((rc = pinned.init(g_nerr))) return finish(in1, rc);
   const uint64_t bytes[2] = {stats->out1_bytes, stats->out2_bytes};
-  for (int x = 0; x < 2; ++x)
-    if (own[x].p && (rc = pinned.device_to_fd(own[x].as<uint8_t>(), bytes[x], fd[x], in1.stream, g_nerr))) return finish(in1, rc);
-  return SCFQ_OK;
+  return scfq_reads::outputs_to_fds(2, own, bytes, fd, in1, g_nerr);
 }
 
 }  // extern "C"

@@ -27,7 +27,6 @@
 //       exclusive scans       one per output over the groups, each with a last entry that is the output's size
 //   U5  ru_write              a wave per group echoes the kept records (sc_write's shape)
 // U5 compares the two totals with the capacities before it stores anything.  Everything is integer / byte work; there is no CPU fallback.
-// (text_span, echo_len and echo_record repeat scfq_trim.hip's: sharing them would change that file, whose kernels stay as they are.)
 #include "../../include/sc_fqcount.h"
 #include "../../include/sc_fqcount_debug.h"
 
@@ -35,11 +34,8 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
-#include "scfq_fdwrite.hpp"
 #include "scfq_hdrhash.hpp"
-#include "scfq_overlap.hpp"
-#include "scfq_record_device.hpp"
-#include "scfq_scratch.hpp"
+#include "scfq_reads_host.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -55,11 +51,14 @@ constexpr uint32_t kStages = 7;
 thread_local char g_rerr[scfq_scratch::kErrBytes] = "";
 thread_local double g_stage_ms[kStages] = {0, 0, 0, 0, 0, 0, 0};
 
-using scfq_scratch::DevBuf;
+using scfq_reads::Dest;
+using scfq_reads::DevBuf;
+using scfq_reads::finish;
+using scfq_reads::Mode;
 
 constexpr uint32_t kLanes = 8;                 // lanes of a group: one unit of U1, one candidate of U3
 constexpr uint32_t kMaxBlocks = 8192;          // of U1 and U3: the blocks stride
-constexpr uint32_t kGroup = 32;                // units of a group: one wave of U5, one entry of the scans
+constexpr uint32_t kGroup = kRecGroup;         // units of a group: one wave of U5, one entry of the scans
 constexpr uint32_t kWaves = 4;                 // groups of a block of U5
 constexpr uint32_t kDefaultHashBits = 40;      // (five radix passes instead of eight; measured beside 32 and 64: DESIGN.md §fq-rmdup)
 constexpr uint64_t kSeed = 0x5DEECE66D1CE4E5Bull;
@@ -67,29 +66,10 @@ constexpr uint64_t kSeed = 0x5DEECE66D1CE4E5Bull;
 // the counters of U4; the histogram follows them
 enum { kUnitsOut = 0, kDupClasses, kBasesIn, kBasesOut, kMaxCopies, kCounters };
 
-struct RuInput {          // one input: the bytes and their line index
-  const uint8_t* base;
-  uint64_t n;
-  const uint64_t* line_off;
-  uint64_t lines;
-  bool has_cr;
-};
-
-struct RuOut {            // one output: where it goes (nullptr: nowhere) and what it holds
-  uint8_t* p;
-  uint64_t cap;
-};
-
 struct RuPlan {           // where the units are: record u * stride of a, record u * stride + second of b
   uint64_t stride, second, units;
   uint32_t paired, swapped, prefix;
 };
-
-// the text of line j (a line the input does not have is empty)
-__device__ __forceinline__ void text_span(const RuInput& in, uint64_t j, uint64_t& s, uint64_t& e) {
-  s = e = 0;
-  if (j < in.lines) line_span(in.base, in.n, in.line_off, j, s, e, in.has_cr);
-}
 
 // a key: len bytes at p, of which `room` bytes (>= len) lie inside the input
 struct RuKey {
@@ -97,7 +77,7 @@ struct RuKey {
   uint64_t len, room;
 };
 
-__device__ __forceinline__ RuKey key_of(const RuInput& in, uint64_t record, uint32_t prefix) {
+__device__ __forceinline__ RuKey key_of(const RecInput& in, uint64_t record, uint32_t prefix) {
   uint64_t s, e;
   text_span(in, 4 * record + 1, s, e);
   uint64_t len = e - s;
@@ -105,7 +85,7 @@ __device__ __forceinline__ RuKey key_of(const RuInput& in, uint64_t record, uint
   return RuKey{in.base + s, len, in.n - s};
 }
 
-__device__ __forceinline__ RuKey mate_key(const RuInput& a, const RuInput& b, const RuPlan& pl, uint64_t u, uint32_t mate) {
+__device__ __forceinline__ RuKey mate_key(const RecInput& a, const RecInput& b, const RuPlan& pl, uint64_t u, uint32_t mate) {
   return mate ? key_of(b, u * pl.stride + pl.second, pl.prefix) : key_of(a, pl.paired ? u * pl.stride : u, pl.prefix);
 }
 
@@ -154,7 +134,7 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
 }
 
 // U1
-__global__ __launch_bounds__(256) void ru_hash(RuInput a, RuInput b, RuPlan pl, uint32_t hash_bits, uint64_t* keys, uint32_t* idx) {
+__global__ __launch_bounds__(256) void ru_hash(RecInput a, RecInput b, RuPlan pl, uint32_t hash_bits, uint64_t* keys, uint32_t* idx) {
   const uint32_t g = threadIdx.x & (kLanes - 1);
   const uint64_t per_step = (uint64_t)gridDim.x * (256 / kLanes);
   const uint64_t steps = (pl.units + per_step - 1) / per_step;            // (the same for every lane: the shuffles are never divergent)
@@ -223,7 +203,7 @@ __device__ __forceinline__ bool group_differs(const RuKey& x, const RuKey& y, ui
 }
 
 // U3.  cand: entries t of the list; head[t]: the entry that starts t's run
-__global__ __launch_bounds__(256) void ru_compare(RuInput a, RuInput b, RuPlan pl, const uint32_t* idx_sorted, const uint32_t* list, const uint32_t* head,
+__global__ __launch_bounds__(256) void ru_compare(RecInput a, RecInput b, RuPlan pl, const uint32_t* idx_sorted, const uint32_t* list, const uint32_t* head,
                                                  const uint32_t* cand, const uint32_t* n_cand, uint32_t* rep, uint8_t* left, unsigned long long* collisions) {
   __shared__ uint32_t wave_miss[4];
   const uint32_t g = threadIdx.x & (kLanes - 1), lane = threadIdx.x & 63;
@@ -284,44 +264,13 @@ __global__ __launch_bounds__(256) void ru_class_sizes(const uint32_t* idx_sorted
   }
 }
 
-// bytes record i echoes: its lines 4i .. min(4i+3, lines-1), each text + '\n' (dd_record_lengths' rule)
-__device__ __forceinline__ uint64_t echo_len(const RuInput& in, uint64_t i) {
-  if (4 * i >= in.lines) return 0;
-  if (!in.has_cr) {
-    const uint64_t j1 = (4 * i + 4 < in.lines) ? 4 * i + 4 : in.lines;
-    return in.line_off[j1] - in.line_off[4 * i];
-  }
-  uint64_t total = 0;
-  for (uint64_t j = 4 * i; j < 4 * i + 4 && j < in.lines; ++j) {
-    uint64_t s, e;
-    line_span(in.base, in.n, in.line_off, j, s, e);
-    total += e - s + 1;
-  }
-  return total;
-}
-
-// record i of `in` echoed to dst, len bytes (dd_gather's rule: one copy when the echo is the record's own bytes)
-__device__ __forceinline__ void echo_record(const RuInput& in, uint64_t i, uint8_t* dst, uint64_t len, uint32_t lane) {
-  const uint64_t j0 = 4 * i, j1 = (j0 + 4 < in.lines) ? j0 + 4 : in.lines;
-  const uint64_t r0 = in.line_off[j0], r1 = in.line_off[j1];
-  if (r1 - r0 == len && r1 <= in.n) { wave_copy(dst, in.base + r0, len, lane); return; }
-  uint64_t w = 0;
-  for (uint64_t j = j0; j < j1; ++j) {
-    uint64_t s, e;
-    line_span(in.base, in.n, in.line_off, j, s, e);
-    for (uint64_t k = lane; k < e - s; k += 64) dst[w + k] = in.base[s + k];
-    if (lane == 0) dst[w + (e - s)] = '\n';
-    w += e - s + 1;
-  }
-}
-
 // what a unit adds to the two outputs if it is kept.  U4 and U5 both get it from here
 struct RuUnit {
   uint64_t len1, len2;                 // bytes for out1 and out2
   uint64_t first;                      // of len1, mate 1's record (interleaved input: mate 2's follows it)
 };
 
-__device__ __forceinline__ RuUnit unit_lengths(const RuInput& a, const RuInput& b, const RuPlan& pl, uint64_t u) {
+__device__ __forceinline__ RuUnit unit_lengths(const RecInput& a, const RecInput& b, const RuPlan& pl, uint64_t u) {
   RuUnit t = {};
   t.first = echo_len(a, pl.paired ? u * pl.stride : u);
   const uint64_t l2 = pl.paired ? echo_len(b, u * pl.stride + pl.second) : 0;
@@ -330,17 +279,10 @@ __device__ __forceinline__ RuUnit unit_lengths(const RuInput& a, const RuInput& 
   return t;
 }
 
-__device__ __forceinline__ uint64_t half_sum(uint64_t v) {      // over the 32 lanes of a half wave
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor((unsigned long long)v, o, 64);
-  return v;
-}
-
 // U4.  group_len: two arrays of n_groups + 1 entries, one after the other (the last entry of each stays 0: the scan's total).  counters:
 // kCounters words, then the SCFQ_RMDUP_HIST_BINS of the histogram.  recs: the table, or nullptr
-__global__ __launch_bounds__(256) void ru_lengths(RuInput a, RuInput b, RuPlan pl, const uint32_t* rep, const uint32_t* copies, scfq_rmdup_rec* recs,
+__global__ __launch_bounds__(256) void ru_lengths(RecInput a, RecInput b, RuPlan pl, const uint32_t* rep, const uint32_t* copies, scfq_rmdup_rec* recs,
                                                  uint64_t n_groups, uint64_t* group_len, unsigned long long* counters) {
-  static_assert(kGroup == 32, "the sums below run over the two halves of a wave");
   __shared__ uint64_t sum_sh[kCounters][4];
   __shared__ uint32_t hist_sh[SCFQ_RMDUP_HIST_BINS];
   for (uint32_t k = threadIdx.x; k < SCFQ_RMDUP_HIST_BINS; k += 256) hist_sh[k] = 0;
@@ -377,10 +319,7 @@ __global__ __launch_bounds__(256) void ru_lengths(RuInput a, RuInput b, RuPlan p
   if ((threadIdx.x & 63) == 0 && ones) atomicAdd(&hist_sh[1], (uint32_t)__popcll(ones));
   if (bin > 1) atomicAdd(&hist_sh[bin], 1u);
 #pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const uint64_t s = half_sum(len[k]);
-    if ((threadIdx.x & 31) == 0 && u < pl.units) group_len[(uint64_t)k * (n_groups + 1) + u / kGroup] = s;
-  }
+  for (int k = 0; k < 2; ++k) store_group_len(len[k], k, u, pl.units, n_groups, group_len);
   // the statistics: ONE atomic per block and counter (dd_count_marks: an atomic per wave on one address costs more than the kernel)
 #pragma unroll
   for (int k = 0; k < kCounters; ++k) {
@@ -402,17 +341,12 @@ __global__ __launch_bounds__(256) void ru_lengths(RuInput a, RuInput b, RuPlan p
     if (hist_sh[k]) atomicAdd(&counters[kCounters + k], (unsigned long long)hist_sh[k]);
 }
 
-__device__ __forceinline__ uint64_t bcast(uint64_t v, uint32_t from) { return (uint64_t)__shfl((unsigned long long)v, (int)from, 64); }
-
 // U5.  group_off: the two scanned arrays of U4's layout
-__global__ __launch_bounds__(64 * kWaves) void ru_write(RuInput a, RuInput b, RuPlan pl, const uint32_t* rep, uint64_t n_groups, const uint64_t* group_off,
-                                                       RuOut o1, RuOut o2) {
+__global__ __launch_bounds__(64 * kWaves) void ru_write(RecInput a, RecInput b, RuPlan pl, const uint32_t* rep, uint64_t n_groups, const uint64_t* group_off,
+                                                       RecOut o1, RecOut o2) {
   const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const uint64_t* off_1 = group_off;
-  const uint64_t* off_2 = group_off + (n_groups + 1);
-  // (each scan's last entry is its output's size: when one is more than its output holds, nothing is written to either)
-  const bool fits = (!o1.p || off_1[n_groups] <= o1.cap) && (!o2.p || off_2[n_groups] <= o2.cap);
-  if (!fits) return;
+  // (when one result is more than its output holds, nothing is written to either)
+  if (!(output_fits(o1, 0, n_groups, group_off) && output_fits(o2, 1, n_groups, group_off))) return;
   const uint64_t g = (uint64_t)blockIdx.x * kWaves + wave;
   if (g >= n_groups) return;
   const uint64_t u0 = g * kGroup;
@@ -420,18 +354,13 @@ __global__ __launch_bounds__(64 * kWaves) void ru_write(RuInput a, RuInput b, Ru
   RuUnit mine = {};
   uint32_t kept = 0;
   if (lane < count && rep[u0 + lane] == (uint32_t)(u0 + lane)) { mine = unit_lengths(a, b, pl, u0 + lane); kept = 1; }
-  // where the unit of this lane goes: the group's offsets and the lengths of the units in front of it
-  uint64_t at_1 = mine.len1, at_2 = mine.len2;
-#pragma unroll
-  for (int o = 1; o < (int)kGroup; o <<= 1) {
-    const uint64_t v1 = __shfl_up((unsigned long long)at_1, o, 64), v2 = __shfl_up((unsigned long long)at_2, o, 64);
-    if (lane >= (uint32_t)o) { at_1 += v1; at_2 += v2; }
-  }
-  at_1 += off_1[g] - mine.len1; at_2 += off_2[g] - mine.len2;
+  const uint64_t len[2] = {mine.len1, mine.len2};
+  uint64_t at[2];
+  place_units(len, g, n_groups, group_off, lane, at);
   const uint64_t keep_mask = __builtin_amdgcn_ballot_w64(kept != 0);
   for (uint32_t q = 0; q < count; ++q) {
     if (!((keep_mask >> q) & 1ull)) continue;                 // (wave-uniform)
-    const uint64_t l1 = bcast(mine.len1, q), l2 = bcast(mine.len2, q), first = bcast(mine.first, q), w1 = bcast(at_1, q), w2 = bcast(at_2, q);
+    const uint64_t l1 = bcast(mine.len1, q), l2 = bcast(mine.len2, q), first = bcast(mine.first, q), w1 = bcast(at[0], q), w2 = bcast(at[1], q);
     const uint64_t u = u0 + q;
     const uint64_t i1 = pl.paired ? u * pl.stride : u, i2 = u * pl.stride + pl.second;
     if (o1.p && first) echo_record(a, i1, o1.p + w1, first, lane);
@@ -464,8 +393,6 @@ bool args_ok(const scfq_rmdup_opts* opts, const scfq_rmdup_stats* st, Params& p)
   return true;
 }
 
-enum class Mode { single, two, interleaved };
-
 bool mode_ok(const Params& prm, bool second, bool out2, const char* what, Mode& mode) {
   const bool interleaved = (prm.flags & SCFQ_RMDUP_INTERLEAVED) != 0;
   if (interleaved && second) { std::snprintf(g_rerr, sizeof g_rerr, "interleaved input takes no second %s", what); return false; }
@@ -477,11 +404,6 @@ bool mode_ok(const Params& prm, bool second, bool out2, const char* what, Mode& 
   if (mode != Mode::two && out2) { std::snprintf(g_rerr, sizeof g_rerr, "one input has no second output (out2)"); return false; }
   return true;
 }
-
-// one output of a call: `want` it, and then the caller's device memory (p, cap) or, with own_outputs, pool memory that rmdup_device
-// takes by the size the scan reports (own[k]; cap is then the caller's host capacity, checked here all the same)
-struct Dest { uint8_t* p; uint64_t cap; bool want; };
-const char* const kDestName[2] = {"out1", "out2"};
 
 // recs_dev / recs_cap: the caller's per-unit table in device memory, or nullptr; want_recs with check_recs: a table of recs_cap entries is
 // wanted wherever it lives, and one that is too small is an error once the statistics are complete.  recs_keep: where the table stays
@@ -498,34 +420,23 @@ int rmdup_device(const uint8_t* d1, uint64_t n1, const uint8_t* d2, uint64_t n2,
   scfq_overlap::Indexed ix;
   int rc = SCFQ_OK;
   double index_ms = 0;
-  if (paired) {
-    rc = scfq_overlap::index_inputs(d1, n1, d2, n2, interleaved, stream, g_rerr, ix, &index_ms);
-  } else {
-    // single-end input: K5 directly
-    if ((rc = scfq_scratch::build_line_index(d1, n1, stream, g_rerr, ix.off1, &ix.lines1, &ix.cr1))) return rc;
-    ix.reads1 = (ix.lines1 + 3) / 4;
-    if (ix.reads1 >= (1ull << 31)) { std::snprintf(g_rerr, sizeof g_rerr, "more than 2^31 records in one input"); rc = SCFQ_EARG; }
-  }
-  st->lines1 = ix.lines1; st->lines2 = ix.lines2;
-  st->reads1 = ix.reads1; st->reads2 = ix.reads2;
-  if (rc) return rc;
-  st->pairs = ix.pairs;
-  st->unpaired = ix.unpaired;
-  const uint64_t units = paired ? ix.pairs : ix.reads1;
+  uint64_t units = 0, reads = 0;
+  if ((rc = scfq_reads::index_units(d1, n1, d2, n2, mode, stream, g_rerr, ix, &index_ms, st, &units, &reads))) return rc;
   st->units_in = units;
-  st->reads_in = paired ? 2 * units : units;
+  st->reads_in = reads;
   const bool recs_small = check_recs && want_recs && recs_cap < units;
   if (units == 0) return SCFQ_OK;           // (two empty outputs: they fit into anything)
-  const uint64_t n_groups = (units + kGroup - 1) / kGroup, row = n_groups + 1;
+  const uint64_t n_groups = (units + kGroup - 1) / kGroup;
   const bool to_caller = recs_dev && !recs_small;
   const bool make_recs = want_recs && !recs_small;
   constexpr size_t kWordsOut = kCounters + SCFQ_RMDUP_HIST_BINS;
   DevBuf keys, keys2, idx, idx2, rep, copies, start_at, head, cand, left, list[2], words, group_len, group_off, counters, tmp;
+  scfq_reads::GroupScan gs(2, n_groups, group_len, group_off, stream, g_rerr);
   if ((make_recs && !to_caller && (rc = recs_keep.alloc(units * sizeof(scfq_rmdup_rec), stream, g_rerr))) || (rc = keys.alloc(units * 8, stream, g_rerr)) ||
       (rc = keys2.alloc(units * 8, stream, g_rerr)) || (rc = idx.alloc(units * 4, stream, g_rerr)) || (rc = idx2.alloc(units * 4, stream, g_rerr)) ||
       (rc = rep.alloc(units * 4, stream, g_rerr)) || (rc = copies.alloc(units * 4, stream, g_rerr)) || (rc = start_at.alloc(units * 4, stream, g_rerr)) ||
       (rc = head.alloc(units * 4, stream, g_rerr)) || (rc = cand.alloc(units * 4, stream, g_rerr)) || (rc = left.alloc(units, stream, g_rerr)) ||
-      (rc = words.alloc(32, stream, g_rerr)) || (rc = group_len.alloc(2 * row * 8, stream, g_rerr)) || (rc = group_off.alloc(2 * row * 8, stream, g_rerr)) ||
+      (rc = words.alloc(32, stream, g_rerr)) || (rc = gs.alloc()) ||
       (rc = counters.alloc(kWordsOut * 8, stream, g_rerr)))
     return rc;
   scfq_rmdup_rec* const recs = to_caller ? recs_dev : (make_recs ? recs_keep.as<scfq_rmdup_rec>() : nullptr);
@@ -536,8 +447,7 @@ int rmdup_device(const uint8_t* d1, uint64_t n1, const uint8_t* d2, uint64_t n2,
   size_t sort_bytes = 0, scan_bytes = 0, max_bytes = 0, select_bytes = 0;
   SCFQ_SCRATCH_CHK(g_rerr, rocprim::radix_sort_pairs(nullptr, sort_bytes, keys.as<uint64_t>(), keys2.as<uint64_t>(), idx.as<uint32_t>(), idx2.as<uint32_t>(),
                                                      (size_t)units, 0u, prm.hash_bits, stream));
-  SCFQ_SCRATCH_CHK(g_rerr, rocprim::exclusive_scan(nullptr, scan_bytes, group_len.as<uint64_t>(), group_off.as<uint64_t>(), (uint64_t)0, (size_t)row,
-                                                   rocprim::plus<uint64_t>(), stream));
+  if ((rc = gs.scratch_bytes(&scan_bytes))) return rc;
   SCFQ_SCRATCH_CHK(g_rerr, rocprim::inclusive_scan(nullptr, max_bytes, start_at.as<uint32_t>(), head.as<uint32_t>(), (size_t)units, rocprim::maximum<uint32_t>(), stream));
   SCFQ_SCRATCH_CHK(g_rerr, rocprim::select(nullptr, select_bytes, rocprim::counting_iterator<uint32_t>(0), left.as<uint8_t>(), cand.as<uint32_t>(), n_left,
                                            (size_t)units, stream));
@@ -546,11 +456,11 @@ int rmdup_device(const uint8_t* d1, uint64_t n1, const uint8_t* d2, uint64_t n2,
   static const bool timing = scfq_scratch::env_switch("SCFQ_RMDUP_TIMING");
   scfq_scratch::StageClock clk(stream, timing), clk2(stream, timing);
   SCFQ_SCRATCH_CHK(g_rerr, hipMemsetAsync(counters.p, 0, kWordsOut * 8, stream));
-  SCFQ_SCRATCH_CHK(g_rerr, hipMemsetAsync(group_len.p, 0, 2 * row * 8, stream));       // (each scan's last input: its last output is the total)
+  if ((rc = gs.zero())) return rc;
   SCFQ_SCRATCH_CHK(g_rerr, hipMemsetAsync(copies.p, 0, units * 4, stream));
   SCFQ_SCRATCH_CHK(g_rerr, hipMemsetAsync(words.p, 0, 32, stream));
-  const RuInput a = {d1, n1, ix.off1.as<uint64_t>(), ix.lines1, ix.cr1};
-  const RuInput b = mode == Mode::two ? RuInput{d2, n2, ix.off2.as<uint64_t>(), ix.lines2, ix.cr2} : a;
+  const RecInput a = {d1, n1, ix.off1.as<uint64_t>(), ix.lines1, ix.cr1};
+  const RecInput b = mode == Mode::two ? RecInput{d2, n2, ix.off2.as<uint64_t>(), ix.lines2, ix.cr2} : a;
   const RuPlan pl = {interleaved ? 2ull : 1ull, interleaved ? 1ull : 0ull, units, paired ? 1u : 0u, (prm.flags & SCFQ_RMDUP_SWAPPED) ? 1u : 0u, prm.prefix};
   auto group_blocks = [](uint64_t items) { return dim3((unsigned)std::min<uint64_t>((items + 256 / kLanes - 1) / (256 / kLanes), kMaxBlocks)); };
   clk.mark(0);
@@ -593,23 +503,19 @@ int rmdup_device(const uint8_t* d1, uint64_t n1, const uint8_t* d2, uint64_t n2,
   clk.mark(4);
   clk2.mark(0);
   hipLaunchKernelGGL(ru_lengths, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, stream, a, b, pl, rep.as<uint32_t>(), copies.as<uint32_t>(), recs, n_groups,
-                     group_len.as<uint64_t>(), counters.as<unsigned long long>());
+                     gs.len(), counters.as<unsigned long long>());
   SCFQ_SCRATCH_CHK(g_rerr, hipGetLastError());
-  for (uint64_t k = 0; k < 2; ++k) {
-    size_t bytes = tmp_bytes;
-    SCFQ_SCRATCH_CHK(g_rerr, rocprim::exclusive_scan(tmp.p, bytes, group_len.as<uint64_t>() + k * row, group_off.as<uint64_t>() + k * row, (uint64_t)0, (size_t)row,
-                                                     rocprim::plus<uint64_t>(), stream));
-  }
+  if ((rc = gs.scan(tmp.p, tmp_bytes))) return rc;
   clk2.mark(1);
   // the sizes and the statistics come back first: pool memory for the outputs is taken to fit, and a caller's buffer that is too small
   // is known here
-  uint64_t total[2] = {0, 0}, coll = 0;
+  uint64_t coll = 0;
   std::vector<uint64_t> h(kWordsOut);
-  for (uint64_t k = 0; k < 2; ++k) SCFQ_SCRATCH_CHK(g_rerr, hipMemcpyAsync(&total[k], group_off.as<uint64_t>() + k * row + n_groups, 8, hipMemcpyDeviceToHost, stream));
+  if ((rc = gs.read_totals())) return rc;
   SCFQ_SCRATCH_CHK(g_rerr, hipMemcpyAsync(h.data(), counters.p, kWordsOut * 8, hipMemcpyDeviceToHost, stream));
   SCFQ_SCRATCH_CHK(g_rerr, hipMemcpyAsync(&coll, collisions, 8, hipMemcpyDeviceToHost, stream));
   SCFQ_SCRATCH_CHK(g_rerr, hipStreamSynchronize(stream));
-  st->out1_bytes = total[0]; st->out2_bytes = total[1];
+  st->out1_bytes = gs.total[0]; st->out2_bytes = gs.total[1];
   st->units_out = h[kUnitsOut];
   st->reads_out = paired ? 2 * h[kUnitsOut] : h[kUnitsOut];
   st->duplicate_units = units - h[kUnitsOut];
@@ -619,21 +525,11 @@ int rmdup_device(const uint8_t* d1, uint64_t n1, const uint8_t* d2, uint64_t n2,
   st->collisions = coll;
   st->rounds = rounds;
   if (hist_host) std::memcpy(hist_host, h.data() + kCounters, SCFQ_RMDUP_HIST_BINS * 8);
-  int small = -1;
-  for (int k = 1; k >= 0; --k)
-    if (check_caps && dst[k].want && total[k] > dst[k].cap) small = k;
-  RuOut out[2];
-  for (int k = 0; k < 2; ++k) {
-    out[k] = RuOut{nullptr, 0};
-    if (!dst[k].want || recs_small) continue;
-    if (!own_outputs) { out[k] = RuOut{dst[k].p, dst[k].cap}; continue; }      // (too small or not: U5 looks at the totals itself)
-    if (small >= 0 || total[k] == 0) continue;
-    if ((rc = own[k].alloc(total[k], stream, g_rerr))) return rc;
-    out[k] = RuOut{own[k].as<uint8_t>(), total[k]};
-  }
-  if (out[0].p || out[1].p) {
+  const scfq_reads::Placement put = scfq_reads::place_outputs(gs, scfq_reads::kOutNames, dst, own_outputs, check_caps, recs_small, own, stream, g_rerr);
+  if (put.rc) return put.rc;
+  if (put.out[0].p || put.out[1].p) {
     hipLaunchKernelGGL(ru_write, dim3((unsigned)((n_groups + kWaves - 1) / kWaves)), dim3(64 * kWaves), 0, stream, a, b, pl, rep.as<uint32_t>(), n_groups,
-                       group_off.as<uint64_t>(), out[0], out[1]);
+                       gs.off(), put.out[0], put.out[1]);
     SCFQ_SCRATCH_CHK(g_rerr, hipGetLastError());
   }
   clk2.mark(2);
@@ -646,28 +542,7 @@ int rmdup_device(const uint8_t* d1, uint64_t n1, const uint8_t* d2, uint64_t n2,
     std::snprintf(g_rerr, sizeof g_rerr, "the per-unit table holds %llu entries, the input has %llu units", (unsigned long long)recs_cap, (unsigned long long)units);
     return SCFQ_EARG;
   }
-  if (small >= 0) {
-    std::snprintf(g_rerr, sizeof g_rerr, "the %s output holds %llu bytes, the result has %llu", kDestName[small], (unsigned long long)dst[small].cap,
-                  (unsigned long long)total[small]);
-    return SCFQ_EARG;
-  }
-  return SCFQ_OK;
-}
-
-// after a failure kernels that read the second input may still be queued on the first one's stream: they are waited for before the
-// second input's memory goes back (as fq-merge's)
-int finish(scfq_scratch::ResidentInput& in1, int rc) {
-  if (rc != SCFQ_OK) (void)hipStreamSynchronize(in1.stream);
-  return rc;
-}
-
-int copy_text(const char* text, int m, char* buf, uint64_t cap) {
-  if (buf && cap) {
-    const uint64_t ncopy = ((uint64_t)m < cap - 1) ? (uint64_t)m : cap - 1;
-    std::memcpy(buf, text, ncopy);
-    buf[ncopy] = 0;
-  }
-  return m;
+  return put.verdict;      // (SCFQ_EARG for an output that is too small: place_outputs has left the text)
 }
 
 }  // namespace
@@ -684,7 +559,7 @@ int scfq_debug_rmdup_stages(double* ms, uint32_t cap) {
 int scfq_format_rmdup_stats_tsv(const scfq_rmdup_stats* s, int header, char* buf, uint64_t cap) {
   static const char kNames[] = "units_in\tunits_out\tduplicate_units\tduplicate_pct\tduplicated_classes\tmax_copies\treads_in\treads_out\tpairs\tunpaired\t"
                                "bases_in\tbases_out\tout1_bytes\tout2_bytes";
-  if (header) return copy_text(kNames, (int)sizeof kNames - 1, buf, cap);
+  if (header) return scfq_reads::copy_text(kNames, (int)sizeof kNames - 1, buf, cap);
   if (!s) return SCFQ_EARG;
   // floor(10000 d / u): the product may pass 64 bits
   uint64_t pct = 0;
@@ -698,15 +573,15 @@ int scfq_format_rmdup_stats_tsv(const scfq_rmdup_stats* s, int header, char* buf
   int m = std::snprintf(tmp, sizeof tmp, "%llu\t%llu\t%llu\t%llu.%02llu", (unsigned long long)s->units_in, (unsigned long long)s->units_out,
                         (unsigned long long)s->duplicate_units, (unsigned long long)(pct / 100), (unsigned long long)(pct % 100));
   for (const uint64_t x : tail) m += std::snprintf(tmp + m, sizeof tmp - m, "\t%llu", (unsigned long long)x);
-  return copy_text(tmp, m, buf, cap);
+  return scfq_reads::copy_text(tmp, m, buf, cap);
 }
 
 int scfq_format_rmdup_rec_tsv(uint64_t unit, const scfq_rmdup_rec* rec, char* buf, uint64_t cap) {
   static const char kNames[] = "unit\trep\tcopies";
-  if (!rec) return copy_text(kNames, (int)sizeof kNames - 1, buf, cap);
+  if (!rec) return scfq_reads::copy_text(kNames, (int)sizeof kNames - 1, buf, cap);
   char tmp[96];
   const int m = std::snprintf(tmp, sizeof tmp, "%llu\t%u\t%u", (unsigned long long)unit, (unsigned)rec->rep, (unsigned)rec->copies);
-  return copy_text(tmp, m, buf, cap);
+  return scfq_reads::copy_text(tmp, m, buf, cap);
 }
 
 int scfq_rmdup_buffers(const void* r1, uint64_t n1, const void* r2, uint64_t n2, int is_device, const scfq_rmdup_opts* opts, scfq_rmdup_rec* recs, uint64_t recs_cap,
@@ -731,8 +606,8 @@ int scfq_rmdup_buffers(const void* r1, uint64_t n1, const void* r2, uint64_t n2,
   if (recs && !recs_on_device && stats->units_in)
     SCFQ_SCRATCH_CHK(g_rerr, hipMemcpyAsync(recs, recs_keep.p, stats->units_in * sizeof(scfq_rmdup_rec), hipMemcpyDeviceToHost, in1.stream));
   if (!direct) {
-    for (int k = 0; k < 2; ++k)
-      if (own[k].p) SCFQ_SCRATCH_CHK(g_rerr, hipMemcpyAsync(dst[k].p, own[k].p, k == 0 ? stats->out1_bytes : stats->out2_bytes, hipMemcpyDeviceToHost, in1.stream));
+    const uint64_t bytes[2] = {stats->out1_bytes, stats->out2_bytes};
+    if ((rc = scfq_reads::outputs_to_host(2, dst, own, bytes, in1.stream, g_rerr))) return rc;
   }
   SCFQ_SCRATCH_CHK(g_rerr, hipStreamSynchronize(in1.stream));
   for (DevBuf& o : own) o.drop();
@@ -777,14 +652,8 @@ int scfq_rmdup_files(const char* path1, const char* path2, const scfq_rmdup_opts
       }
     }
   }
-  if (!own[0].p && !own[1].p) { in1.mark_clean(); return SCFQ_OK; }
-  // one output after the other, each in full: HBM -> two pinned buffers -> write()
-  scfq_fdwrite::Pinned pinned;
-  if ((rc = pinned.init(g_rerr))) return finish(in1, rc);
   const uint64_t bytes[2] = {stats->out1_bytes, stats->out2_bytes};
-  for (int k = 0; k < 2; ++k)
-    if (own[k].p && (rc = pinned.device_to_fd(own[k].as<uint8_t>(), bytes[k], fd[k], in1.stream, g_rerr))) return finish(in1, rc);
-  return SCFQ_OK;
+  return scfq_reads::outputs_to_fds(2, own, bytes, fd, in1, g_rerr);
 }
 
 }  // extern "C"

@@ -26,7 +26,6 @@
 // Every probe loop, in S1 and in S2, makes at most `slots` steps, and the host makes the table larger than the number of windows, so
 // that an empty slot always exists: a table that cannot hold the keys is refused before any launch (pick_slots) and, should an insert
 // run out of steps all the same, S1 raises a flag that fails the build.  There is no CPU fallback.
-// (text_span, echo_len and echo_record repeat scfq_trim.hip's: sharing them would change that file, whose kernels stay as they are.)
 #include "../../include/sc_fqcount.h"
 #include "../../include/sc_fqcount_debug.h"
 
@@ -34,10 +33,7 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
-#include "scfq_fdwrite.hpp"
-#include "scfq_overlap.hpp"
-#include "scfq_record_device.hpp"
-#include "scfq_scratch.hpp"
+#include "scfq_reads_host.hpp"
 #include "scfq_screen_host.hpp"
 
 #include <algorithm>
@@ -72,13 +68,16 @@ namespace {
 thread_local char g_serr[scfq_scratch::kErrBytes] = "";
 thread_local double g_stage_ms[4] = {0, 0, 0, 0};
 
-using scfq_scratch::DevBuf;
+using scfq_reads::Dest;
+using scfq_reads::DevBuf;
+using scfq_reads::finish;
+using scfq_reads::Mode;
 
 constexpr uint64_t kEmpty = ~0ull;
 constexpr uint32_t kRun = 64;                            // window starts of a thread of S1
 constexpr uint32_t kScWaves = 4;                         // reads a block of S2 works on at a time; groups of a block of S4
 constexpr uint32_t kScMaxBlocks = 2048;                  // of S2
-constexpr uint32_t kScGroup = 32;                        // reads or pairs of a group: one wave of S4, one entry of the scans
+constexpr uint32_t kScGroup = kRecGroup;                 // reads or pairs of a group: one wave of S4, one entry of the scans
 constexpr uint32_t kChunk = 512;                         // window starts of a chunk of S2
 constexpr uint32_t kCodeWords = 18, kInvWords = 10;      // 64-bit words of a wave's two planes: 9 rounds of 64 bases, and the word behind
 constexpr uint32_t kWaveLds = (kCodeWords + kInvWords) * 8 + SCFQ_SCREEN_MAX_REFS * 4;      // bytes of LDS of a wave of S2
@@ -153,19 +152,6 @@ __global__ __launch_bounds__(256) void sc_count_slots(const unsigned long long* 
   if (threadIdx.x < 2 * SCFQ_SCREEN_MAX_REFS + 1 && c_sh[threadIdx.x]) atomicAdd(&counts[threadIdx.x], c_sh[threadIdx.x]);
 }
 
-struct ScInput {          // one input: the bytes and their line index
-  const uint8_t* base;
-  uint64_t n;
-  const uint64_t* line_off;
-  uint64_t lines;
-  bool has_cr;
-};
-
-struct ScOut {            // one output: where it goes (nullptr: nowhere) and what it holds
-  uint8_t* p;
-  uint64_t cap;
-};
-
 struct ScTable {          // the index as S2 sees it
   const unsigned long long* keys;
   const uint32_t* masks;
@@ -175,12 +161,6 @@ struct ScTable {          // the index as S2 sees it
   uint32_t k;
   uint32_t min_hits, min_hit_pct;
 };
-
-// the text of line j (a line the input does not have is empty)
-__device__ __forceinline__ void text_span(const ScInput& in, uint64_t j, uint64_t& s, uint64_t& e) {
-  s = e = 0;
-  if (j < in.lines) line_span(in.base, in.n, in.line_off, j, s, e, in.has_cr);
-}
 
 // what a wave has written to LDS is read by its other lanes behind this
 __device__ __forceinline__ void wave_lds_sync() {
@@ -199,7 +179,7 @@ __device__ __forceinline__ uint64_t rev_comp(uint64_t f, uint32_t k) {
 
 // S2.  Read r is record r of `a` (single-end: paired = 0) or mate r & 1 of pair r >> 1: record p * stride of a, record p * stride + second
 // of b.  Dynamic LDS: the bitmap (t.filter_bits / 8 bytes, or nothing), then kWaveLds bytes per wave.
-__global__ __launch_bounds__(64 * kScWaves) void sc_lookup(ScInput a, ScInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t reads, ScTable t,
+__global__ __launch_bounds__(64 * kScWaves) void sc_lookup(RecInput a, RecInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t reads, ScTable t,
                                                           scfq_screen_rec* recs, unsigned long long* ref_hits) {
   extern __shared__ uint64_t lds64[];
   const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -218,7 +198,7 @@ __global__ __launch_bounds__(64 * kScWaves) void sc_lookup(ScInput a, ScInput b,
     if (r >= reads) continue;
     const uint64_t p = paired ? r >> 1 : r;
     const bool mate2 = paired && (r & 1);
-    const ScInput& in = mate2 ? b : a;
+    const RecInput& in = mate2 ? b : a;
     const uint64_t i = paired ? p * stride + (mate2 ? second : 0) : r;
     uint64_t ss, se;
     text_span(in, 4 * i + 1, ss, se);
@@ -291,37 +271,6 @@ __global__ __launch_bounds__(64 * kScWaves) void sc_lookup(ScInput a, ScInput b,
   }
 }
 
-// bytes record i echoes: its lines 4i .. min(4i+3, lines-1), each text + '\n' (dd_record_lengths' rule)
-__device__ __forceinline__ uint64_t echo_len(const ScInput& in, uint64_t i) {
-  if (4 * i >= in.lines) return 0;
-  if (!in.has_cr) {
-    const uint64_t j1 = (4 * i + 4 < in.lines) ? 4 * i + 4 : in.lines;
-    return in.line_off[j1] - in.line_off[4 * i];
-  }
-  uint64_t total = 0;
-  for (uint64_t j = 4 * i; j < 4 * i + 4 && j < in.lines; ++j) {
-    uint64_t s, e;
-    line_span(in.base, in.n, in.line_off, j, s, e);
-    total += e - s + 1;
-  }
-  return total;
-}
-
-// record i of `in` echoed to dst, len bytes (dd_gather's rule: one copy when the echo is the record's own bytes)
-__device__ __forceinline__ void echo_record(const ScInput& in, uint64_t i, uint8_t* dst, uint64_t len, uint32_t lane) {
-  const uint64_t j0 = 4 * i, j1 = (j0 + 4 < in.lines) ? j0 + 4 : in.lines;
-  const uint64_t r0 = in.line_off[j0], r1 = in.line_off[j1];
-  if (r1 - r0 == len && r1 <= in.n) { wave_copy(dst, in.base + r0, len, lane); return; }
-  uint64_t w = 0;
-  for (uint64_t j = j0; j < j1; ++j) {
-    uint64_t s, e;
-    line_span(in.base, in.n, in.line_off, j, s, e);
-    for (uint64_t x = lane; x < e - s; x += 64) dst[w + x] = in.base[s + x];
-    if (lane == 0) dst[w + (e - s)] = '\n';
-    w += e - s + 1;
-  }
-}
-
 // a unit: a single-end read, or a pair.  S3 and S4 both get it from here, so the lengths the scans saw are the lengths S4 writes
 struct ScUnit {
   uint64_t len1, len2;                 // bytes for out1 and out2 (0 for a unit that is not written)
@@ -329,7 +278,7 @@ struct ScUnit {
   bool kept;
 };
 
-__device__ __forceinline__ ScUnit look_up(const ScInput& a, const ScInput& b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t u,
+__device__ __forceinline__ ScUnit look_up(const RecInput& a, const RecInput& b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t u,
                                           const scfq_screen_rec* recs, uint32_t keep_matched) {
   ScUnit t = {};
   const bool matched = paired ? (recs[2 * u].mask | recs[2 * u + 1].mask) != 0 : recs[u].mask != 0;
@@ -342,21 +291,14 @@ __device__ __forceinline__ ScUnit look_up(const ScInput& a, const ScInput& b, ui
   return t;
 }
 
-__device__ __forceinline__ uint64_t half_sum(uint64_t v) {      // over the 32 lanes of a half wave
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor((unsigned long long)v, o, 64);
-  return v;
-}
-
 // the counters of S3
 enum { kDropped = 0, kMatchedReads, kMatchedPairs, kMulti, kShort, kBasesIn, kBasesOut, kWindows, kKmers, kHitKmers, kRefReads,
        kRefOnly = kRefReads + SCFQ_SCREEN_MAX_REFS, kRefBest = kRefOnly + SCFQ_SCREEN_MAX_REFS, kCounters = kRefBest + SCFQ_SCREEN_MAX_REFS };
 
 // S3.  group_len: two arrays of n_groups + 1 entries, one after the other (the last entry of each stays 0: the scan's total)
-__global__ __launch_bounds__(256) void sc_lengths(ScInput a, ScInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t units,
+__global__ __launch_bounds__(256) void sc_lengths(RecInput a, RecInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t units,
                                                  const scfq_screen_rec* recs, uint32_t keep_matched, uint32_t k, uint64_t n_groups, uint64_t* group_len,
                                                  unsigned long long* counters) {
-  static_assert(kScGroup == 32, "the sums below run over the two halves of a wave");
   __shared__ unsigned long long sum_sh[kCounters];
   if (threadIdx.x < kCounters) sum_sh[threadIdx.x] = 0;
   __syncthreads();
@@ -392,10 +334,7 @@ __global__ __launch_bounds__(256) void sc_lengths(ScInput a, ScInput b, uint64_t
     c[kMatchedPairs] = paired && any;
   }
 #pragma unroll
-  for (int x = 0; x < 2; ++x) {
-    const uint64_t s = half_sum(len[x]);
-    if ((threadIdx.x & 31) == 0 && live) group_len[(uint64_t)x * (n_groups + 1) + u / kScGroup] = s;
-  }
+  for (int x = 0; x < 2; ++x) store_group_len(len[x], x, u, units, n_groups, group_len);
   // the statistics: a sum per wave into LDS, then ONE atomic per block and counter.  The counts per reference are ballots
   const bool first_lane = (threadIdx.x & 63) == 0;
 #pragma unroll
@@ -422,33 +361,24 @@ __global__ __launch_bounds__(256) void sc_lengths(ScInput a, ScInput b, uint64_t
   if (threadIdx.x < kCounters && sum_sh[threadIdx.x]) atomicAdd(&counters[threadIdx.x], sum_sh[threadIdx.x]);
 }
 
-__device__ __forceinline__ uint64_t bcast(uint64_t v, uint32_t from) { return (uint64_t)__shfl((unsigned long long)v, (int)from, 64); }
-
 // S4.  group_off: the two scanned arrays of S3's layout
-__global__ __launch_bounds__(64 * kScWaves) void sc_write(ScInput a, ScInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t units,
+__global__ __launch_bounds__(64 * kScWaves) void sc_write(RecInput a, RecInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t units,
                                                          const scfq_screen_rec* recs, uint32_t keep_matched, uint64_t n_groups, const uint64_t* group_off,
-                                                         ScOut o1, ScOut o2) {
+                                                         RecOut o1, RecOut o2) {
   const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const uint64_t* off_1 = group_off;
-  const uint64_t* off_2 = group_off + (n_groups + 1);
-  // (each scan's last entry is its output's size: when one is more than its output holds, nothing is written to either)
-  const bool fits = (!o1.p || off_1[n_groups] <= o1.cap) && (!o2.p || off_2[n_groups] <= o2.cap);
-  if (!fits) return;
+  // (when one result is more than its output holds, nothing is written to either)
+  if (!(output_fits(o1, 0, n_groups, group_off) && output_fits(o2, 1, n_groups, group_off))) return;
   const uint64_t g = (uint64_t)blockIdx.x * kScWaves + wave;
   if (g >= n_groups) return;
   const uint64_t u0 = g * kScGroup;
   const uint32_t count = (uint32_t)std::min<uint64_t>(kScGroup, units - u0);
   ScUnit mine = {};
   if (lane < count) mine = look_up(a, b, stride, second, paired, u0 + lane, recs, keep_matched);
-  uint64_t at_1 = mine.len1, at_2 = mine.len2;
-#pragma unroll
-  for (int o = 1; o < (int)kScGroup; o <<= 1) {
-    const uint64_t v1 = __shfl_up((unsigned long long)at_1, o, 64), v2 = __shfl_up((unsigned long long)at_2, o, 64);
-    if (lane >= (uint32_t)o) { at_1 += v1; at_2 += v2; }
-  }
-  at_1 += off_1[g] - mine.len1; at_2 += off_2[g] - mine.len2;
+  const uint64_t len[2] = {mine.len1, mine.len2};
+  uint64_t at[2];
+  place_units(len, g, n_groups, group_off, lane, at);
   for (uint32_t q = 0; q < count; ++q) {
-    const uint64_t l1 = bcast(mine.len1, q), l2 = bcast(mine.len2, q), first = bcast(mine.first, q), w1 = bcast(at_1, q), w2 = bcast(at_2, q);
+    const uint64_t l1 = bcast(mine.len1, q), l2 = bcast(mine.len2, q), first = bcast(mine.first, q), w1 = bcast(at[0], q), w2 = bcast(at[1], q);
     if (l1 + l2 == 0) continue;                            // (a unit that is not written, or the echo of nothing)
     const uint64_t u = u0 + q;
     const uint64_t i1 = paired ? u * stride : u, i2 = u * stride + second;
@@ -482,11 +412,6 @@ bool have_index(const scfq_screen_index* index) {
   return index != nullptr;
 }
 
-enum class Mode { single, two, interleaved };
-
-struct Dest { uint8_t* p; uint64_t cap; bool want; };
-const char* const kDestName[2] = {"out1", "out2"};
-
 // recs_out / rec_cap: the caller's per-read table (device memory), or nullptr; recs_keep: where the table stays for the caller of this
 // function to copy it (the file entry point)
 int screen_device(const scfq_screen_index* ix_, const uint8_t* d1, uint64_t n1, const uint8_t* d2, uint64_t n2, Mode mode, const Params& prm,
@@ -504,41 +429,29 @@ int screen_device(const scfq_screen_index* ix_, const uint8_t* d1, uint64_t n1, 
   scfq_overlap::Indexed ix;
   int rc = SCFQ_OK;
   double index_ms = 0;
-  if (paired) {
-    rc = scfq_overlap::index_inputs(d1, n1, d2, n2, interleaved, stream, g_serr, ix, &index_ms);
-  } else {
-    if ((rc = scfq_scratch::build_line_index(d1, n1, stream, g_serr, ix.off1, &ix.lines1, &ix.cr1))) return rc;
-    ix.reads1 = (ix.lines1 + 3) / 4;
-    if (ix.reads1 >= (1ull << 31)) { std::snprintf(g_serr, sizeof g_serr, "more than 2^31 records in one input"); rc = SCFQ_EARG; }
-  }
-  st->lines1 = ix.lines1; st->lines2 = ix.lines2;
-  st->reads1 = ix.reads1; st->reads2 = ix.reads2;
-  if (rc) return rc;
-  st->pairs = ix.pairs;
-  st->unpaired = ix.unpaired;
-  const uint64_t units = paired ? ix.pairs : ix.reads1, reads = paired ? 2 * ix.pairs : ix.reads1;
+  uint64_t units = 0, reads = 0;
+  if ((rc = scfq_reads::index_units(d1, n1, d2, n2, mode, stream, g_serr, ix, &index_ms, st, &units, &reads))) return rc;
   st->reads_in = reads;
   if (check_rec_cap && recs_out && rec_cap < reads) {
     std::snprintf(g_serr, sizeof g_serr, "the per-read table holds %llu entries, the input has %llu reads", (unsigned long long)rec_cap, (unsigned long long)reads);
     return SCFQ_EARG;
   }
   if (units == 0) return SCFQ_OK;           // (two empty outputs: they fit into anything)
-  const uint64_t n_groups = (units + kScGroup - 1) / kScGroup, row = n_groups + 1;
+  const uint64_t n_groups = (units + kScGroup - 1) / kScGroup;
   DevBuf group_len, group_off, counters, tmp;
-  if ((!recs_out && (rc = recs_keep.alloc(reads * sizeof(scfq_screen_rec), stream, g_serr))) || (rc = group_len.alloc(2 * row * 8, stream, g_serr)) ||
-      (rc = group_off.alloc(2 * row * 8, stream, g_serr)) || (rc = counters.alloc((kCounters + SCFQ_SCREEN_MAX_REFS) * 8, stream, g_serr)))
+  scfq_reads::GroupScan gs(2, n_groups, group_len, group_off, stream, g_serr);
+  if ((!recs_out && (rc = recs_keep.alloc(reads * sizeof(scfq_screen_rec), stream, g_serr))) || (rc = gs.alloc()) ||
+      (rc = counters.alloc((kCounters + SCFQ_SCREEN_MAX_REFS) * 8, stream, g_serr)))
     return rc;
   scfq_screen_rec* const recs = recs_out ? recs_out : recs_keep.as<scfq_screen_rec>();
   size_t scan_bytes = 0;
-  SCFQ_SCRATCH_CHK(g_serr, rocprim::exclusive_scan(nullptr, scan_bytes, group_len.as<uint64_t>(), group_off.as<uint64_t>(), (uint64_t)0, (size_t)row,
-                                                   rocprim::plus<uint64_t>(), stream));
-  if ((rc = tmp.alloc(scan_bytes, stream, g_serr))) return rc;
+  if ((rc = gs.scratch_bytes(&scan_bytes)) || (rc = tmp.alloc(scan_bytes, stream, g_serr))) return rc;
   static const bool timing = scfq_scratch::env_switch("SCFQ_SCREEN_TIMING");
   scfq_scratch::StageClock clk(stream, timing);
   SCFQ_SCRATCH_CHK(g_serr, hipMemsetAsync(counters.p, 0, (kCounters + SCFQ_SCREEN_MAX_REFS) * 8, stream));
-  SCFQ_SCRATCH_CHK(g_serr, hipMemsetAsync(group_len.p, 0, 2 * row * 8, stream));       // (each scan's last input: its last output is the total)
-  const ScInput a = {d1, n1, ix.off1.as<uint64_t>(), ix.lines1, ix.cr1};
-  const ScInput b = mode == Mode::two ? ScInput{d2, n2, ix.off2.as<uint64_t>(), ix.lines2, ix.cr2} : a;
+  if ((rc = gs.zero())) return rc;
+  const RecInput a = {d1, n1, ix.off1.as<uint64_t>(), ix.lines1, ix.cr1};
+  const RecInput b = mode == Mode::two ? RecInput{d2, n2, ix.off2.as<uint64_t>(), ix.lines2, ix.cr2} : a;
   const uint64_t stride = interleaved ? 2 : 1, second = interleaved ? 1 : 0;
   const uint32_t keep_matched = (prm.flags & SCFQ_SCREEN_KEEP_MATCHED) ? 1u : 0u;
   const ScTable table = {reinterpret_cast<const unsigned long long*>(idx.d_keys), idx.d_masks, idx.slots, idx.d_filter, idx.filter_bits, idx.k, prm.min_hits,
@@ -552,19 +465,17 @@ int screen_device(const scfq_screen_index* ix_, const uint8_t* d1, uint64_t n1, 
   SCFQ_SCRATCH_CHK(g_serr, hipGetLastError());
   clk.mark(1);
   hipLaunchKernelGGL(sc_lengths, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, stream, a, b, stride, second, paired ? 1u : 0u, units, recs, keep_matched,
-                     idx.k, n_groups, group_len.as<uint64_t>(), counters.as<unsigned long long>());
+                     idx.k, n_groups, gs.len(), counters.as<unsigned long long>());
   SCFQ_SCRATCH_CHK(g_serr, hipGetLastError());
-  for (uint64_t x = 0; x < 2; ++x)
-    SCFQ_SCRATCH_CHK(g_serr, rocprim::exclusive_scan(tmp.p, scan_bytes, group_len.as<uint64_t>() + x * row, group_off.as<uint64_t>() + x * row, (uint64_t)0, (size_t)row,
-                                                     rocprim::plus<uint64_t>(), stream));
+  if ((rc = gs.scan(tmp.p, scan_bytes))) return rc;
   clk.mark(2);
   // the sizes and the statistics come back first: pool memory for the outputs is taken to fit, and a caller's buffer that is too small
   // is known here
-  uint64_t total[2] = {0, 0}, h[kCounters + SCFQ_SCREEN_MAX_REFS];
-  for (uint64_t x = 0; x < 2; ++x) SCFQ_SCRATCH_CHK(g_serr, hipMemcpyAsync(&total[x], group_off.as<uint64_t>() + x * row + n_groups, 8, hipMemcpyDeviceToHost, stream));
+  uint64_t h[kCounters + SCFQ_SCREEN_MAX_REFS];
+  if ((rc = gs.read_totals())) return rc;
   SCFQ_SCRATCH_CHK(g_serr, hipMemcpyAsync(h, counters.p, sizeof h, hipMemcpyDeviceToHost, stream));
   SCFQ_SCRATCH_CHK(g_serr, hipStreamSynchronize(stream));
-  st->out1_bytes = total[0]; st->out2_bytes = total[1];
+  st->out1_bytes = gs.total[0]; st->out2_bytes = gs.total[1];
   st->dropped_reads = h[kDropped]; st->reads_out = reads - h[kDropped];
   st->matched_reads = h[kMatchedReads]; st->matched_pairs = h[kMatchedPairs]; st->multi_reads = h[kMulti]; st->short_reads = h[kShort];
   st->bases_in = h[kBasesIn]; st->bases_out = h[kBasesOut];
@@ -573,21 +484,11 @@ int screen_device(const scfq_screen_index* ix_, const uint8_t* d1, uint64_t n1, 
     st->ref_reads[r] = h[kRefReads + r]; st->ref_only_reads[r] = h[kRefOnly + r]; st->ref_best_reads[r] = h[kRefBest + r];
     st->ref_kmer_hits[r] = h[kCounters + r];
   }
-  int small = -1;
-  for (int x = 1; x >= 0; --x)
-    if (check_caps && dst[x].want && total[x] > dst[x].cap) small = x;
-  ScOut out[2];
-  for (int x = 0; x < 2; ++x) {
-    out[x] = ScOut{nullptr, 0};
-    if (!dst[x].want) continue;
-    if (!own_outputs) { out[x] = ScOut{dst[x].p, dst[x].cap}; continue; }      // (too small or not: S4 looks at the totals itself)
-    if (small >= 0 || total[x] == 0) continue;
-    if ((rc = own[x].alloc(total[x], stream, g_serr))) return rc;
-    out[x] = ScOut{own[x].as<uint8_t>(), total[x]};
-  }
-  if (out[0].p || out[1].p) {
+  const scfq_reads::Placement put = scfq_reads::place_outputs(gs, scfq_reads::kOutNames, dst, own_outputs, check_caps, false, own, stream, g_serr);
+  if (put.rc) return put.rc;
+  if (put.out[0].p || put.out[1].p) {
     hipLaunchKernelGGL(sc_write, dim3((unsigned)((n_groups + kScWaves - 1) / kScWaves)), dim3(64 * kScWaves), 0, stream, a, b, stride, second, paired ? 1u : 0u,
-                       units, recs, keep_matched, n_groups, group_off.as<uint64_t>(), out[0], out[1]);
+                       units, recs, keep_matched, n_groups, gs.off(), put.out[0], put.out[1]);
     SCFQ_SCRATCH_CHK(g_serr, hipGetLastError());
   }
   clk.mark(3);
@@ -596,18 +497,7 @@ int screen_device(const scfq_screen_index* ix_, const uint8_t* d1, uint64_t n1, 
   g_stage_ms[1] = clk.between(0, 1);
   g_stage_ms[2] = clk.between(1, 2);
   g_stage_ms[3] = clk.between(2, 3);
-  if (small >= 0) {
-    std::snprintf(g_serr, sizeof g_serr, "the %s output holds %llu bytes, the result has %llu", kDestName[small], (unsigned long long)dst[small].cap,
-                  (unsigned long long)total[small]);
-    return SCFQ_EARG;
-  }
-  return SCFQ_OK;
-}
-
-// after a failure kernels that read the second input may still be queued on the first one's stream (as fq-merge's)
-int finish(scfq_scratch::ResidentInput& in1, int rc) {
-  if (rc != SCFQ_OK) (void)hipStreamSynchronize(in1.stream);
-  return rc;
+  return put.verdict;      // (SCFQ_EARG for an output that is too small: place_outputs has left the text)
 }
 
 int env_number(const char* name, int fallback) {
@@ -791,8 +681,8 @@ int scfq_screen_buffers(const scfq_screen_index* index, const void* r1, uint64_t
                      /*check_caps=*/true, stats, in1.stream);
   if (rc) return finish(in1, rc);
   if (!direct) {
-    for (int x = 0; x < 2; ++x)
-      if (own[x].p) SCFQ_SCRATCH_CHK(g_serr, hipMemcpyAsync(dst[x].p, own[x].p, x == 0 ? stats->out1_bytes : stats->out2_bytes, hipMemcpyDeviceToHost, in1.stream));
+    const uint64_t bytes[2] = {stats->out1_bytes, stats->out2_bytes};
+    if ((rc = scfq_reads::outputs_to_host(2, dst, own, bytes, in1.stream, g_serr))) return rc;
     SCFQ_SCRATCH_CHK(g_serr, hipStreamSynchronize(in1.stream));
   }
   for (DevBuf& o : own) o.drop();
@@ -830,14 +720,8 @@ int scfq_screen_files(const scfq_screen_index* index, const char* path1, const c
     SCFQ_SCRATCH_CHK(g_serr, hipMemcpyAsync(recs_host, recs_keep.p, stats->reads_in * sizeof(scfq_screen_rec), hipMemcpyDeviceToHost, in1.stream));
     SCFQ_SCRATCH_CHK(g_serr, hipStreamSynchronize(in1.stream));
   }
-  if (!own[0].p && !own[1].p) { in1.mark_clean(); return SCFQ_OK; }
-  // one output after the other, each in full: HBM -> two pinned buffers -> write()
-  scfq_fdwrite::Pinned pinned;
-  if ((rc = pinned.init(g_serr))) return finish(in1, rc);
   const uint64_t bytes[2] = {stats->out1_bytes, stats->out2_bytes};
-  for (int x = 0; x < 2; ++x)
-    if (own[x].p && (rc = pinned.device_to_fd(own[x].as<uint8_t>(), bytes[x], fd[x], in1.stream, g_serr))) return finish(in1, rc);
-  return SCFQ_OK;
+  return scfq_reads::outputs_to_fds(2, own, bytes, fd, in1, g_serr);
 }
 
 }  // extern "C"

@@ -3,6 +3,8 @@
 #pragma once
 #include "../../include/sc_fqcount.h"
 
+#include "scfq_copy_text.hpp"
+
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -119,15 +121,6 @@ inline bool pick_slots(uint64_t windows, int forced_bits, uint64_t* slots, char*
   return true;
 }
 
-inline int copy_out(const char* text, int m, char* buf, uint64_t cap) {
-  if (buf && cap) {
-    const uint64_t ncopy = ((uint64_t)m < cap - 1) ? (uint64_t)m : cap - 1;
-    std::memcpy(buf, text, ncopy);
-    buf[ncopy] = 0;
-  }
-  return m;
-}
-
 // the report row (include/sc_fqcount.h: scfq_format_screen_row_tsv)
 inline int format_row(const scfq_screen_stats* s, const std::vector<RefInfo>& infos, uint32_t k, uint32_t r, char* buf, uint64_t cap) {
   if (!s || r > infos.size() || s->n_refs != infos.size() || s->k != k) return SCFQ_EARG;
@@ -144,7 +137,7 @@ inline int format_row(const scfq_screen_stats* s, const std::vector<RefInfo>& in
                               (unsigned long long)(all ? s->matched_reads - s->multi_reads : s->ref_only_reads[r]),
                               (unsigned long long)(all ? s->multi_reads : s->ref_best_reads[r]),
                               (unsigned long long)(all ? s->hit_kmers : s->ref_kmer_hits[r]));
-  return copy_out(tmp, m, buf, cap);
+  return scfq_reads::copy_text(tmp, m, buf, cap);
 }
 
 }  // namespace scfq_screen_host

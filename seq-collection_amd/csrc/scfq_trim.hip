@@ -23,7 +23,6 @@
 //                             record that is its own input bytes is one wave_copy, any other one its four pieces, each a wave_copy.
 // T3 compares the two totals with the capacities before it stores anything: a result that does not fit leaves both outputs alone.
 // T2 and T3 get a record's lengths from the same function (read_of).  Everything is integer / byte work; there is no CPU fallback.
-// (text_span, echo_len and echo_record repeat scfq_merge.hip's: sharing them would change that file, whose kernels stay as they are.)
 #include "../../include/sc_fqcount.h"
 #include "../../include/sc_fqcount_debug.h"
 
@@ -31,10 +30,7 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
-#include "scfq_fdwrite.hpp"
-#include "scfq_overlap.hpp"
-#include "scfq_record_device.hpp"
-#include "scfq_scratch.hpp"
+#include "scfq_reads_host.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -45,12 +41,15 @@ namespace {
 thread_local char g_terr[scfq_scratch::kErrBytes] = "";
 thread_local double g_stage_ms[4] = {0, 0, 0, 0};
 
-using scfq_scratch::DevBuf;
+using scfq_reads::Dest;
+using scfq_reads::DevBuf;
+using scfq_reads::finish;
+using scfq_reads::Mode;
 
 constexpr uint32_t kTrWaves = 4;                         // reads a block of T1 works on at a time; groups of a block of T3
 constexpr uint32_t kTrMaxBlocks = 4096;                  // of T1
 constexpr uint32_t kTrWords = SCFQ_TRIM_MAX_LEN / 64;    // words of a plane
-constexpr uint32_t kTrGroup = 32;                        // reads or pairs of a group: one wave of T3, one entry of the scans
+constexpr uint32_t kTrGroup = kRecGroup;                 // reads or pairs of a group: one wave of T3, one entry of the scans
 static_assert(SCFQ_TRIM_MAX_LEN == 512 && SCFQ_TRIM_MAX_PROBES == 8 && SCFQ_ADAPTERS_MAX_LEN == 32, "a cut point is 10 bits, a window one 32-bit word");
 
 // T1's word per read: e after the overlap, adapter, poly-G and quality step, 10 bits each (the last one is the cut point), the probe
@@ -62,31 +61,12 @@ __host__ __device__ __forceinline__ uint32_t cut_probe(uint64_t c) { return (uin
 enum { kTooLong = 0, kShort, kDropped, kBasesIn, kBasesOut, kCutOverlap, kCutAdapter, kCutPolyG, kCutQuality, kBasesOverlap, kBasesAdapter, kBasesPolyG,
        kBasesQuality, kAdapterReads, kBasesDropped = kAdapterReads + SCFQ_TRIM_MAX_PROBES, kOverlapped, kCounters };
 
-struct TrInput {          // one input: the bytes and their line index
-  const uint8_t* base;
-  uint64_t n;
-  const uint64_t* line_off;
-  uint64_t lines;
-  bool has_cr;
-};
-
-struct TrOut {            // one output: where it goes (nullptr: nowhere) and what it holds
-  uint8_t* p;
-  uint64_t cap;
-};
-
 struct TrProbes {         // bit k of a plane: letter k of the probe (P1's code: bits 1 and 2 of the letter)
   uint32_t c0[SCFQ_TRIM_MAX_PROBES], c1[SCFQ_TRIM_MAX_PROBES], len[SCFQ_TRIM_MAX_PROBES];
   uint32_t n;
 };
 
 struct TrSteps { uint32_t min_adapter_overlap, adapter_pct, poly_g, window, window_quality, q0, min_length; };
-
-// the text of line j (a line the input does not have is empty)
-__device__ __forceinline__ void text_span(const TrInput& in, uint64_t j, uint64_t& s, uint64_t& e) {
-  s = e = 0;
-  if (j < in.lines) line_span(in.base, in.n, in.line_off, j, s, e, in.has_cr);
-}
 
 // code (bit 0, bit 1) and valid bit of a byte: bits 1 and 2 of 'A' 'C' 'T' 'G' are 0 1 2 3 (is_overlap's classify)
 __device__ __forceinline__ void classify(uint32_t b, bool& c0, bool& c1, bool& v) {
@@ -119,7 +99,7 @@ __device__ __forceinline__ uint32_t window_at(uint64_t plane, uint32_t w, uint32
 // of b.  recs: P1's table, or nullptr (no overlap step).  (Held to 64 VGPRs and 8 waves per SIMD with amdgpu_waves_per_eu the
 // kernel took the same time as with the 118 VGPRs and 4 waves the compiler chooses, within 6 % either way: it is bound by instruction
 // issue, not by waves in flight — profiles/trim/measure.json, t1_waves_per_eu_8.)
-__global__ __launch_bounds__(64 * kTrWaves) void tr_cut(TrInput a, TrInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t reads,
+__global__ __launch_bounds__(64 * kTrWaves) void tr_cut(RecInput a, RecInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t reads,
                                                        const scfq_overlap_rec* recs, TrProbes pr, TrSteps st, uint64_t* cuts) {
   const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   // (no barrier and no LDS: the waves of a block go their own ways)
@@ -128,7 +108,7 @@ __global__ __launch_bounds__(64 * kTrWaves) void tr_cut(TrInput a, TrInput b, ui
     if (r >= reads) continue;
     const uint64_t p = paired ? r >> 1 : r;
     const bool mate2 = paired && (r & 1);
-    const TrInput& in = mate2 ? b : a;
+    const RecInput& in = mate2 ? b : a;
     const uint64_t i = paired ? p * stride + (mate2 ? second : 0) : r;
     uint64_t ss, se, qs, qe;
     text_span(in, 4 * i + 1, ss, se);
@@ -245,37 +225,6 @@ __global__ __launch_bounds__(64 * kTrWaves) void tr_cut(TrInput a, TrInput b, ui
   }
 }
 
-// bytes record i echoes: its lines 4i .. min(4i+3, lines-1), each text + '\n' (dd_record_lengths' rule)
-__device__ __forceinline__ uint64_t echo_len(const TrInput& in, uint64_t i) {
-  if (4 * i >= in.lines) return 0;
-  if (!in.has_cr) {
-    const uint64_t j1 = (4 * i + 4 < in.lines) ? 4 * i + 4 : in.lines;
-    return in.line_off[j1] - in.line_off[4 * i];
-  }
-  uint64_t total = 0;
-  for (uint64_t j = 4 * i; j < 4 * i + 4 && j < in.lines; ++j) {
-    uint64_t s, e;
-    line_span(in.base, in.n, in.line_off, j, s, e);
-    total += e - s + 1;
-  }
-  return total;
-}
-
-// record i of `in` echoed to dst, len bytes (dd_gather's rule: one copy when the echo is the record's own bytes)
-__device__ __forceinline__ void echo_record(const TrInput& in, uint64_t i, uint8_t* dst, uint64_t len, uint32_t lane) {
-  const uint64_t j0 = 4 * i, j1 = (j0 + 4 < in.lines) ? j0 + 4 : in.lines;
-  const uint64_t r0 = in.line_off[j0], r1 = in.line_off[j1];
-  if (r1 - r0 == len && r1 <= in.n) { wave_copy(dst, in.base + r0, len, lane); return; }
-  uint64_t w = 0;
-  for (uint64_t j = j0; j < j1; ++j) {
-    uint64_t s, e;
-    line_span(in.base, in.n, in.line_off, j, s, e);
-    for (uint64_t k = lane; k < e - s; k += 64) dst[w + k] = in.base[s + k];
-    if (lane == 0) dst[w + (e - s)] = '\n';
-    w += e - s + 1;
-  }
-}
-
 // what a read adds to its output if it is kept and where its pieces lie.  T2 and T3 both get it from here, so the lengths the scans saw
 // are the lengths T3 writes
 enum : uint32_t { kPieces = 0, kCopy, kEcho };
@@ -286,7 +235,7 @@ struct TrRead {
   uint32_t kind;                       // kPieces: the four pieces; kCopy: len bytes from hs on; kEcho: a too-long read
 };
 
-__device__ __forceinline__ TrRead read_of(const TrInput& in, uint64_t i, uint64_t cut, uint64_t& seq_len) {
+__device__ __forceinline__ TrRead read_of(const RecInput& in, uint64_t i, uint64_t cut, uint64_t& seq_len) {
   TrRead r = {};
   uint64_t e;
   text_span(in, 4 * i + 1, r.ss, e);
@@ -313,7 +262,7 @@ __device__ __forceinline__ TrRead read_of(const TrInput& in, uint64_t i, uint64_
 }
 
 // a kept read's record, by the whole wave
-__device__ __forceinline__ void write_read(const TrInput& in, uint64_t i, const TrRead& r, uint8_t* dst, uint32_t lane) {
+__device__ __forceinline__ void write_read(const RecInput& in, uint64_t i, const TrRead& r, uint8_t* dst, uint32_t lane) {
   if (r.kind == kEcho) { echo_record(in, i, dst, r.len, lane); return; }
   if (r.kind == kCopy) { wave_copy(dst, in.base + r.hs, r.len, lane); return; }
   uint8_t* const s = dst + r.hl + 1;
@@ -339,7 +288,7 @@ struct TrUnit {
   bool dropped;
 };
 
-__device__ __forceinline__ TrUnit look_up(const TrInput& a, const TrInput& b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t u,
+__device__ __forceinline__ TrUnit look_up(const RecInput& a, const RecInput& b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t u,
                                           const uint64_t* cuts, uint32_t min_length) {
   TrUnit t = {};
   t.mates = paired ? 2u : 1u;
@@ -360,17 +309,10 @@ __device__ __forceinline__ TrUnit look_up(const TrInput& a, const TrInput& b, ui
   return t;
 }
 
-__device__ __forceinline__ uint64_t half_sum(uint64_t v) {      // over the 32 lanes of a half wave
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor((unsigned long long)v, o, 64);
-  return v;
-}
-
 // T2.  group_len: two arrays of n_groups + 1 entries, one after the other (the last entry of each stays 0: the scan's total)
-__global__ __launch_bounds__(256) void tr_lengths(TrInput a, TrInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t units, const uint64_t* cuts,
+__global__ __launch_bounds__(256) void tr_lengths(RecInput a, RecInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t units, const uint64_t* cuts,
                                                  const scfq_overlap_rec* recs, uint32_t min_length, uint64_t n_groups, uint64_t* group_len,
                                                  unsigned long long* counters) {
-  static_assert(kTrGroup == 32, "the sums below run over the two halves of a wave");
   __shared__ uint64_t sum_sh[kCounters][4];
   const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   uint64_t len[2] = {0, 0}, c[kCounters];
@@ -402,10 +344,7 @@ __global__ __launch_bounds__(256) void tr_lengths(TrInput a, TrInput b, uint64_t
     }
   }
 #pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const uint64_t s = half_sum(len[k]);
-    if ((threadIdx.x & 31) == 0 && u < units) group_len[(uint64_t)k * (n_groups + 1) + u / kTrGroup] = s;
-  }
+  for (int k = 0; k < 2; ++k) store_group_len(len[k], k, u, units, n_groups, group_len);
   // the statistics: ONE atomic per block and counter (dd_count_marks: an atomic per wave on one address costs more than the kernel)
 #pragma unroll
   for (int k = 0; k < kCounters; ++k) {
@@ -419,9 +358,7 @@ __global__ __launch_bounds__(256) void tr_lengths(TrInput a, TrInput b, uint64_t
   }
 }
 
-__device__ __forceinline__ uint64_t bcast(uint64_t v, uint32_t from) { return (uint64_t)__shfl((unsigned long long)v, (int)from, 64); }
-__device__ __forceinline__ uint32_t bcast(uint32_t v, uint32_t from) { return (uint32_t)__shfl((int)v, (int)from, 64); }
-
+using ::bcast;      // (the overload below hides the shared ones otherwise)
 __device__ __forceinline__ TrRead bcast(const TrRead& m, uint32_t from) {
   TrRead r;
   r.len = bcast(m.len, from);
@@ -432,31 +369,23 @@ __device__ __forceinline__ TrRead bcast(const TrRead& m, uint32_t from) {
 }
 
 // T3.  group_off: the two scanned arrays of T2's layout
-__global__ __launch_bounds__(64 * kTrWaves) void tr_write(TrInput a, TrInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t units,
-                                                         const uint64_t* cuts, uint32_t min_length, uint64_t n_groups, const uint64_t* group_off, TrOut o1,
-                                                         TrOut o2) {
+__global__ __launch_bounds__(64 * kTrWaves) void tr_write(RecInput a, RecInput b, uint64_t stride, uint64_t second, uint32_t paired, uint64_t units,
+                                                         const uint64_t* cuts, uint32_t min_length, uint64_t n_groups, const uint64_t* group_off, RecOut o1,
+                                                         RecOut o2) {
   const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const uint64_t* off_1 = group_off;
-  const uint64_t* off_2 = group_off + (n_groups + 1);
-  // (each scan's last entry is its output's size: when one is more than its output holds, nothing is written to either)
-  const bool fits = (!o1.p || off_1[n_groups] <= o1.cap) && (!o2.p || off_2[n_groups] <= o2.cap);
-  if (!fits) return;
+  // (when one result is more than its output holds, nothing is written to either)
+  if (!(output_fits(o1, 0, n_groups, group_off) && output_fits(o2, 1, n_groups, group_off))) return;
   const uint64_t g = (uint64_t)blockIdx.x * kTrWaves + wave;
   if (g >= n_groups) return;
   const uint64_t u0 = g * kTrGroup;
   const uint32_t count = (uint32_t)std::min<uint64_t>(kTrGroup, units - u0);
   TrUnit mine = {};
   if (lane < count) mine = look_up(a, b, stride, second, paired, u0 + lane, cuts, min_length);
-  // where the unit of this lane goes: the group's offsets and the lengths of the units in front of it
-  uint64_t at_1 = mine.len1, at_2 = mine.len2;
-#pragma unroll
-  for (int o = 1; o < (int)kTrGroup; o <<= 1) {
-    const uint64_t v1 = __shfl_up((unsigned long long)at_1, o, 64), v2 = __shfl_up((unsigned long long)at_2, o, 64);
-    if (lane >= (uint32_t)o) { at_1 += v1; at_2 += v2; }
-  }
-  at_1 += off_1[g] - mine.len1; at_2 += off_2[g] - mine.len2;
+  const uint64_t len[2] = {mine.len1, mine.len2};
+  uint64_t at[2];
+  place_units(len, g, n_groups, group_off, lane, at);
   for (uint32_t q = 0; q < count; ++q) {
-    const uint64_t l1 = bcast(mine.len1, q), l2 = bcast(mine.len2, q), first = bcast(mine.first, q), w1 = bcast(at_1, q), w2 = bcast(at_2, q);
+    const uint64_t l1 = bcast(mine.len1, q), l2 = bcast(mine.len2, q), first = bcast(mine.first, q), w1 = bcast(at[0], q), w2 = bcast(at[1], q);
     if (l1 + l2 == 0) continue;                            // (a dropped unit; a kept record has its four '\n' at the least, or is an echo of nothing)
     const uint64_t u = u0 + q;
     const uint64_t i1 = paired ? u * stride : u, i2 = u * stride + second;
@@ -530,13 +459,6 @@ bool args_ok(const scfq_trim_opts* opts, const scfq_trim_stats* st, Params& p) {
   return true;
 }
 
-enum class Mode { single, two, interleaved };
-
-// one output of a call: `want` it, and then the caller's device memory (p, cap) or, with own_outputs, pool memory that trim_device
-// takes by the size the scan reports (own[k]; cap is then the caller's host capacity, checked here all the same)
-struct Dest { uint8_t* p; uint64_t cap; bool want; };
-const char* const kDestName[2] = {"out1", "out2"};
-
 int trim_device(const uint8_t* d1, uint64_t n1, const uint8_t* d2, uint64_t n2, Mode mode, const Params& prm, bool own_outputs, Dest dst[2], DevBuf own[2],
                 bool check_caps, scfq_trim_stats* st, hipStream_t stream) {
   for (double& m : g_stage_ms) m = 0;
@@ -552,43 +474,29 @@ int trim_device(const uint8_t* d1, uint64_t n1, const uint8_t* d2, uint64_t n2, 
   scfq_overlap::Indexed ix;
   int rc = SCFQ_OK;
   double index_ms = 0;
-  if (paired) {
-    rc = scfq_overlap::index_inputs(d1, n1, d2, n2, interleaved, stream, g_terr, ix, &index_ms);
-  } else {
-    // single-end input: K5 directly
-    if ((rc = scfq_scratch::build_line_index(d1, n1, stream, g_terr, ix.off1, &ix.lines1, &ix.cr1))) return rc;
-    ix.reads1 = (ix.lines1 + 3) / 4;
-    if (ix.reads1 >= (1ull << 31)) { std::snprintf(g_terr, sizeof g_terr, "more than 2^31 records in one input"); rc = SCFQ_EARG; }
-  }
-  st->lines1 = ix.lines1; st->lines2 = ix.lines2;
-  st->reads1 = ix.reads1; st->reads2 = ix.reads2;
-  if (rc) return rc;
-  st->pairs = ix.pairs;
-  st->unpaired = ix.unpaired;
-  const uint64_t units = paired ? ix.pairs : ix.reads1, reads = paired ? 2 * ix.pairs : ix.reads1;
+  uint64_t units = 0, reads = 0;
+  if ((rc = scfq_reads::index_units(d1, n1, d2, n2, mode, stream, g_terr, ix, &index_ms, st, &units, &reads))) return rc;
   st->reads_in = reads;
   if (units == 0) return SCFQ_OK;           // (two empty outputs: they fit into anything)
-  const uint64_t n_groups = (units + kTrGroup - 1) / kTrGroup, row = n_groups + 1;
+  const uint64_t n_groups = (units + kTrGroup - 1) / kTrGroup;
   DevBuf recs, acc, cuts, group_len, group_off, counters, tmp;
+  scfq_reads::GroupScan gs(2, n_groups, group_len, group_off, stream, g_terr);
   if ((overlap && ((rc = recs.alloc(units * sizeof(scfq_overlap_rec), stream, g_terr)) || (rc = acc.alloc(scfq_overlap::kAccWords * 8, stream, g_terr)))) ||
-      (rc = cuts.alloc(reads * 8, stream, g_terr)) || (rc = group_len.alloc(2 * row * 8, stream, g_terr)) ||
-      (rc = group_off.alloc(2 * row * 8, stream, g_terr)) || (rc = counters.alloc(kCounters * 8, stream, g_terr)))
+      (rc = cuts.alloc(reads * 8, stream, g_terr)) || (rc = gs.alloc()) || (rc = counters.alloc(kCounters * 8, stream, g_terr)))
     return rc;
   size_t scan_bytes = 0;
-  SCFQ_SCRATCH_CHK(g_terr, rocprim::exclusive_scan(nullptr, scan_bytes, group_len.as<uint64_t>(), group_off.as<uint64_t>(), (uint64_t)0, (size_t)row,
-                                                   rocprim::plus<uint64_t>(), stream));
-  if ((rc = tmp.alloc(scan_bytes, stream, g_terr))) return rc;
+  if ((rc = gs.scratch_bytes(&scan_bytes)) || (rc = tmp.alloc(scan_bytes, stream, g_terr))) return rc;
   static const bool timing = scfq_scratch::env_switch("SCFQ_TRIM_TIMING");
   scfq_scratch::StageClock clk(stream, timing);
   if (overlap) SCFQ_SCRATCH_CHK(g_terr, hipMemsetAsync(acc.p, 0, scfq_overlap::kAccWords * 8, stream));
   SCFQ_SCRATCH_CHK(g_terr, hipMemsetAsync(counters.p, 0, kCounters * 8, stream));
-  SCFQ_SCRATCH_CHK(g_terr, hipMemsetAsync(group_len.p, 0, 2 * row * 8, stream));       // (each scan's last input: its last output is the total)
+  if ((rc = gs.zero())) return rc;
   clk.mark(0);
   if (overlap && (rc = scfq_overlap::queue_overlap(d1, n1, d2, n2, interleaved, ix, prm.ov, recs.as<scfq_overlap_rec>(), acc.as<unsigned long long>(), stream, g_terr)))
     return rc;
   clk.mark(1);
-  const TrInput a = {d1, n1, ix.off1.as<uint64_t>(), ix.lines1, ix.cr1};
-  const TrInput b = mode == Mode::two ? TrInput{d2, n2, ix.off2.as<uint64_t>(), ix.lines2, ix.cr2} : a;
+  const RecInput a = {d1, n1, ix.off1.as<uint64_t>(), ix.lines1, ix.cr1};
+  const RecInput b = mode == Mode::two ? RecInput{d2, n2, ix.off2.as<uint64_t>(), ix.lines2, ix.cr2} : a;
   const uint64_t stride = interleaved ? 2 : 1, second = interleaved ? 1 : 0;
   const scfq_overlap_rec* table = overlap ? recs.as<scfq_overlap_rec>() : nullptr;
   hipLaunchKernelGGL(tr_cut, dim3((unsigned)std::min<uint64_t>((reads + kTrWaves - 1) / kTrWaves, kTrMaxBlocks)), dim3(64 * kTrWaves), 0, stream, a, b, stride,
@@ -596,40 +504,28 @@ int trim_device(const uint8_t* d1, uint64_t n1, const uint8_t* d2, uint64_t n2, 
   SCFQ_SCRATCH_CHK(g_terr, hipGetLastError());
   clk.mark(2);
   hipLaunchKernelGGL(tr_lengths, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, stream, a, b, stride, second, paired ? 1u : 0u, units, cuts.as<uint64_t>(),
-                     table, prm.steps.min_length, n_groups, group_len.as<uint64_t>(), counters.as<unsigned long long>());
+                     table, prm.steps.min_length, n_groups, gs.len(), counters.as<unsigned long long>());
   SCFQ_SCRATCH_CHK(g_terr, hipGetLastError());
-  for (uint64_t k = 0; k < 2; ++k)
-    SCFQ_SCRATCH_CHK(g_terr, rocprim::exclusive_scan(tmp.p, scan_bytes, group_len.as<uint64_t>() + k * row, group_off.as<uint64_t>() + k * row, (uint64_t)0, (size_t)row,
-                                                     rocprim::plus<uint64_t>(), stream));
+  if ((rc = gs.scan(tmp.p, scan_bytes))) return rc;
   clk.mark(3);
   // the sizes and the statistics come back first: pool memory for the outputs is taken to fit, and a caller's buffer that is too small
   // is known here
-  uint64_t total[2] = {0, 0}, h[kCounters];
-  for (uint64_t k = 0; k < 2; ++k) SCFQ_SCRATCH_CHK(g_terr, hipMemcpyAsync(&total[k], group_off.as<uint64_t>() + k * row + n_groups, 8, hipMemcpyDeviceToHost, stream));
+  uint64_t h[kCounters];
+  if ((rc = gs.read_totals())) return rc;
   SCFQ_SCRATCH_CHK(g_terr, hipMemcpyAsync(h, counters.p, kCounters * 8, hipMemcpyDeviceToHost, stream));
   SCFQ_SCRATCH_CHK(g_terr, hipStreamSynchronize(stream));
-  st->out1_bytes = total[0]; st->out2_bytes = total[1];
+  st->out1_bytes = gs.total[0]; st->out2_bytes = gs.total[1];
   st->too_long = h[kTooLong]; st->short_reads = h[kShort]; st->dropped_reads = h[kDropped]; st->reads_out = reads - h[kDropped];
   st->bases_in = h[kBasesIn]; st->bases_out = h[kBasesOut]; st->bases_dropped = h[kBasesDropped];
   st->cut_overlap = h[kCutOverlap]; st->cut_adapter = h[kCutAdapter]; st->cut_polyg = h[kCutPolyG]; st->cut_quality = h[kCutQuality];
   st->bases_overlap = h[kBasesOverlap]; st->bases_adapter = h[kBasesAdapter]; st->bases_polyg = h[kBasesPolyG]; st->bases_quality = h[kBasesQuality];
   for (uint32_t j = 0; j < SCFQ_TRIM_MAX_PROBES; ++j) st->adapter_reads[j] = h[kAdapterReads + j];
   st->overlapped_pairs = h[kOverlapped];
-  int small = -1;
-  for (int k = 1; k >= 0; --k)
-    if (check_caps && dst[k].want && total[k] > dst[k].cap) small = k;
-  TrOut out[2];
-  for (int k = 0; k < 2; ++k) {
-    out[k] = TrOut{nullptr, 0};
-    if (!dst[k].want) continue;
-    if (!own_outputs) { out[k] = TrOut{dst[k].p, dst[k].cap}; continue; }      // (too small or not: T3 looks at the totals itself)
-    if (small >= 0 || total[k] == 0) continue;
-    if ((rc = own[k].alloc(total[k], stream, g_terr))) return rc;
-    out[k] = TrOut{own[k].as<uint8_t>(), total[k]};
-  }
-  if (out[0].p || out[1].p) {
+  const scfq_reads::Placement put = scfq_reads::place_outputs(gs, scfq_reads::kOutNames, dst, own_outputs, check_caps, false, own, stream, g_terr);
+  if (put.rc) return put.rc;
+  if (put.out[0].p || put.out[1].p) {
     hipLaunchKernelGGL(tr_write, dim3((unsigned)((n_groups + kTrWaves - 1) / kTrWaves)), dim3(64 * kTrWaves), 0, stream, a, b, stride, second, paired ? 1u : 0u,
-                       units, cuts.as<uint64_t>(), prm.steps.min_length, n_groups, group_off.as<uint64_t>(), out[0], out[1]);
+                       units, cuts.as<uint64_t>(), prm.steps.min_length, n_groups, gs.off(), put.out[0], put.out[1]);
     SCFQ_SCRATCH_CHK(g_terr, hipGetLastError());
   }
   clk.mark(4);
@@ -638,19 +534,7 @@ int trim_device(const uint8_t* d1, uint64_t n1, const uint8_t* d2, uint64_t n2, 
   g_stage_ms[1] = clk.between(1, 2);
   g_stage_ms[2] = clk.between(2, 3);
   g_stage_ms[3] = clk.between(3, 4);
-  if (small >= 0) {
-    std::snprintf(g_terr, sizeof g_terr, "the %s output holds %llu bytes, the result has %llu", kDestName[small], (unsigned long long)dst[small].cap,
-                  (unsigned long long)total[small]);
-    return SCFQ_EARG;
-  }
-  return SCFQ_OK;
-}
-
-// after a failure kernels that read the second input may still be queued on the first one's stream: they are waited for before the
-// second input's memory goes back (as fq-merge's)
-int finish(scfq_scratch::ResidentInput& in1, int rc) {
-  if (rc != SCFQ_OK) (void)hipStreamSynchronize(in1.stream);
-  return rc;
+  return put.verdict;      // (SCFQ_EARG for an output that is too small: place_outputs has left the text)
 }
 
 }  // namespace
@@ -682,8 +566,8 @@ int scfq_trim_buffers(const void* r1, uint64_t n1, const void* r2, uint64_t n2, 
   rc = trim_device(in1.d_in, in1.n, in2.d_in, in2.n, mode, prm, /*own_outputs=*/!direct, dst, own, /*check_caps=*/true, stats, in1.stream);
   if (rc) return finish(in1, rc);
   if (!direct) {
-    for (int k = 0; k < 2; ++k)
-      if (own[k].p) SCFQ_SCRATCH_CHK(g_terr, hipMemcpyAsync(dst[k].p, own[k].p, k == 0 ? stats->out1_bytes : stats->out2_bytes, hipMemcpyDeviceToHost, in1.stream));
+    const uint64_t bytes[2] = {stats->out1_bytes, stats->out2_bytes};
+    if ((rc = scfq_reads::outputs_to_host(2, dst, own, bytes, in1.stream, g_terr))) return rc;
     SCFQ_SCRATCH_CHK(g_terr, hipStreamSynchronize(in1.stream));
   }
   for (DevBuf& o : own) o.drop();
@@ -709,14 +593,8 @@ int scfq_trim_files(const char* path1, const char* path2, const scfq_opts* opts,
   DevBuf own[2];
   rc = trim_device(in1.d_in, in1.n, in2.d_in, in2.n, mode, prm, /*own_outputs=*/true, dst, own, /*check_caps=*/false, stats, in1.stream);
   if (rc) return finish(in1, rc);
-  if (!own[0].p && !own[1].p) { in1.mark_clean(); return SCFQ_OK; }
-  // one output after the other, each in full: HBM -> two pinned buffers -> write()
-  scfq_fdwrite::Pinned pinned;
-  if ((rc = pinned.init(g_terr))) return finish(in1, rc);
   const uint64_t bytes[2] = {stats->out1_bytes, stats->out2_bytes};
-  for (int k = 0; k < 2; ++k)
-    if (own[k].p && (rc = pinned.device_to_fd(own[k].as<uint8_t>(), bytes[k], fd[k], in1.stream, g_terr))) return finish(in1, rc);
-  return SCFQ_OK;
+  return scfq_reads::outputs_to_fds(2, own, bytes, fd, in1, g_terr);
 }
 
 }  // extern "C"
