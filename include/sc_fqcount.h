@@ -1375,6 +1375,76 @@ int scfq_format_rmdup_stats_tsv(const scfq_rmdup_stats* s, int header, char* buf
 int scfq_format_rmdup_rec_tsv(uint64_t unit, const scfq_rmdup_rec* rec, char* buf, uint64_t cap);
 const char* scfq_rmdup_error_detail(void);       /* static, thread-local */
 
+/* ---- `sc fq-repair` (addition; not in the reference): R1 and R2 re-paired by READ NAME ---------------------------------
+ * Every paired command above pairs record i of R1 with record i of R2 and looks at no name. This one joins the records of
+ * two FASTQs by name: the mates that find each other leave in step, the others as singles.
+ * Inputs, lines, records, texts and the echo of a record are fq-trim's and fq-screen's, word for word: a record is four lines,
+ * reads = (lines + 3) / 4, a text has no "\r\n" or '\n' end, a record is echoed as each line it has, as text plus '\n'.
+ * Exactly two inputs; reads1 < 2^31 and reads2 < 2^31 (so reads1 + reads2 < 2^32 - 1); beyond that SCFQ_EARG with text.
+ * Name of a record, from the text H of its header line, in this order: (1) H's first byte is dropped, whatever it is (an
+ *  empty H gives the empty name); (2) what is left is cut at its first space (0x20) or tab (0x09), exclusive; (3) if what is
+ *  left has at least two bytes and ends in "/1" or "/2", those two bytes are dropped — once, and in either input. The
+ *  comparison is byte-exact, there is no length limit, and the empty name is a name like any other.
+ * Matching. The r-th record in input order that carries a name in R1 is the mate of the r-th record that carries that name
+ *  in R2; records of a name beyond the other input's count are singles. Without repeated names this is the plain join; with
+ *  them it is deterministic, and an input that is in step maps onto itself.
+ * Outputs. out1: the matched R1 records in R1's order, echoed. out2: their mates in that same order (a gather from R2).
+ *  singles1 / singles2: the unmatched records of each input in that input's order. Any subset may be left out.
+ * Per-record table: reads1 + reads2 words of uint32_t. Entry i < reads1 is the R2 index of R1 record i's mate; entry
+ *  reads1 + j is the R1 index of R2 record j's mate; SCFQ_REPAIR_SINGLE for a single.
+ * No field other than collisions, rounds and path, and no output byte, depends on the hash, on hash_bits or on the fast path
+ * (reads1 == reads2: name i of R1 is compared with name i of R2 first, and when none differs the table is the identity and
+ * no join runs; SCFQ_REPAIR_FAST=0 in the environment, read per call, turns that off). All values are integers and exact.
+ * Device pipeline: DESIGN.md §fq-repair. */
+#define SCFQ_REPAIR_SINGLE 0xFFFFFFFFu
+typedef struct scfq_repair_opts {
+  uint64_t struct_size;   /* sizeof(scfq_repair_opts) */
+  uint32_t flags;         /* every bit is reserved: an unknown bit is SCFQ_EARG */
+  uint32_t hash_bits;     /* 0: the library's default (40); 1 .. 64: the bits of the name hash that are sorted */
+  uint32_t reserved[4];   /* 0 */
+} scfq_repair_opts;
+typedef struct scfq_repair_stats {  /* 24 x 8 bytes */
+  uint64_t struct_size;   /* caller sets to sizeof(scfq_repair_stats) before the call */
+  uint64_t abi_version;   /* library writes SCFQ_ABI_VERSION */
+  uint64_t reads1, reads2;
+  uint64_t lines1, lines2;
+  uint64_t input_bytes1, input_bytes2;
+  uint64_t pairs;                      /* matched pairs; not min(reads1, reads2) */
+  uint64_t singles1, singles2;         /* unmatched records of each input */
+  uint64_t moved;                      /* pairs (i, j) with i != j */
+  uint64_t in_step;                    /* 1 iff reads1 == reads2, singles1 == singles2 == 0 and moved == 0 */
+  uint64_t repeated1, repeated2;       /* records whose name occurred earlier in their own input */
+  uint64_t collisions, rounds;         /* as fq-rmdup's: they depend on the hash only */
+  uint64_t path;                       /* 0: the positional check answered; 1: the full join ran */
+  uint64_t out1_bytes, out2_bytes, singles1_bytes, singles2_bytes;   /* sizes of the outputs, written or not */
+  uint64_t flags, hash_bits;           /* the parameters as used (hash_bits: 40 for 0) */
+} scfq_repair_stats;
+
+/* r1 / r2: host (is_device = 0) or device memory, both needed (a NULL pointer goes with a size of 0: an empty input). The four
+ * outputs (NULL: not wanted), the sizing call (no output: the four *_bytes say what to bring), a too-small output (SCFQ_EARG
+ * naming it, stats complete, NO byte written to ANY output: both writers compare the scanned totals with the capacities
+ * before they store) and the device-pointer rules are those of scfq_trim_buffers. table: NULL, or memory of the outputs' kind
+ * for table_cap words; fewer than reads1 + reads2 is SCFQ_EARG with text: stats is complete and nothing is written to the
+ * table or to an output. SCFQ_EARG with text in scfq_repair_error_detail(), before any HIP call: flag bits, hash_bits above
+ * 64, reserved not 0; without text: a NULL stats or a wrong struct_size (stats' or opts'), a NULL pointer with a size or
+ * capacity. opts = NULL: the defaults. There is no CPU fallback (SCFQ_EHIP without a device). */
+int scfq_repair_buffers(const void* r1, uint64_t n1, const void* r2, uint64_t n2, int is_device, const scfq_repair_opts* opts,
+                        uint32_t* table, uint64_t table_cap, void* out1, uint64_t cap1, void* out2, uint64_t cap2, void* singles1,
+                        uint64_t cap_s1, void* singles2, uint64_t cap_s2, int out_is_device, scfq_repair_stats* stats);
+/* As scfq_merge_files: staged inputs (".gz" / BGZF by suffix), descriptors below 0 are not produced, out1, out2, singles1,
+ * singles2 in that order, SCFQ_EPIPE / SCFQ_EIO. per_read_fd >= 0: the table as rows of scfq_format_repair_rec_tsv, each with
+ * a '\n', R1's records and then R2's, written before the outputs. Both paths are needed (SCFQ_EARG). */
+int scfq_repair_files(const char* path1, const char* path2, const scfq_repair_opts* opts, const scfq_opts* ropts, int out1_fd,
+                      int out2_fd, int singles1_fd, int singles2_fd, int per_read_fd, scfq_repair_stats* stats);
+/* The one-row report without trailing newline; header != 0: the names of its columns instead. The columns: reads1 reads2 pairs
+ * singles1 singles2 moved in_step repeated1 repeated2 out1_bytes out2_bytes singles1_bytes singles2_bytes. Returns the number
+ * of bytes needed (excluding NUL); writes at most cap bytes incl. NUL. */
+int scfq_format_repair_stats_tsv(const scfq_repair_stats* s, int header, char* buf, uint64_t cap);
+/* "<input>\t<record>\t<mate>" without trailing newline: input 1 or 2, the record's index in it, its mate's index in the other
+ * input or "-" for a single; input = 0: the names of the columns. The same return rule. */
+int scfq_format_repair_rec_tsv(uint32_t input, uint64_t record, uint32_t mate, char* buf, uint64_t cap);
+const char* scfq_repair_error_detail(void);      /* static, thread-local */
+
 /* ---- `sc fa-gc` (FASTA group): src/fa_gc.nim, docs/fa-gc.md, sc.nim:84-96 --------------------------------------------
  * GC content of the windows [pos - w, pos + w] around 1-based positions of a FASTA. The contract:
  *   Lines.   A header line is a line whose first byte is '>' (a line that starts at byte 0 of the input included); every

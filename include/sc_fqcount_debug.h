@@ -133,6 +133,12 @@ int scfq_debug_cplx_stages(double* ms, uint32_t cap);
  * ms[4] the class sizes, ms[5] U4 with its scans, ms[6] U5, the write kernel — the last six HIP-event times, taken only while
  * SCFQ_RMDUP_TIMING=1 is in the environment (zeros otherwise). Writes min(cap, 7) values, returns 7. */
 int scfq_debug_rmdup_stages(double* ms, uint32_t cap);
+/* Stage times of the calling thread's last scfq_repair_buffers / scfq_repair_files, in milliseconds: ms[0] the two line indexes
+ * (host clock), ms[1] P1, the name spans, ms[2] the positional check with its readback, ms[3] P2, the name hash, ms[4] the radix
+ * sort, ms[5] the rounds, ms[6] the mates (second sort, scans, kernel), ms[7] the pair list and the lengths with their scans,
+ * ms[8] W1 and W2, the writers — all but the first HIP-event times, taken only while SCFQ_REPAIR_TIMING=1 is in the environment
+ * (zeros otherwise). Writes min(cap, 9) values, returns 9. */
+int scfq_debug_repair_stages(double* ms, uint32_t cap);
 /* Stage times of the calling thread's last scfq_fa_index_buffer / scfq_fa_index_file, in milliseconds: ms[0] F1, the tile scan,
  * ms[1] F2, the scan over the tile records, ms[2] F3, the contig table's kernel, ms[3] unused (0) — HIP-event times, taken only
  * while SCFQ_FA_TIMING=1 is in the environment (zeros otherwise). Writes min(cap, 4) values, returns 4. */

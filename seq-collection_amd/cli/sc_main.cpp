@@ -1310,6 +1310,87 @@ static int cmd_fq_rmdup(const std::vector<std::string>& params) {
   return 0;
 }
 
+// command "fq-repair" (addition, not in the reference): R1.fq R2.fq with --out1=PATH --out2=PATH (or neither: the report only),
+// --singles1=PATH, --singles2=PATH, --check, --per-read=PATH, -t/--header, -b/--basename, -a/--absolute.  The report goes to stdout.
+static int cmd_fq_repair(const std::vector<std::string>& params) {
+  static const char* const help =
+      "Re-pair R1 and R2 by read name: the mates that find each other leave in step, the others as singles\n\n"
+      "Usage:\n  fq-repair [options] --out1=PATH --out2=PATH [--singles1=PATH] [--singles2=PATH] R1.fq R2.fq\n"
+      "  fq-repair [options] --check R1.fq R2.fq\n\n"
+      "Arguments:\n  R1.fq R2.fq      Two FASTQs. A record's name is its header without the first byte, up to the first blank or tab,\n"
+      "                   without one trailing /1 or /2; without --out1 and --out2 only the report is produced\n\nOptions:\n"
+      "      --out1=PATH            The R1 records that have a mate, in R1's order\n"
+      "      --out2=PATH            Their mates from R2, in that same order\n"
+      "      --singles1=PATH        The R1 records without a mate\n"
+      "      --singles2=PATH        The R2 records without a mate\n"
+      "      --check                No reads are written: the one-row report, and exit status 0 when the inputs are in step, else 1\n"
+      "      --per-read=PATH        One row per record to PATH: input record mate (\"-\" for a single)\n"
+      "  -t, --header               Output the header\n  -b, --basename             Add a column with the basename of the first FASTQ\n"
+      "  -a, --absolute             Add a column with the absolute path of the first FASTQ\n"
+      "  -h, --help                 Show this help\n";
+  Columns cols;
+  scfq_repair_opts co = fresh<scfq_repair_opts>();
+  bool check = false;
+  std::vector<std::string> files;
+  std::string path[4], per_read;          // out1, out2, singles1, singles2
+  const std::vector<Opt> table = cols.options({
+      opt_text("out1", &path[0]),
+      opt_text("out2", &path[1]),
+      opt_text("singles1", &path[2]),
+      opt_text("singles2", &path[3]),
+      opt_flag("check", 0, &check),
+      opt_text("per-read", &per_read),
+  });
+  if (!parse_options(params, help, table, &files)) return 0;
+  if (files.empty()) quit_no_fastq();
+  if (files.size() != 2) usage_error(help, "fq-repair takes R1.fq and R2.fq");
+  if (path[0].empty() != path[1].empty()) usage_error(help, "--out1=PATH and --out2=PATH go together");
+  if (check && !(path[0].empty() && path[2].empty() && path[3].empty())) usage_error(help, "--check writes no reads: it goes without --out1, --out2, --singles1 and --singles2");
+  for (const std::string& f : files) require_suffix_room(f);
+  // the inputs are looked at before an output file is made
+  for (const std::string& f : files)
+    if (access(f.c_str(), R_OK) != 0) quit_unable_to_open(f);
+  int fd[4] = {-1, -1, -1, -1}, fdr = -1;
+  // a call that fails leaves no output file behind: what this process created goes again (fq-trim's rule)
+  auto discard = [&]() {
+    auto drop = [](int& d, const std::string& p) {
+      if (d < 0) return;
+      struct stat st;
+      const bool regular = fstat(d, &st) == 0 && S_ISREG(st.st_mode);
+      close(d);
+      if (regular) unlink(p.c_str());
+      d = -1;
+    };
+    for (int k = 0; k < 4; ++k) drop(fd[k], path[k]);
+    drop(fdr, per_read);
+  };
+  auto create = [&](const std::string& p) -> int {
+    const int d = open(p.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
+    if (d < 0) { discard(); quit_error("Unable to create file: " + p, 1); }
+    return d;
+  };
+  for (int k = 0; k < 4; ++k)
+    if (!path[k].empty()) fd[k] = create(path[k]);
+  if (!per_read.empty()) fdr = create(per_read);
+  scfq_repair_stats st = fresh<scfq_repair_stats>();
+  std::fflush(stdout);
+  const int rc = scfq_repair_files(files[0].c_str(), files[1].c_str(), &co, nullptr, fd[0], fd[1], fd[2], fd[3], fdr, &st);
+  if (rc != SCFQ_OK && rc != SCFQ_EPIPE) discard();
+  else { for (int d : fd) if (d >= 0) close(d); if (fdr >= 0) close(fdr); }
+  if (rc == SCFQ_EOPEN) quit_unable_to_open(first_unopenable(files[0], &files[1]));
+  if (rc == SCFQ_EPIPE) return 0;              // a reader that went away: quiet, as `sc fq-dedup | head`
+  if (rc != SCFQ_OK) quit_error(library_error(rc, scfq_repair_error_detail()), 1);
+  char row[1024];
+  if (cols.header) {
+    scfq_format_repair_stats_tsv(nullptr, 1, row, sizeof row);
+    std::printf("%s\n", output_header(row, cols.basename, cols.absolute).c_str());
+  }
+  scfq_format_repair_stats_tsv(&st, 0, row, sizeof row);
+  std::printf("%s\n", cols.row(row, files[0]).c_str());
+  std::fflush(stdout);
+  return check && !st.in_step ? 1 : 0;
+}
+
 // command "fq-kcount" (addition, not in the reference): -t/--header, -b/--basename, -a/--absolute as fq-count, --k=N, --canonical,
 // --table-bits=N, --high=N, --totals, --dump [--min-count=C] [--max-count=C], --top=N, IN.fq [IN2.fq]
 static const char* kKcountHistHeader = "count\tkmers";
@@ -1863,7 +1944,7 @@ int main(int argc, char** argv) {
       {"fq-adapters", cmd_fq_adapters}, {"fq-insert-size", cmd_fq_insert_size}, {"fq-merge", cmd_fq_merge},
       {"fq-trim", cmd_fq_trim},         {"fq-screen", cmd_fq_screen},     {"fq-demux", cmd_fq_demux},
       {"fq-kcount", cmd_fq_kcount},     {"fq-normalize", cmd_fq_normalize}, {"fq-complexity", cmd_fq_complexity},
-      {"fq-rmdup", cmd_fq_rmdup},
+      {"fq-rmdup", cmd_fq_rmdup},       {"fq-repair", cmd_fq_repair},
       {"fa-gc", cmd_fa_gc}};
   for (const auto& c : commands)
     if (params[0] == c.name) return c.run(params);

@@ -1,5 +1,5 @@
 // scfq_reads_host.hpp — internal: the host side the pipelines that write reads (fq-merge, fq-trim, fq-screen, fq-demux, fq-normalize,
-// fq-complexity, fq-rmdup) share, between the scaffold of every record pipeline (scfq_scratch.hpp) and their own kernels: the units of
+// fq-complexity, fq-rmdup, fq-repair) share, between the scaffold of every record pipeline (scfq_scratch.hpp) and their own kernels: the units of
 // the inputs, the scans over the groups' lengths, where the outputs go and how they leave.  Every function takes the pipeline's
 // thread-local error buffer (kErrBytes) as errbuf.
 #pragma once
@@ -26,7 +26,7 @@ enum class Mode { single, two, interleaved };
 // one output of a call: `want` it, and then the caller's device memory (p, cap) or, with own_outputs, pool memory that place_outputs
 // takes by the size the scan reports (own[k]; cap is then the caller's host capacity, checked all the same)
 struct Dest { uint8_t* p; uint64_t cap; bool want; };
-constexpr int kMaxOutputs = 3;
+constexpr int kMaxOutputs = 4;
 constexpr const char* kOutNames[2] = {"out1", "out2"};
 
 // after a failure kernels that read the second input may still be queued on the first one's stream: they are waited for before the
@@ -70,7 +70,7 @@ struct GroupScan {
   const hipStream_t stream;
   char* const errbuf;
   DevBuf &len_, &off_;                           // the caller's, declared among its other buffers: pool memory goes back in that order
-  uint64_t total[kMaxOutputs] = {0, 0, 0};      // the outputs' sizes: read_totals, once the stream has been waited for
+  uint64_t total[kMaxOutputs] = {0, 0, 0, 0};    // the outputs' sizes: read_totals, once the stream has been waited for
 
   GroupScan(int rows_, uint64_t n_groups_, DevBuf& group_len, DevBuf& group_off, hipStream_t stream_, char* errbuf_)
       : rows(rows_), n_groups(n_groups_), row(n_groups_ + 1), stream(stream_), errbuf(errbuf_), len_(group_len), off_(group_off) {}
@@ -115,7 +115,7 @@ struct Placement {
 };
 inline Placement place_outputs(const GroupScan& gs, const char* const* names, const Dest* dst, bool own_outputs, bool check_caps, bool hold_back, DevBuf* own,
                                hipStream_t stream, char* errbuf) {
-  Placement put = {{{nullptr, 0}, {nullptr, 0}, {nullptr, 0}}, SCFQ_OK, SCFQ_OK};
+  Placement put = {{{nullptr, 0}, {nullptr, 0}, {nullptr, 0}, {nullptr, 0}}, SCFQ_OK, SCFQ_OK};
   int small = -1;
   for (int k = gs.rows - 1; k >= 0; --k)
     if (check_caps && dst[k].want && gs.total[k] > dst[k].cap) small = k;

@@ -68,6 +68,8 @@ EXPORTS = [
     "scfq_debug_cplx_stages",
     "scfq_rmdup_buffers", "scfq_rmdup_files", "scfq_format_rmdup_stats_tsv", "scfq_format_rmdup_rec_tsv", "scfq_rmdup_error_detail",
     "scfq_debug_rmdup_stages",
+    "scfq_repair_buffers", "scfq_repair_files", "scfq_format_repair_stats_tsv", "scfq_format_repair_rec_tsv", "scfq_repair_error_detail",
+    "scfq_debug_repair_stages",
     "scfq_fa_index_buffer", "scfq_fa_index_file", "scfq_fa_contig_at", "scfq_fa_contig_find", "scfq_fa_count_intervals",
     "scfq_fa_index_free", "scfq_fa_error_detail", "scfq_fa_parse_window", "scfq_fa_gc_interval", "scfq_format_fa_gc_value",
     "scfq_debug_fa_stages",
@@ -413,6 +415,24 @@ class RmdupStats(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in RMDUP_STATS_FIELDS]
 
 
+SCFQ_REPAIR_SINGLE = 0xFFFFFFFF
+REPAIR_OUTPUTS = ("out1", "out2", "singles1", "singles2")
+REPAIR_STATS_FIELDS = ("struct_size", "abi_version", "reads1", "reads2", "lines1", "lines2", "input_bytes1", "input_bytes2", "pairs", "singles1", "singles2",
+                       "moved", "in_step", "repeated1", "repeated2", "collisions", "rounds", "path", "out1_bytes", "out2_bytes", "singles1_bytes",
+                       "singles2_bytes", "flags", "hash_bits")
+REPAIR_HASH_FIELDS = ("collisions", "rounds", "path")      # the three that depend on the hash or on the fast path
+
+
+class RepairOpts(ctypes.Structure):
+    """scfq_repair_opts (32 bytes)"""
+    _fields_ = [("struct_size", ctypes.c_uint64), ("flags", ctypes.c_uint32), ("hash_bits", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 4)]
+
+
+class RepairStats(ctypes.Structure):
+    """scfq_repair_stats (24 uint64)"""
+    _fields_ = [(n, ctypes.c_uint64) for n in REPAIR_STATS_FIELDS]
+
+
 FA_SUMMARY_FIELDS = ("struct_size", "abi_version", "input_bytes", "tiles", "contigs", "bases", "gc_bases", "acgt_bases", "orphan_bases")
 
 
@@ -638,6 +658,13 @@ def lib():
         L.scfq_format_rmdup_rec_tsv.argtypes = [ctypes.c_uint64, vp, ctypes.c_char_p, ctypes.c_uint64]
         L.scfq_rmdup_error_detail.restype = ctypes.c_char_p
         L.scfq_debug_rmdup_stages.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]
+        L.scfq_repair_buffers.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_int, vp, vp, ctypes.c_uint64] + [vp, ctypes.c_uint64] * 4 + [
+            ctypes.c_int, vp]
+        L.scfq_repair_files.argtypes = [ctypes.c_char_p, ctypes.c_char_p, vp, vp] + [ctypes.c_int] * 5 + [vp]
+        L.scfq_format_repair_stats_tsv.argtypes = [vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_uint64]
+        L.scfq_format_repair_rec_tsv.argtypes = [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_uint64]
+        L.scfq_repair_error_detail.restype = ctypes.c_char_p
+        L.scfq_debug_repair_stages.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]
         L.scfq_fa_index_buffer.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, pvp, ctypes.POINTER(FaSummary)]
         L.scfq_fa_index_file.argtypes = [ctypes.c_char_p, ctypes.c_void_p, pvp, ctypes.POINTER(FaSummary)]
         L.scfq_fa_contig_at.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(FaContig)]
@@ -1981,6 +2008,97 @@ def rmdup_stages():
     the first are HIP-event times, zeros unless SCFQ_RMDUP_TIMING=1 is in the environment"""
     ms = (ctypes.c_double * 7)()
     lib().scfq_debug_rmdup_stages(ms, 7)
+    return list(ms)
+
+
+def repair_opts(hash_bits=0, flags=0, reserved=(0, 0, 0, 0)):
+    """scfq_repair_opts.  hash_bits: 0 (the library's default) or the bits of the name hash that are sorted; every flag bit is reserved"""
+    o = RepairOpts()
+    o.struct_size = ctypes.sizeof(RepairOpts)
+    o.flags, o.hash_bits = flags, hash_bits
+    for k in range(4):
+        o.reserved[k] = reserved[k]
+    return o
+
+
+def _repair_call(fn, what, args):
+    """Returns RepairStats.  An ScfqError carries the stats as `stats` (complete when an output or the table was too small)."""
+    s = RepairStats()
+    s.struct_size = ctypes.sizeof(RepairStats)
+    rc = fn(*args, ctypes.byref(s))
+    if rc != 0:
+        e = ScfqError(rc, what, lib().scfq_repair_error_detail().decode() or lib().scfq_last_error_detail().decode())
+        e.stats = s
+        raise e
+    return s
+
+
+def _repair_outputs(outs):
+    """four (address, capacity) pairs or None -> the eight arguments"""
+    outs = tuple(outs or ()) + (None,) * (4 - len(outs or ()))
+    return _trim_outputs(outs)
+
+
+def repair_resident(ptr1, n1, ptr2, n2, opts=None, outs=None, table=None):
+    """fq-repair of two device-resident FASTQs (the pointer rules of trim_device; not named *_device: tests/_caller_cases.py lists the
+    wrappers of that name, and this one's caller-stream and thread tests are tests/test_gpu_repair_callers.py's).  outs: up to four
+    (device address, capacity) or None, in the order of REPAIR_OUTPUTS; table: (device address, words) of the per-record table or None.
+    Returns RepairStats."""
+    return _repair_call(lib().scfq_repair_buffers, "scfq_repair_buffers",
+                        [ctypes.c_void_p(ptr1) if ptr1 else None, n1, ctypes.c_void_p(ptr2) if ptr2 else None, n2, 1, _opts_ref(opts),
+                         ctypes.c_void_p(table[0]) if table else None, table[1] if table else 0] + _repair_outputs(outs) + [1])
+
+
+def repair_host(data1, data2, opts=None, caps=None, table_cap=None, want=(True, True, True, True)):
+    """fq-repair of two host buffers.  caps: the four capacities (None in it: that output is left out), or None: a sizing call first and
+    then the outputs in `want` at their sizes; table_cap: the words of the per-record table (None: reads1 + reads2, 0: no table).
+    Returns (RepairStats, table, [out1, out2, singles1, singles2]): table a numpy uint32 array or None, the outputs as bytes or None."""
+    import numpy as np
+    a1, n1, keep1 = _host_ptr(data1)
+    a2, n2, keep2 = _host_ptr(data2)
+    head = [a1, n1, a2, n2, 0, _opts_ref(opts)]
+    fn = lib().scfq_repair_buffers
+    if caps is None or table_cap is None:
+        s = _repair_call(fn, "scfq_repair_buffers", head + [None, 0] + [None, 0] * 4 + [0])
+        if caps is None:
+            caps = [getattr(s, n + "_bytes") if w else None for n, w in zip(REPAIR_OUTPUTS, want)]
+        if table_cap is None:
+            table_cap = int(s.reads1 + s.reads2)
+    table = np.zeros(max(table_cap, 1), dtype=np.uint32) if table_cap else None
+    bufs = [None if c is None else ctypes.create_string_buffer(max(int(c), 1)) for c in caps]
+    outs = [None if b is None else (ctypes.addressof(b), int(c)) for b, c in zip(bufs, caps)]
+    s = _repair_call(fn, "scfq_repair_buffers", head + [table.ctypes.data if table_cap else None, table_cap] + _repair_outputs(outs) + [0])
+    sizes = [getattr(s, n + "_bytes") for n in REPAIR_OUTPUTS]
+    return s, (table[:int(s.reads1 + s.reads2)] if table_cap else None), [None if b is None else b.raw[:int(k)] for b, k in zip(bufs, sizes)]
+
+
+def repair_files(path1, path2, opts=None, out1_fd=-1, out2_fd=-1, singles1_fd=-1, singles2_fd=-1, per_read_fd=-1):
+    """A descriptor below 0: that output is not produced.  Returns RepairStats"""
+    return _repair_call(lib().scfq_repair_files, "scfq_repair_files",
+                        [os.fsencode(path1) if path1 is not None else None, os.fsencode(path2) if path2 is not None else None, _opts_ref(opts), None,
+                         out1_fd, out2_fd, singles1_fd, singles2_fd, per_read_fd])
+
+
+def format_repair_stats_tsv(s, header=False):
+    buf = ctypes.create_string_buffer(1024)
+    n = lib().scfq_format_repair_stats_tsv(ctypes.byref(s) if s is not None else None, 1 if header else 0, buf, 1024)
+    if n < 0:
+        raise ScfqError(n, "scfq_format_repair_stats_tsv")
+    return buf.value.decode()
+
+
+def format_repair_rec_tsv(which, record=0, mate=SCFQ_REPAIR_SINGLE):
+    """which: 1 or 2, the input of the record; 0: the column names"""
+    buf = ctypes.create_string_buffer(96)
+    lib().scfq_format_repair_rec_tsv(which, record, mate, buf, 96)
+    return buf.value.decode()
+
+
+def repair_stages():
+    """(line indexes, P1, the positional check, P2, sort, rounds, mates, lengths with their scans, W1 + W2) milliseconds of this thread's last
+    fq-repair call; all but the first are HIP-event times, zeros unless SCFQ_REPAIR_TIMING=1 is in the environment"""
+    ms = (ctypes.c_double * 9)()
+    lib().scfq_debug_repair_stages(ms, 9)
     return list(ms)
 
 
